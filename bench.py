@@ -7,13 +7,18 @@ One "step" = one batch of B queries through the whole hot path with inputs resid
 Workload (BASELINE.json: the metric is quoted on the 1M-node KG): configs[2] =
   synthetic 1M-node / 10M-edge KG, 1M x 768 bf16 embeddings, batch 256, 20 PPR iterations.
 
-    python bench.py [--gpus N --steps K --warmup W] [--config cfg2|cfg3|cfg4]
+    python bench.py [--gpus N --steps K --warmup W] [--config cfg2|cfg3|cfg4] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (N > 1, external launcher)
 
 N > 1 without a launcher (no WORLD_SIZE in the environment): bench.py spawns its own N ranks, one per GPU
 (hipporag_amd/launch.py), and prints rank 0's line: `value` = the row-sharded leg (BASELINE.json's layout) when it is
 parity-green, `value_hybrid` / `value_replica` beside it, and -- on the default configs[2] workload -- `configs3_strong`
 = BASELINE configs[3] (global batch 1024 on the same index).  Prints ONE JSON line (rank 0), last.
+
+On one GPU a plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, the
+PPR residual the timed steps left); `--full` adds everything else on the same engine: the convergence-contract and
+accelerated-stage legs, per-step HIP-event times, the phase breakdown, the roofline and the CPU baselines with the
+oracle parity spot check.  `--dump-outputs DIR` writes what the last timed step returned (DIR/<name>.npy).
 """
 
 from __future__ import annotations
@@ -102,6 +107,27 @@ def load_traffic():
         except Exception:
             return None
     return None
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: the arrays the last timed step handed its caller, one DIR/<name>.npy each -- scores as float32, ids /
+    flags / counts as float64 (exact).  The inputs are seeded, so two builds run with the same arguments can be compared
+    output for output."""
+    host = {}
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        a = t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+        host[name] = a.astype(np.float32 if a.dtype.kind == "f" else np.float64)
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_BUDGET_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs exceed the {DUMP_BUDGET_BYTES}-byte budget")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
 
 
 def _time_launches(fn, n_l):
@@ -573,9 +599,11 @@ def bench_shard_share(args, cfg, dev):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.warmup, n):
-        step(i)
+        o = step(i)
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(zip(("doc_ids", "doc_scores", "flags"), o[:3])))
     lay = eng.shard_layout(B, args.exchange_groups)
     rps = sidx.rows_per_shard
     nnz_own = int(sidx.csr.row_ptr[rps] - sidx.csr.row_ptr[0])
@@ -648,6 +676,11 @@ def main():
                     help="tolerance of the secondary leg that runs under the convergence contract (the headline runs "
                          "BASELINE.json's fixed 20 sweeps and reports the residual they leave)")
     ap.add_argument("--ppr-max-iters", type=int, default=29)
+    ap.add_argument("--full", action="store_true",
+                    help="one GPU: besides the headline, the convergence-contract and accelerated legs, per-step HIP-event "
+                         "times, the phase breakdown, the roofline and the CPU baselines + oracle parity (off: headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 scores, float64 ids / flags)")
     args = ap.parse_args()
     args.locality = None if args.locality == "none" else args.locality
 
@@ -663,13 +696,18 @@ def main():
         return self_spawn(args.gpus, os.path.abspath(__file__), sys.argv[1:])
 
     import torch
-    from hipporag_amd import synth
+    from hipporag_amd import _lib, synth
     from hipporag_amd.engine import HippoRAGEngine
+
+    # the library build() left, as it is: a benchmark compiles nothing and needs no write access to the tree
+    _lib.load(build_if_missing=False)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if args.gpus > 1 or world > 1 or os.environ.get("HRAG_FORCE_DIST"):   # env: exercise the N>1 code on 1 GPU
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: one GPU only (the N > 1 harness does not write outputs)")
         import bench_dist
         return bench_dist.bench_main(args, CONFIGS, rank, local_rank, world, roofline_fn=measure_roofline)
 
@@ -680,6 +718,8 @@ def main():
     cfg = CONFIGS[args.config]
     V, E, D, B, seed = cfg["V"], cfg["E"], cfg["D"], args.batch or cfg["B"], cfg["seed"]
     if cfg.get("local_shards"):
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: --config cfg4local is a parity run without timed steps")
         return bench_local_shards(args, cfg, dev)
     if cfg.get("shard_of"):
         return bench_shard_share(args, cfg, dev)
@@ -731,13 +771,15 @@ def main():
         # SURVEY 8(d)'s median of per-step HIP-event times, in a loop of its own AFTER the wall-clock region (an event
         # per step inside it cost sporadic 7-26 ms stalls on the small configurations); events on torch's current
         # stream = the stream the library launches on
-        marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
-        marks[0].record()
-        for i in range(args.warmup, n_batches):
-            step(i, tol, max_iters)
-            marks[i - args.warmup + 1].record()
-        torch.cuda.synchronize()
-        per_step = sorted(a.elapsed_time(b) for a, b in zip(marks[:-1], marks[1:]))
+        per_step = []
+        if args.full:
+            marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+            marks[0].record()
+            for i in range(args.warmup, n_batches):
+                step(i, tol, max_iters)
+                marks[i - args.warmup + 1].record()
+            torch.cuda.synchronize()
+            per_step = sorted(a.elapsed_time(b) for a, b in zip(marks[:-1], marks[1:]))
         from hipporag_amd._lib import PPR_ERR_FLOOR_F16, PPR_ERR_FLOOR_FP8, PPR_ERR_K
         res_max = float(torch.stack(res).max())
         floor = PPR_ERR_FLOOR_FP8 if B > 64 else PPR_ERR_FLOOR_F16
@@ -761,6 +803,46 @@ def main():
     out, elapsed, contract = timed()                                    # BASELINE.json: exactly 20 PPR iterations
     ms_per_step = elapsed * 1e3 / max(args.steps, 1)
     qps = B * args.steps / elapsed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"doc_ids": out.doc_idx, "doc_scores": out.doc_score, "flags": out.flags,
+                                         "residual": out.residual, "sweeps_used": out.iters_used})
+    slab_width = eng.timings()["slab_width"]                            # the state the timed steps ran on
+    f8, f16 = slab_width == 128, slab_width == 64 and B > 32
+    result = {
+        "metric": "retrieval_queries_per_sec", "value": qps, "unit": "queries/s", "n_gpus": 1,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": cfg["label"], "V": V, "E": E, "nnz": kg.csr.nnz, "n_passages": kg.n_passages,
+                   "n_facts": kg.n_facts, "dim": D, "global_batch": B, "ppr_iters": PPR_ITERS,
+                   "linking_top_k": K_F, "retrieval_top_k": K_P, "damping": DAMPING,
+                   "embedding_dtype": "fp16" if cfg.get("fp16") else "bf16",
+                   "ppr_state_dtype": ("e4m3 staged corrections + fp32 true residual (fp32 arithmetic)" if f8 else
+                                       "f16 hi + f16 correction (fp32 arithmetic)" if f16 else "f32"),
+                   "sell_sigma": args.sell_sigma, "engine_flags": args.engine_flags, "locality": args.locality,
+                   "locality_score_after_renumbering": eng.locality_score, "vertex_numbering": eng.numbering,
+                   "engine_opt_flags": eng.opt_flags,
+                   "parallelism": "1gpu"},
+    }
+    step_ms = {"step_ms_median_hip_events": contract.pop("step_ms_median_hip_events"),
+               "step_ms_min_max_hip_events": contract.pop("step_ms_min_max_hip_events")}
+    result["ppr_contract"] = contract
+    result["setup_s"] = setup_s
+    # hrag_engine_stats: device bytes of the shareable index / of this handle's workspace, PPR state types, the state
+    # the last call ran on (8 = staged e4m3), why no e4m3 state if there is none
+    result["engine_stats"] = (lambda st: {k: st[k] for k in ("index_bytes", "workspace_bytes", "ppr_states", "last_ppr_state",
+                                                              "fp8_unavailable", "fp8_unavailable_reasons")})(eng.stats())
+    if args.full:
+        result.update(step_ms)
+        full_legs(args, eng, kg, V, D, B, fact_emb, pass_emb, qf, qp, cnt, n_batches, step, timed, out, qps, result)
+    eng.close()
+    print(json.dumps(result))
+    return 0
+
+
+def full_legs(args, eng, kg, V, D, B, fact_emb, pass_emb, qf, qp, cnt, n_batches, step, timed, out, qps, result):
+    """--full: the secondary legs on the engine of the headline, added to `result`."""
+    import torch
     if args.ppr_tol > 0:
         _, el_c, contract_c = timed(args.ppr_tol, args.ppr_max_iters)   # the mirror's default: the convergence contract
         contract_c.update({"value": B * args.steps / el_c, "unit": "queries/s", "ms_per_step": el_c * 1e3 / max(args.steps, 1)})
@@ -800,27 +882,10 @@ def main():
     phases = sorted(runs, key=lambda t: t["ppr_ms"])[len(runs) // 2]
     eng.set_profiling(False)
 
-    roofline, f8, f16 = measure_roofline(eng, kg, V, B, phases, args.config, args.sweep_launches)
-    nnz = kg.csr.nnz
-    result = {
-        "metric": "retrieval_queries_per_sec", "value": qps, "unit": "queries/s", "n_gpus": 1,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-        "data": "synthetic",
-        "config": {"workload": cfg["label"], "V": V, "E": E, "nnz": nnz, "n_passages": kg.n_passages,
-                   "n_facts": kg.n_facts, "dim": D, "global_batch": B, "ppr_iters": PPR_ITERS,
-                   "linking_top_k": K_F, "retrieval_top_k": K_P, "damping": DAMPING,
-                   "embedding_dtype": "fp16" if cfg.get("fp16") else "bf16",
-                   "ppr_state_dtype": ("e4m3 staged corrections + fp32 true residual (fp32 arithmetic)" if f8 else
-                                       "f16 hi + f16 correction (fp32 arithmetic)" if f16 else "f32"),
-                   "sell_sigma": args.sell_sigma, "engine_flags": args.engine_flags, "locality": args.locality,
-                   "locality_score_after_renumbering": eng.locality_score, "vertex_numbering": eng.numbering,
-                   "engine_opt_flags": eng.opt_flags,
-                   "parallelism": "1gpu"},
+    roofline, _, _ = measure_roofline(eng, kg, V, B, phases, args.config, args.sweep_launches)
+    result.update({
         "roofline": roofline,
-        "step_ms_median_hip_events": contract.pop("step_ms_median_hip_events"),
-        "step_ms_min_max_hip_events": contract.pop("step_ms_min_max_hip_events"),
-        "ppr_contract": contract, "with_convergence_contract": contract_c, "with_accelerated_stages": accel,
+        "with_convergence_contract": contract_c, "with_accelerated_stages": accel,
         "phases_ms": {k: phases[k] for k in ("fact_sim_ms", "pass_sim_ms", "seed_ms", "ppr_ms", "rank_ms", "total_ms")},
         "sim_algorithmic_bytes": sim_algorithmic_bytes(kg.n_facts, kg.n_passages, D, B),
         # the similarity stage against ITS roofline -- max(HBM time, MFMA time) of the algorithmic
@@ -833,12 +898,8 @@ def main():
             "peaks": "8.0 TB/s HBM, 2.5 PFLOP/s dense bf16 MFMA (MI355X_MICROARCH.md)"})(
                 sim_algorithmic_bytes(kg.n_facts, kg.n_passages, D, B), 2.0 * B * (kg.n_facts + kg.n_passages) * D,
                 phases["fact_sim_ms"] + phases["pass_sim_ms"]),
-        "n_long_rows": phases["n_long_rows"], "setup_s": setup_s,
-        # hrag_engine_stats: device bytes of the shareable index / of this handle's workspace, PPR state types, the state
-        # the last call ran on (8 = staged e4m3), why no e4m3 state if there is none
-        "engine_stats": (lambda st: {k: st[k] for k in ("index_bytes", "workspace_bytes", "ppr_states", "last_ppr_state",
-                                                         "fp8_unavailable", "fp8_unavailable_reasons")})(eng.stats()),
-    }
+        "n_long_rows": phases["n_long_rows"],
+    })
     if not args.no_cpu_baseline:
         last = n_batches - 1
         also = ({"with_accelerated_stages": (out_a.doc_idx.cpu().numpy(), out_a.doc_score.cpu().numpy())}
@@ -856,9 +917,6 @@ def main():
         result["speedup_vs_cpu_port"] = qps / cb["value"]
         if "value" in cb.get("vectorised", {}):
             result["speedup_vs_cpu_vectorised"] = qps / cb["vectorised"]["value"]
-    eng.close()
-    print(json.dumps(result))
-    return 0
 
 
 if __name__ == "__main__":

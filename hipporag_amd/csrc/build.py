@@ -55,6 +55,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     temporary name and renamed into place, so a peer never dlopens a half-written file and the ranks that waited
     find everything up to date."""
     hipcc = _hipcc()
+    if not force and _up_to_date():
+        return LIB          # nothing to compile: no lock taken, so a tree the caller cannot write loads what build() left
     os.makedirs(OBJ_DIR, exist_ok=True)
     with open(os.path.join(OBJ_DIR, ".lock"), "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
@@ -62,6 +64,18 @@ def build(force: bool = False, verbose: bool = False) -> str:
             return _build_locked(hipcc, force, verbose)
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
+
+
+def _object_current(src: str, hdr_digest: str) -> bool:
+    obj = os.path.join(OBJ_DIR, src + ".o")
+    stamp = obj + ".sha"
+    return os.path.exists(obj) and os.path.exists(stamp) and open(stamp).read() == _digest([os.path.join(HERE, src)]) + hdr_digest
+
+
+def _up_to_date() -> bool:
+    """What _build_locked would leave alone: every object stamped with its current digest, and the library linked."""
+    hdr_digest = _digest(HEADERS)
+    return os.path.exists(LIB) and all(_object_current(src, hdr_digest) for src in SOURCES)
 
 
 def _build_locked(hipcc: str, force: bool, verbose: bool) -> str:
@@ -72,7 +86,7 @@ def _build_locked(hipcc: str, force: bool, verbose: bool) -> str:
         obj = os.path.join(OBJ_DIR, src + ".o")
         stamp = obj + ".sha"
         want = _digest([src_path]) + hdr_digest
-        if not force and os.path.exists(obj) and os.path.exists(stamp) and open(stamp).read() == want:
+        if not force and _object_current(src, hdr_digest):
             return obj, False
         tmp = obj + f".tmp{os.getpid()}"
         cmd = [hipcc, *FLAGS, "-x", "hip", "-c", src_path, "-o", tmp]

@@ -12,7 +12,7 @@ cd "$REPO"
 ( time timeout 1500 python -m pytest tests -q -m gpu --maxfail=12 --tb=short --durations=8 ) > "$OUT/gpu_tests.log" 2>&1
 tail -16 "$OUT/gpu_tests.log"
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1; tail -1 "$OUT/smoke.log"
-timeout 900 python bench.py --steps 20 --warmup 5 > "$OUT/bench_cfg3.json" 2> "$OUT/bench_cfg3.err"
+timeout 900 python bench.py --full --steps 20 --warmup 5 > "$OUT/bench_cfg3.json" 2> "$OUT/bench_cfg3.err"
 python - "$TAG" <<'P'
 import json,sys
 d=json.load(open(f"gpurun_out/{sys.argv[1]}/bench_cfg3.json")); r=d["roofline"]
@@ -22,7 +22,7 @@ print("cfg3:", round(d["value"]), d["ms_per_step"], "frac", r["frac"], "harness"
       "accel", d["with_accelerated_stages"].get("value"), d["with_accelerated_stages"].get("with_convergence_contract",{}).get("value"))
 P
 for CFG in cfg1s cfg2; do
-  timeout 600 python bench.py --config $CFG --steps 50 --warmup 5 --cpu-queries 16 > "$OUT/bench_$CFG.json" 2> "$OUT/bench_$CFG.err"
+  timeout 600 python bench.py --full --config $CFG --steps 50 --warmup 5 --cpu-queries 16 > "$OUT/bench_$CFG.json" 2> "$OUT/bench_$CFG.err"
   python - "$TAG" "$CFG" <<'P'
 import json,sys
 d=json.load(open(f"gpurun_out/{sys.argv[1]}/bench_{sys.argv[2]}.json"))
@@ -30,7 +30,7 @@ print(sys.argv[2], round(d["value"]), d["roofline"]["frac"], d["parity_spot_chec
 P
 done
 for LOC in none auto; do
-  timeout 600 python bench.py --config real2wiki --locality $LOC --steps 20 --warmup 5 --cpu-queries 6 --cpu-budget-s 15 --cpu-vec-queries 8 > "$OUT/bench_real2wiki_$LOC.json" 2> "$OUT/bench_real2wiki_$LOC.err"
+  timeout 600 python bench.py --full --config real2wiki --locality $LOC --steps 20 --warmup 5 --cpu-queries 6 --cpu-budget-s 15 --cpu-vec-queries 8 > "$OUT/bench_real2wiki_$LOC.json" 2> "$OUT/bench_real2wiki_$LOC.err"
   python - "$TAG" "$LOC" <<'P'
 import json,sys
 d=json.load(open(f"gpurun_out/{sys.argv[1]}/bench_real2wiki_{sys.argv[2]}.json")); r=d["roofline"]

@@ -7,8 +7,11 @@ queried by the reference's own code (tests/golden/ref_harness.py: everything rea
 whose PageRank is oracle/prpack_port.c, the LLM steps and the embedding model), and every stage the reference produced --
 fact scores, candidates, reset vectors, run_ppr rankings, retrieve() and retrieve_dpr() results -- is checked against the
 oracle with the assertions of tests/test_ref_golden.py.  The committed fixtures are three such cases; this widens the pin.
+--record FILE keeps what the reference produced for every case; --replay FILE checks the oracle against such a recording
+instead of running the reference (same --cases / --seed: the corpora and configurations come from the same generator), which
+is how tests/test_ref_golden.py runs it on tests/golden/ref_soak_oracle_s11.npz.
 
-    python tools/soak_oracle_vs_reference.py [--cases 40] [--seed 1]"""
+    python tools/soak_oracle_vs_reference.py [--cases 40] [--seed 1] [--record FILE | --replay FILE]"""
 import argparse
 import json
 import os
@@ -28,11 +31,14 @@ def main():
     ap.add_argument("--cases", type=int, default=40)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "soak_oracle_vs_reference.json"))
+    ap.add_argument("--record", default=None, help="write the reference's output of every case to this .npz")
+    ap.add_argument("--replay", default=None, help="check against the reference outputs recorded in this .npz")
     args = ap.parse_args()
     import ref_harness as rh
-    if not rh.reference_available():
+    if not args.replay and not rh.reference_available():
         print("the reference sources are not present: nothing to do")
         return 0
+    recorded = dict(np.load(args.replay)) if args.replay else {}
     import make_ref_golden as mg
     from tests import test_ref_golden as trg
     import oracle
@@ -75,8 +81,14 @@ def main():
         par = dict(n_docs=n_docs, n_ent=n_ent, seed=seed, filter=mode, **cfg)
         t0 = time.time()
         try:
-            docs, triples, queries = mg.synth_corpus(n_docs, n_ent, seed)
-            out = mg.run_case(f"soak{n}", docs, triples, queries, mode, save=False, **cfg)
+            if args.replay:
+                out = {k.split("__", 1)[1]: v for k, v in recorded.items() if k.startswith(f"c{n}__")}
+                assert out, f"case {n} is not in {args.replay}"
+            else:
+                docs, triples, queries = mg.synth_corpus(n_docs, n_ent, seed)
+                out = mg.run_case(f"soak{n}", docs, triples, queries, mode, save=False, **cfg)
+                if args.record:
+                    recorded.update({f"c{n}__{k}": np.asarray(v) for k, v in out.items()})
             trg.load = lambda case, _o=out: _o
             failed = []
             for chk in checks:
@@ -94,6 +106,8 @@ def main():
         bad += 0 if par["ok"] else 1
         print("ok  " if par["ok"] else "FAIL", json.dumps(par), flush=True)
         rows.append(par)
+    if args.record:
+        np.savez_compressed(args.record, **recorded)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     json.dump({"cases": rows, "failed": bad}, open(args.out, "w"), indent=0)
     print(f"{len(rows)} cases;", "SOAK OK" if bad == 0 else f"SOAK FAILED ({bad})")
