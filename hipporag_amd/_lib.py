@@ -112,6 +112,8 @@ SIGNATURES = {
     "hrag_sim_scores": (C.c_int, [_P, _I32, _P, _I32, _P, _P]),
     "hrag_ppr": (C.c_int, [_P, _P, _I32, _F32, _I32, _P, _P, _P]),
     "hrag_topk_rows": (C.c_int, [_P, _I32, _I64, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
+    "hrag_topk_rows_workspace_bytes": (C.c_int64, [_I32, _I64, _I32]),
+    "hrag_topk_rows_ws": (C.c_int, [_P, _I32, _I64, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "hrag_ppr_sweeps": (C.c_int, [_P, _I32, _I32, _F32, _I32, _P]),
     "hrag_ppr_layout": (C.c_int, [_P, _I32, C.POINTER(_I32), C.POINTER(_I32)]),
     "hrag_row_minmax": (C.c_int, [_P, _I32, _I64, _I64, _P, _P, _P]),

@@ -456,6 +456,14 @@ hrag_status launch_row_topk(const float *scores, int32_t batch, int64_t n, int64
                             size_t ws_bytes = 0);
 hrag_status launch_row_minmax(const float *scores, int32_t batch, int64_t n, int64_t ld,
                               float *mn_out, float *mx_out, hipStream_t s, float *sum_out = nullptr);
+// K4' (topk.hip): the same ranking and output for any k > kTopkMax.  kk = min(k, n) <= kLargeTile keys are selected,
+// sorted and written by one kernel without workspace; larger kk take topk_large_ws_bytes of 8-byte aligned workspace
+// (two key buffers of batch x round_up(kk, kLargeTile) + the row min / max)
+constexpr int kLargeTile = 16384;   // keys per LDS sort (128 KiB)
+int64_t topk_large_ws_bytes(int32_t batch, int64_t n, int32_t k);
+hrag_status launch_row_topk_large(const float *scores, int32_t batch, int64_t n, int64_t ld, int32_t k,
+                                  int32_t idx_offset, TopkNorm norm, int32_t *idx_out, float *val_out, float *mn_out,
+                                  float *mx_out, hipStream_t s, void *ws, size_t ws_bytes);
 
 // knn.hip : fp32 rows -> the 3 * dim bf16 layout of HRAG_F32_SPLIT engines ([hi | lo | hi]; queries [hi | hi | lo])
 hrag_status launch_split3(const float *x, int64_t rows, int32_t dim, int32_t as_query, uint16_t *out, hipStream_t s,

@@ -32,7 +32,7 @@ static void workspace_ptrs(hrag_engine *e, std::vector<void **> &out) {
                      (void **)&e->d_colsum_partial, (void **)&e->d_sums, (void **)&e->d_partial16, (void **)&e->d_h16[0],
                      (void **)&e->d_h16[1], (void **)&e->d_h16[2], (void **)&e->d_h16[3], (void **)&e->d_tele16,
                      (void **)&e->d_row_slot, (void **)&e->d_qscale, (void **)&e->d_ssum, (void **)&e->d_tele_sv,
-                     (void **)&e->d_partial_sv, (void **)&e->d_topk_ws, (void **)&e->d_R8, (void **)&e->d_rho8,
+                     (void **)&e->d_partial_sv, (void **)&e->d_topk_ws, (void **)&e->d_topk_large, (void **)&e->d_R8, (void **)&e->d_rho8,
                      (void **)&e->d_partial8, (void **)&e->d_fused_ws, (void **)&e->d_mn_f, (void **)&e->d_mx_f,
                      (void **)&e->d_fused_sel, (void **)&e->d_xp8, (void **)&e->d_colmask, (void **)&e->d_stagep,
                      (void **)&e->d_pool8[0], (void **)&e->d_pool8[1], (void **)&e->d_pool8[2], (void **)&e->d_sv16[0],
@@ -686,6 +686,15 @@ static hrag_status alloc_workspace(hrag_engine *e) {
         HRAG_TRY(dev_alloc(&ws, (int64_t)kTopkWsBytes));
         e->d_topk_ws = ws;
     }
+    // per-call since ABI 0.8's workspaces: the fp32 queries of a split engine in the [hi | hi | lo] layout
+    if (e->split) HRAG_TRY(dev_alloc(&e->d_qsplit, (int64_t)B * e->kdim));
+    // K4' scratch of the final rankings beyond kTopkMax (none for max_topk <= kTopkMax: those engines keep their footprint)
+    e->topk_large_bytes = e->max_topk > kTopkMax ? topk_large_ws_bytes(B, std::max<int64_t>(e->p_rows, 1), e->max_topk) : 0;
+    if (e->topk_large_bytes > 0) {
+        char *ws = nullptr;
+        HRAG_TRY(dev_alloc(&ws, e->topk_large_bytes));
+        e->d_topk_large = ws;
+    }
     if (e->state_elems) {
         HRAG_HIP_TRY(hipMemset(e->d_x, 0, (size_t)e->state_elems * sizeof(float)));
         HRAG_HIP_TRY(hipMemset(e->d_y, 0, (size_t)e->state_elems * sizeof(float)));
@@ -732,7 +741,7 @@ hrag_status hrag_engine_create(const hrag_graph_desc *g, const hrag_embed_desc *
                             fd->obj_vertex && fd->num_chunks),
                  "fact shard outside [0, n_facts) or fact_desc arrays missing");
     HRAG_REQUIRE(opts->max_batch >= 1, "max_batch must be >= 1");
-    HRAG_REQUIRE(opts->max_topk >= 1 && opts->max_topk <= kTopkMax, "max_topk outside [1, %d]", kTopkMax);
+    HRAG_REQUIRE(opts->max_topk >= 1, "max_topk must be >= 1");
     const int sw = opts->slab_width;
     HRAG_REQUIRE(sw == 0 || sw == 4 || sw == 8 || sw == 16 || sw == 32 || sw == 64,
                  "slab_width must be 0 or one of 4, 8, 16, 32, 64");
@@ -961,7 +970,6 @@ hrag_status hrag_engine_create(const hrag_graph_desc *g, const hrag_embed_desc *
     // passages->data == NULL: an engine WITHOUT passage embeddings -- the raw passage scores come from the caller
     // (hrag_retrieve_scored: the PPR side of the hybrid multi-GPU mode, whose embeddings live row-sharded elsewhere)
     if (passages->data) E_TRY(upload_emb(&e->d_pemb, passages->data, e->p_rows, passages->dtype));
-    if (e->split) E_TRY(dev_alloc(&e->d_qsplit, (int64_t)opts->max_batch * e->kdim));
     if (facts) {
         e->f_rows = facts->rows; e->f_offset = facts->row_offset; e->n_facts = fd->n_facts;
         E_TRY(upload_emb(&e->d_femb, facts->data, e->f_rows, facts->dtype));
@@ -1110,6 +1118,21 @@ hrag_status hrag_topk_rows(const float *scores, int32_t batch, int64_t n, int64_
     HRAG_REQUIRE(scores && idx_out && val_out && batch >= 1 && n >= 0 && ld >= n, "bad argument");
     return launch_row_topk(scores, batch, n, ld, k, idx_offset, normalize ? kNormMinMax : kNormNone,
                            idx_out, val_out, mn, mx, (hipStream_t)stream);
+}
+
+int64_t hrag_topk_rows_workspace_bytes(int32_t batch, int64_t n, int32_t k) {
+    return topk_large_ws_bytes(batch, n, k);
+}
+
+hrag_status hrag_topk_rows_ws(const float *scores, int32_t batch, int64_t n, int64_t ld, int32_t k, int32_t idx_offset,
+                              int32_t normalize, int32_t *idx_out, float *val_out, float *mn, float *mx,
+                              void *workspace, size_t workspace_bytes, hrag_stream stream) {
+    HRAG_REQUIRE(scores && idx_out && val_out && batch >= 1 && n >= 0 && ld >= n && k >= 1, "bad argument");
+    const TopkNorm norm = normalize ? kNormMinMax : kNormNone;
+    if (k <= kTopkMax)   // exactly hrag_topk_rows
+        return launch_row_topk(scores, batch, n, ld, k, idx_offset, norm, idx_out, val_out, mn, mx, (hipStream_t)stream);
+    return launch_row_topk_large(scores, batch, n, ld, k, idx_offset, norm, idx_out, val_out, mn, mx, (hipStream_t)stream,
+                                 workspace, workspace_bytes);
 }
 
 hrag_status hrag_score_facts(hrag_engine *e, const uint16_t *q, int32_t batch, int32_t k,
@@ -1396,8 +1419,7 @@ static hrag_status retrieve_impl(hrag_engine *e, const uint16_t *q_pass, const f
                                      lay, s));
     }
     HRAG_TRY(launch_flag_zero_mass(e->d_sums, batch, e->d_flags, 2, s));
-    HRAG_TRY(launch_row_topk(e->d_doc, batch, e->n_passages, e->ld_p, k, 0, kNormNone, doc_idx_out,
-                             doc_score_out, nullptr, nullptr, s, e->d_topk_ws, kTopkWsBytes));
+    HRAG_TRY(rank_rows(e, e->d_doc, batch, e->n_passages, k, 0, kNormNone, doc_idx_out, doc_score_out, s));
     const bool measured = f8 || est != nullptr;
     if (!f8 && est)
         HRAG_TRY(launch_ppr8_finalize(est, e->d_flags, batch, damping / (1.0f - damping), ppr_tol, sweeps_run, e->d_ctl,
@@ -1475,8 +1497,7 @@ hrag_status hrag_dense_retrieve(hrag_engine *e, const uint16_t *q_pass, int32_t 
     e->counters.queries.fetch_add(batch);
     HRAG_TRY(prep_query(e, q_pass, batch, s, &q_pass));
     HRAG_TRY(launch_sim_gemm(e->d_pemb, e->p_rows, e->kdim, q_pass, batch, e->d_spass, e->ld_p, s, 0, e->emb_dtype));
-    return launch_row_topk(e->d_spass, batch, e->n_passages, e->ld_p, k, 0, kNormMinMax, doc_idx_out,
-                           doc_score_out, nullptr, nullptr, s, e->d_topk_ws, kTopkWsBytes);
+    return rank_rows(e, e->d_spass, batch, e->n_passages, k, 0, kNormMinMax, doc_idx_out, doc_score_out, s);
 }
 
 hrag_status hrag_ppr(hrag_engine *e, const float *reset, int32_t batch, float damping, int32_t iters,

@@ -167,6 +167,8 @@ struct hrag_engine {
     float *d_seed_w = nullptr;
     double *d_colsum_partial = nullptr, *d_sums = nullptr;
     void *d_topk_ws = nullptr;   // kTopkWsBytes: lets small batches split a row over several workgroups
+    void *d_topk_large = nullptr;   // max_topk > kTopkMax only: the K4' scratch of a [max_batch, p_rows] ranking
+    int64_t topk_large_bytes = 0;
     // fused fact top-k (sim_gemm.hip): tile max / min, selected tiles, global min / max per query
     float *d_fused_ws = nullptr, *d_mn_f = nullptr, *d_mx_f = nullptr;
     int32_t *d_fused_sel = nullptr;
@@ -302,6 +304,17 @@ struct EngineCall {
 #define HRAG_ENGINE_CALL(e, stream)                 \
     EngineCall _engine_call((e), (hipStream_t)(stream)); \
     if (_engine_call.st != HRAG_OK) return _engine_call.st
+
+// the final ranking of [batch, n] score rows (row stride ld_p): K4 for k <= kTopkMax (unchanged), K4' beyond it in the
+// scratch that alloc_workspace sized for max_batch x max_topk
+inline hrag_status rank_rows(hrag_engine *e, const float *rows, int32_t batch, int64_t n, int32_t k, int32_t idx_offset,
+                             TopkNorm norm, int32_t *idx_out, float *val_out, hipStream_t s) {
+    if (k <= kTopkMax)
+        return launch_row_topk(rows, batch, n, e->ld_p, k, idx_offset, norm, idx_out, val_out, nullptr, nullptr, s,
+                               e->d_topk_ws, kTopkWsBytes);
+    return launch_row_topk_large(rows, batch, n, e->ld_p, k, idx_offset, norm, idx_out, val_out, nullptr, nullptr, s,
+                                 e->d_topk_large, (size_t)e->topk_large_bytes);
+}
 
 // the query matrix as the similarity kernels take it: the caller's pointer, or (HRAG_F32_SPLIT) its fp32 rows split
 // into [hi | hi | lo] in the engine's buffer (one call in flight per engine: include/hrag.h)

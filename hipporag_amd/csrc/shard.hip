@@ -674,8 +674,7 @@ hrag_status hrag_shard_finish(hrag_engine *e, const float *mn, const float *mx, 
         return launch_flag_zero_mass(e->d_sums, batch, flags, 2, s);
     }
     HRAG_TRY(ppr8_doc_scores(e, mn, mx, flags, batch, s, true));
-    HRAG_TRY(launch_row_topk(e->d_doc, batch, e->p_rows, e->ld_p, k, (int32_t)e->p_offset, kNormNone, idx_out,
-                             score_out, nullptr, nullptr, s, e->d_topk_ws, kTopkWsBytes));
+    HRAG_TRY(rank_rows(e, e->d_doc, batch, e->p_rows, k, (int32_t)e->p_offset, kNormNone, idx_out, score_out, s));
     BlitList out;
     out.copy(residual_out, e->d_resid, (int64_t)batch * sizeof(float));
     out.copy(iters_out, e->d_iters_used, (int64_t)batch * sizeof(int32_t));

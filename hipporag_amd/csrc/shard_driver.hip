@@ -112,7 +112,11 @@ hrag_status merge_topk(const hrag_comm *c, const int32_t *lidx, const float *lva
     hipLaunchKernelGGL(merge_prepare_kernel, dim3((unsigned)ceil_div(per * w, 256)), dim3(256), 0, s, gidx, gval, w, batch, k,
                        cidx, cval);
     HRAG_LAUNCH_CHECK();
-    HRAG_TRY(hrag_topk_rows(cval, batch, (int64_t)w * k, (int64_t)w * k, k, 0, 0, pos, tval, nullptr, nullptr, (hrag_stream)s));
+    const int64_t large = topk_large_ws_bytes(batch, (int64_t)w * k, k);   // k > kTopkMax: K4' scratch (0 otherwise)
+    uint64_t *lws = large > 0 ? ws.take<uint64_t>(large / (int64_t)sizeof(uint64_t)) : nullptr;
+    HRAG_REQUIRE(large == 0 || lws, "workspace too small (hrag_shard_workspace_bytes)");
+    HRAG_TRY(hrag_topk_rows_ws(cval, batch, (int64_t)w * k, (int64_t)w * k, k, 0, 0, pos, tval, nullptr, nullptr, lws,
+                               (size_t)large, (hrag_stream)s));
     hipLaunchKernelGGL(merge_finish_kernel, dim3((unsigned)ceil_div(per, 256)), dim3(256), 0, s, pos, tval, cidx, batch, k,
                        w * k, mn, mx, out_idx, out_val);
     HRAG_LAUNCH_CHECK();
@@ -136,6 +140,8 @@ int64_t hrag_shard_workspace_bytes(hrag_engine *e, int32_t world, int32_t batch,
     n += 2 * pad(b * HRAG_SEED_STRIDE * 4) + 3 * pad(b * 4);   // seeds, seed count, flags, sat
     n += 2 * pad(per * 4);                                 // local top-k
     n += 4 * pad(per * world * 4) + 2 * pad(per * 4);      // gathered lists, candidates, merged positions / values
+    const int64_t large = topk_large_ws_bytes(batch, (int64_t)world * k, k);   // k > 2048: the merge's K4' scratch
+    if (large > 0) n += pad(large);
     return n;
 }
 

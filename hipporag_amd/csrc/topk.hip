@@ -356,6 +356,216 @@ __global__ __launch_bounds__(TK_THREADS) void topk_merge_kernel(
     }
 }
 
+// ---- K4': exact top-k for k > kTopkMax (any k; the full ranking of a row included)
+//
+// The same ranking rule and output format as row_topk_kernel, in three steps:
+//   select   one workgroup per row finds the exact kk-th largest key, kk = min(k, n), by 1024-bin radix histograms over
+//            the whole 64-bit key range (lo = 0, hi = ~0: keys of NaN scores are counted like any other; no pass when
+//            kk == n), then streams the row once more for the row min / max and the kk keys >= that threshold (keys are
+//            unique: exactly kk of them);
+//   sort     kk <= kLargeTile: the keys never leave LDS (select + sort + write in one kernel); larger kk: the keys go to
+//            the workspace, every kLargeTile tile is bitonic-sorted in LDS, then log2(L / kLargeTile) merge-path passes
+//            (co-rank by binary search, a fixed span of kMergeSpan outputs per thread) ping-pong between two buffers --
+//            the last pass writes the indices and scores.
+// The atomics only decide slot order, which the sort erases: the output is deterministic.
+constexpr int kMergeSpan = 8;   // outputs per thread of a merge pass
+
+template <typename F>
+__device__ __forceinline__ void wave_append(bool take, unsigned int *counter, F store) {
+    // one LDS atomic per wavefront instead of one per taken element (rows where every key is taken: kk == n)
+    const uint64_t m = __ballot(take);
+    if (!m) return;
+    const int lane = __lane_id();
+    const int leader = __ffsll((unsigned long long)m) - 1;
+    unsigned int base = 0;
+    if (lane == leader) base = atomicAdd(counter, (unsigned int)__popcll(m));
+    base = __shfl(base, leader, 64);
+    if (take) store(base + (unsigned int)__popcll(m & ((1ull << lane) - 1ull)));
+}
+
+__global__ __launch_bounds__(TK_THREADS) void large_select_kernel(
+    const float *__restrict__ scores, int64_t n, int64_t ld, int32_t k, int32_t idx_offset, int32_t norm,
+    int32_t *__restrict__ idx_out, float *__restrict__ val_out, float *__restrict__ mn_out, float *__restrict__ mx_out,
+    uint64_t *__restrict__ keys, int64_t L, float *__restrict__ row_mnmx) {
+    extern __shared__ uint64_t lbuf[];   // kLargeTile keys (keys == nullptr), or the histogram only
+    __shared__ float red_mn[TK_THREADS / 64], red_mx[TK_THREADS / 64];
+    __shared__ unsigned int s_count, s_bin;
+    unsigned int *hist = reinterpret_cast<unsigned int *>(lbuf);
+    static_assert(TK_THREADS == 1024, "one thread per histogram bin");
+
+    const int tid = threadIdx.x;
+    const int row = blockIdx.x;
+    const float *s = scores + (size_t)row * ld;
+    const int64_t kk = (int64_t)k < n ? (int64_t)k : n;
+
+    // ---- select: the exact kk-th largest key.  Invariant: count(key > hi) = above < kk <= above + count(lo <= key <= hi)
+    uint64_t thresh = 0;
+    if (kk < n) {
+        uint64_t lo = 0, hi = ~0ull;
+        unsigned int above = 0;
+        for (;;) {
+            const uint64_t width = hi - lo;
+            int shift = 0;
+            while ((width >> shift) >= 1024) ++shift;   // bins 0 .. width >> shift <= 1023
+            hist[tid] = 0;
+            if (tid == 0) s_bin = 0;
+            __syncthreads();
+            for_each_in_row(s, n, tid, [&](float v, uint32_t i) {
+                const uint64_t key = rank_key(v, i);
+                if (key >= lo && key <= hi) atomicAdd(&hist[(unsigned int)((key - lo) >> shift)], 1u);
+            });
+            __syncthreads();
+            for (int o = 1; o < TK_THREADS; o <<= 1) {   // hist[b] := keys in the bins >= b
+                const unsigned int add = tid + o < TK_THREADS ? hist[tid + o] : 0u;
+                __syncthreads();
+                hist[tid] += add;
+                __syncthreads();
+            }
+            // the counts fall with b, above + hist[0] >= kk and above < kk: exactly one bin b has
+            // above + hist[b] >= kk > above + hist[b + 1]
+            const bool here = above + hist[tid] >= (unsigned int)kk;
+            const bool next = tid + 1 < TK_THREADS && above + hist[tid + 1] >= (unsigned int)kk;
+            if (here && !next) s_bin = (unsigned int)tid;
+            __syncthreads();
+            const int b = (int)s_bin;
+            const unsigned int c_ge = above + hist[b];
+            const unsigned int c_gt = b + 1 < TK_THREADS ? above + hist[b + 1] : above;
+            __syncthreads();
+            const uint64_t blo = lo + ((uint64_t)b << shift);
+            if (c_ge == (unsigned int)kk || shift == 0) {   // (shift 0: bins are single keys, so c_ge = c_gt + 1 = kk)
+                thresh = blo;
+                break;
+            }
+            const uint64_t span = ((uint64_t)1 << shift) - 1;
+            above = c_gt;
+            hi = hi - blo > span ? blo + span : hi;
+            lo = blo;
+        }
+    }
+
+    // ---- compact the kk keys >= thresh (LDS or the workspace row) + the row min / max
+    if (tid == 0) s_count = 0;
+    __syncthreads();
+    uint64_t *grow = keys ? keys + (size_t)row * L : nullptr;
+    float mn = INFINITY, mx = -INFINITY;
+    for_each_in_row(s, n, tid, [&](float v, uint32_t i) {
+        mn = fminf(mn, v);
+        mx = fmaxf(mx, v);
+        const uint64_t key = rank_key(v, i);
+        wave_append(key >= thresh, &s_count, [&](unsigned int slot) {
+            if (slot < (unsigned int)kk) {
+                if (grow) grow[slot] = key; else lbuf[slot] = key;
+            }
+        });
+    });
+    mn = wave_min(mn);
+    mx = wave_max(mx);
+    if ((tid & 63) == 0) {
+        red_mn[tid >> 6] = mn;
+        red_mx[tid >> 6] = mx;
+    }
+    __syncthreads();
+    mn = red_mn[0];
+    mx = red_mx[0];
+    for (int w = 1; w < TK_THREADS / 64; ++w) {
+        mn = fminf(mn, red_mn[w]);
+        mx = fmaxf(mx, red_mx[w]);
+    }
+    if (tid == 0) {
+        if (mn_out) mn_out[row] = mn;
+        if (mx_out) mx_out[row] = mx;
+    }
+    if (grow) {   // sorted by large_tile_sort_kernel + large_merge_kernel; pad the row to L with the smallest key
+        for (int64_t j = kk + tid; j < L; j += TK_THREADS) grow[j] = 0;
+        if (tid == 0) {
+            row_mnmx[2 * row] = mn;
+            row_mnmx[2 * row + 1] = mx;
+        }
+        return;
+    }
+    int p2 = 2;
+    while (p2 < (int)kk) p2 <<= 1;
+    for (int j = (int)kk + tid; j < p2; j += TK_THREADS) lbuf[j] = 0;
+    __syncthreads();
+    bitonic_sort_desc(lbuf, p2, tid);
+    for (int64_t j = tid; j < k; j += TK_THREADS) {
+        int32_t idx = -1;
+        float val = 0.f;
+        if (j < kk) {
+            const uint64_t key = lbuf[j];
+            idx = (int32_t)(uint32_t)key + idx_offset;
+            val = ordered_to_f32((uint32_t)(key >> 32));
+            if (norm == kNormMinMax) val = minmax_norm(val, mn, mx);
+        }
+        idx_out[(size_t)row * k + j] = idx;
+        val_out[(size_t)row * k + j] = val;
+    }
+}
+
+// every kLargeTile run of a workspace row sorted descending in LDS; grid (L / kLargeTile, batch)
+__global__ __launch_bounds__(TK_THREADS) void large_tile_sort_kernel(uint64_t *__restrict__ keys, int64_t L) {
+    extern __shared__ uint64_t lbuf[];
+    uint64_t *t = keys + (size_t)blockIdx.y * L + (size_t)blockIdx.x * kLargeTile;
+    for (int j = threadIdx.x; j < kLargeTile; j += TK_THREADS) lbuf[j] = t[j];
+    __syncthreads();
+    bitonic_sort_desc(lbuf, kLargeTile, threadIdx.x);
+    for (int j = threadIdx.x; j < kLargeTile; j += TK_THREADS) t[j] = lbuf[j];
+}
+
+// one merge-path pass: the sorted runs [2 p w, +w) and [2 p w + w, +w) of every row (clipped to L) become one run.
+// Thread t emits the kMergeSpan outputs starting at o0 = t * kMergeSpan; its co-rank (how many come from the first run)
+// is found by binary search, ties taken from the first run (only the zero padding repeats a key).
+// last: write the indices / scores of the outputs o < k (and -1 / 0 for kk <= o < k) instead of keys.
+__global__ __launch_bounds__(TK_THREADS) void large_merge_kernel(
+    const uint64_t *__restrict__ src, uint64_t *__restrict__ dst, int64_t L, int64_t w, int32_t last, int32_t k,
+    int64_t kk, int32_t idx_offset, int32_t norm, const float *__restrict__ row_mnmx, int32_t *__restrict__ idx_out,
+    float *__restrict__ val_out) {
+    const int row = blockIdx.y;
+    const int64_t o0 = ((int64_t)blockIdx.x * TK_THREADS + threadIdx.x) * kMergeSpan;
+    uint64_t out[kMergeSpan];
+    if (o0 < L) {   // L is a multiple of kMergeSpan and of 2 w / kLargeTile: a span never straddles a run pair
+        const uint64_t *r = src + (size_t)row * L;
+        const int64_t base = o0 / (2 * w) * (2 * w);
+        const uint64_t *A = r + base, *B = r + base + w;
+        const int64_t la = L - base < w ? L - base : w;
+        const int64_t lb = L - base - w <= 0 ? 0 : (L - base - w < w ? L - base - w : w);
+        const int64_t d = o0 - base;
+        int64_t lo = d - lb > 0 ? d - lb : 0, hi = d < la ? d : la;
+        while (lo < hi) {   // smallest i with NOT (A[i] goes before B[d - i - 1])
+            const int64_t i = (lo + hi) >> 1;
+            if (A[i] >= B[d - i - 1]) lo = i + 1; else hi = i;
+        }
+        int64_t i = lo, j = d - lo;
+#pragma unroll
+        for (int u = 0; u < kMergeSpan; ++u) {
+            if (i < la && (j >= lb || A[i] >= B[j])) out[u] = A[i++];
+            else out[u] = B[j++];
+        }
+    }
+    if (!last) {
+        if (o0 < L) {
+#pragma unroll
+            for (int u = 0; u < kMergeSpan; ++u) dst[(size_t)row * L + o0 + u] = out[u];
+        }
+        return;
+    }
+    const float mn = row_mnmx[2 * row], mx = row_mnmx[2 * row + 1];
+#pragma unroll
+    for (int u = 0; u < kMergeSpan; ++u) {
+        const int64_t o = o0 + u;
+        if (o >= k) break;
+        int32_t idx = -1;
+        float val = 0.f;
+        if (o < kk) {
+            idx = (int32_t)(uint32_t)out[u] + idx_offset;
+            val = ordered_to_f32((uint32_t)(out[u] >> 32));
+            if (norm == kNormMinMax) val = minmax_norm(val, mn, mx);
+        }
+        idx_out[(size_t)row * k + o] = idx;
+        val_out[(size_t)row * k + o] = val;
+    }
+}
+
 }  // namespace
 
 hrag_status launch_row_topk(const float *scores, int32_t batch, int64_t n, int64_t ld, int32_t k,
@@ -391,6 +601,65 @@ hrag_status launch_row_topk(const float *scores, int32_t batch, int64_t n, int64
     hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)batch), dim3(TK_THREADS), 0, s, c_idx, c_val, p_mn, p_mx,
                        parts, k, n, idx_offset, (int32_t)norm, idx_out, val_out, mn_out, mx_out);
     HRAG_LAUNCH_CHECK();
+    return HRAG_OK;
+}
+
+int64_t topk_large_ws_bytes(int32_t batch, int64_t n, int32_t k) {
+    if (batch < 1 || n < 0 || k <= kTopkMax) return 0;
+    const int64_t kk = std::min<int64_t>(k, n);
+    if (kk <= kLargeTile) return 0;   // select + sort + write in one kernel, nothing leaves LDS
+    const int64_t L = round_up(kk, kLargeTile);
+    return 2 * (int64_t)batch * L * (int64_t)sizeof(uint64_t) + round_up((int64_t)batch * 2 * (int64_t)sizeof(float), 256);
+}
+
+hrag_status launch_row_topk_large(const float *scores, int32_t batch, int64_t n, int64_t ld, int32_t k,
+                                  int32_t idx_offset, TopkNorm norm, int32_t *idx_out, float *val_out, float *mn_out,
+                                  float *mx_out, hipStream_t s, void *ws, size_t ws_bytes) {
+    HRAG_REQUIRE(k > kTopkMax, "large top-k path for k > %d only (k=%d)", kTopkMax, k);
+    HRAG_REQUIRE(n >= 0 && n < (int64_t)0xffffffffll, "row length %lld not supported", (long long)n);
+    if (batch == 0) return HRAG_OK;
+    const int64_t need = topk_large_ws_bytes(batch, n, k);
+    HRAG_REQUIRE((int64_t)ws_bytes >= need && (need == 0 || ws != nullptr),
+                 "top-k workspace too small: %lld < %lld bytes (hrag_topk_rows_workspace_bytes)", (long long)ws_bytes,
+                 (long long)need);
+    HRAG_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7) == 0, "top-k workspace must be 8-byte aligned");
+    HRAG_REQUIRE(need == 0 || batch <= 65535, "large top-k: batch %d above 65535 rows per call", batch);
+    constexpr int lds_tile = kLargeTile * (int)sizeof(uint64_t);   // 128 KiB: > 64 KiB of dynamic LDS needs the opt-in
+    static bool configured = false;
+    if (!configured) {
+        HRAG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(large_select_kernel),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds_tile));
+        HRAG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(large_tile_sort_kernel),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds_tile));
+        configured = true;
+    }
+    if (need == 0) {
+        hipLaunchKernelGGL(large_select_kernel, dim3((unsigned)batch), dim3(TK_THREADS), lds_tile, s, scores, n, ld, k,
+                           idx_offset, (int32_t)norm, idx_out, val_out, mn_out, mx_out, nullptr, (int64_t)0, nullptr);
+        HRAG_LAUNCH_CHECK();
+        return HRAG_OK;
+    }
+    const int64_t kk = std::min<int64_t>(k, n);
+    const int64_t L = round_up(kk, kLargeTile);
+    uint64_t *ka = static_cast<uint64_t *>(ws);
+    uint64_t *kb = ka + (size_t)batch * L;
+    float *row_mnmx = reinterpret_cast<float *>(kb + (size_t)batch * L);
+    hipLaunchKernelGGL(large_select_kernel, dim3((unsigned)batch), dim3(TK_THREADS), 4 * TK_THREADS, s, scores, n, ld, k,
+                       idx_offset, (int32_t)norm, idx_out, val_out, mn_out, mx_out, ka, L, row_mnmx);
+    HRAG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(large_tile_sort_kernel, dim3((unsigned)(L / kLargeTile), (unsigned)batch), dim3(TK_THREADS),
+                       lds_tile, s, ka, L);
+    HRAG_LAUNCH_CHECK();
+    const int64_t per_wg = (int64_t)TK_THREADS * kMergeSpan;
+    for (int64_t w = kLargeTile; w < L; w *= 2) {
+        const bool last = 2 * w >= L;
+        const int64_t outs = last ? std::max<int64_t>(L, k) : L;
+        hipLaunchKernelGGL(large_merge_kernel, dim3((unsigned)ceil_div(outs, per_wg), (unsigned)batch), dim3(TK_THREADS),
+                           0, s, ka, kb, L, w, (int32_t)last, k, kk, idx_offset, (int32_t)norm, row_mnmx, idx_out,
+                           val_out);
+        HRAG_LAUNCH_CHECK();
+        std::swap(ka, kb);
+    }
     return HRAG_OK;
 }
 

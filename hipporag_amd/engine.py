@@ -792,9 +792,22 @@ class CapturedPipeline:
         return self._out
 
 
+_TOPK_WS = {}   # (device, stream) -> the K4' scratch of topk_rows at k > 2048, grown on demand
+
+
+def _topk_workspace(device, stream: int, nbytes: int):
+    torch = _torch()
+    key = (device, stream)
+    ws = _TOPK_WS.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _TOPK_WS[key] = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+    return ws
+
+
 def topk_rows(scores, k: int, *, n: Optional[int] = None, idx_offset: int = 0, normalize: bool = False,
               want_minmax: bool = False):
-    """Row-wise top-k of a device fp32 matrix with the library ranking rule (hrag_topk_rows)."""
+    """Row-wise top-k of a device fp32 matrix with the library ranking rule (hrag_topk_rows; any k > 2048 through
+    hrag_topk_rows_ws with a workspace cached per device and stream)."""
     torch = _torch()
     lib = _lib.load()
     if not scores.is_cuda:
@@ -806,8 +819,14 @@ def topk_rows(scores, k: int, *, n: Optional[int] = None, idx_offset: int = 0, n
     val = torch.empty((b, k), dtype=torch.float32, device=s.device)
     mn = torch.empty((b,), dtype=torch.float32, device=s.device)
     mx = torch.empty((b,), dtype=torch.float32, device=s.device)
-    check(lib.hrag_topk_rows(s.data_ptr(), b, n, ld, k, idx_offset, 1 if normalize else 0, idx.data_ptr(),
-                             val.data_ptr(), mn.data_ptr(), mx.data_ptr(), _stream()))
+    if k <= 2048:
+        check(lib.hrag_topk_rows(s.data_ptr(), b, n, ld, k, idx_offset, 1 if normalize else 0, idx.data_ptr(),
+                                 val.data_ptr(), mn.data_ptr(), mx.data_ptr(), _stream()))
+    else:
+        need = int(lib.hrag_topk_rows_workspace_bytes(b, n, k))
+        ws = _topk_workspace(s.device, _stream(), need).data_ptr() if need else None
+        check(lib.hrag_topk_rows_ws(s.data_ptr(), b, n, ld, k, idx_offset, 1 if normalize else 0, idx.data_ptr(),
+                                    val.data_ptr(), mn.data_ptr(), mx.data_ptr(), ws, need, _stream()))
     return (idx, val, mn, mx) if want_minmax else (idx, val)
 
 

@@ -5,7 +5,8 @@ issues: blocked ``torch.mm`` + ``torch.topk``), called by ``add_synonymy_edges``
 (HippoRAG.py:959-1020) with k = synonymy_edge_topk = 2047.  Here: L2-normalise + split into two fp16 halves
 in the layout [hi | lo | hi] (keys) / [hi | hi | lo] (queries) (csrc/knn.hip ``split3_kernel``), ONE pass of the
 wide-batch 256-row MFMA GEMM over 3 * dim elements into an fp32 score block (every product exact, the sum is the
-fp32 product to 2^-21: ``precision="f32"``, the default), exact row top-k (csrc/topk.hip).  Round 1 ran three
+fp32 product to 2^-21: ``precision="f32"``, the default), exact row top-k (csrc/topk.hip; any k: beyond 2048 the
+large-k selection K4').  Round 1 ran three
 accumulating passes of bf16 halves on the 128-row kernel (61 TFLOP/s effective).  No key blocking is needed -- a [query_batch x n_keys] fp32 block fits
 HBM comfortably -- so ``key_batch_size`` is accepted and ignored (the reference's per-block top-k
 followed by a merge is exact, hence equivalent).
@@ -57,8 +58,8 @@ def retrieve_knn(query_ids: List[str], key_ids: List[str], query_vecs, key_vecs,
     if dim % 8:
         raise ValueError("embedding dim must be a multiple of 8")
     kk = int(min(k, n_keys))
-    if kk > 2048:
-        raise ValueError("k > 2048 is not supported by the selection kernel")
+    if kk < 1:
+        raise ValueError("k must be >= 1")
     split = precision != "bf16"
     kdim, dtype = (3 * dim, 1) if split else (dim, 0)        # hrag_dtype: fp16 halves / bf16
 
@@ -83,6 +84,7 @@ def retrieve_knn(query_ids: List[str], key_ids: List[str], query_vecs, key_vecs,
     if min_score is not None:
         qb = max(qb, 4096)     # no [qb, n_keys] block in this mode: wider query tiles keep the key stream on the MFMAs
     scores = None
+    topk_ws = None     # kk > 2048: the scratch of the large-k selection (hrag_topk_rows_ws; none up to 16384 entries)
     fused_k = min(16, n_keys)
     if min_score is not None:
         # the thresholded call never writes a [qb, n_keys] block unless a query has 16 or more neighbours above the
@@ -93,7 +95,7 @@ def retrieve_knn(query_ids: List[str], key_ids: List[str], query_vecs, key_vecs,
     def dense(qq, rows_out):
         """[b, n_keys] score block + exact row top-k for the prepared queries qq; rows_out: their rows of the result
         (thresholded mode: cut to the prefix above min_score)"""
-        nonlocal scores
+        nonlocal scores, topk_ws
         b = qq.shape[0]
         if scores is None or scores.shape[0] < b:
             scores = torch.empty((b, ld), dtype=torch.float32, device=dev)
@@ -101,8 +103,15 @@ def retrieve_knn(query_ids: List[str], key_ids: List[str], query_vecs, key_vecs,
         check(lib.hrag_sim_gemm(keys.data_ptr(), n_keys, kdim, qq.data_ptr(), b, s.data_ptr(), ld, 0, dtype, stream))
         idx = torch.empty((b, kk), dtype=torch.int32, device=dev)
         val = torch.empty((b, kk), dtype=torch.float32, device=dev)
-        check(lib.hrag_topk_rows(s.data_ptr(), b, n_keys, ld, kk, 0, 0, idx.data_ptr(), val.data_ptr(),
-                                 None, None, stream))
+        if kk <= 2048:
+            check(lib.hrag_topk_rows(s.data_ptr(), b, n_keys, ld, kk, 0, 0, idx.data_ptr(), val.data_ptr(),
+                                     None, None, stream))
+        else:
+            need = int(lib.hrag_topk_rows_workspace_bytes(b, n_keys, kk))
+            if need and (topk_ws is None or topk_ws.numel() < need):
+                topk_ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+            check(lib.hrag_topk_rows_ws(s.data_ptr(), b, n_keys, ld, kk, 0, 0, idx.data_ptr(), val.data_ptr(), None,
+                                        None, topk_ws.data_ptr() if need else None, need, stream))
         if min_score is not None:      # rows are sorted: keep the longest prefix any of these rows needs
             keep = val >= float(min_score)
             w = int(keep.sum(1).max().item())

@@ -104,7 +104,7 @@ def build_engine_from_reference(rag, *, max_batch: int = 256, embedding_precisio
                          a["subj_vertex"] if has_facts else None, a["obj_vertex"] if has_facts else None,
                          a["num_chunks"] if has_facts else None, max_batch=max_batch, locality="auto",
                          flags=_lib.OPT_ACCEL if accel else 0,   # Chebyshev steps in the fp8 stages (undirected graph: :236)
-                         max_topk=int(min(2048, max(1, min(cfg.retrieval_top_k, len(pv))))))
+                         max_topk=int(max(1, min(cfg.retrieval_top_k, len(pv)))))
     return eng, facts
 
 

@@ -254,7 +254,7 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
     beyond = k_docs < want and hasattr(eng, "last_doc_scores")
     if k_docs < want and not beyond:
         logger.warning("num_to_retrieve=%d exceeds the engine's max_topk=%d: %d documents per query are returned "
-                       "(create the engine with a larger retrieval_top_k, <= 2048)", num_to_retrieve, eng.max_topk, k_docs)
+                       "(create the engine with a larger retrieval_top_k)", num_to_retrieve, eng.max_topk, k_docs)
     use_facts = len(facts) > 0 and k_f > 0
     two_halves = hasattr(eng, "retrieve_converged_start")
     starts = list(range(0, len(queries), eng.max_batch))
@@ -664,7 +664,7 @@ class HippoRAG:
                                   a["subj"] if has_facts else None, a["obj"] if has_facts else None,
                                   a["num_chunks"] if has_facts else None,
                                   max_batch=self.global_config.max_batch,
-                                  max_topk=min(2048, max(self.global_config.retrieval_top_k, 1)),
+                                  max_topk=max(1, min(self.global_config.retrieval_top_k, len(a["passage_vertex"]))),
                                   slab_width=self.global_config.slab_width,
                                   flags=_lib.OPT_ACCEL if self.global_config.ppr_accel else 0,
                                   locality=self.global_config.locality)

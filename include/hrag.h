@@ -51,7 +51,9 @@ extern "C" {
  *        hrag_shard_ppr_sweep enforces the ascending (step, group) order of a session with measured stage scales;
  *        later in 0.7 (no signature change): the accelerated two-stage fp16 plan (HRAG_OPT_ACCEL, batch <= 64, ppr_tol = 0)
  *        carries a margin of 16 instead of 4: 16 sweeps stand for 20 at damping 0.5 (14 before);
- *   0.8  hrag_sim_topk_min_score (the thresholded fused top-k of the index-time KNN: prefix first pass + cut). */
+ *   0.8  hrag_sim_topk_min_score (the thresholded fused top-k of the index-time KNN: prefix first pass + cut);
+ *        later in 0.8 (no struct layout changes; detect by the symbol): hrag_topk_rows_ws +
+ *        hrag_topk_rows_workspace_bytes (any k), hrag_opts.max_topk above 2048. */
 #define HRAG_VERSION_MAJOR 0
 #define HRAG_VERSION_MINOR 8
 
@@ -197,7 +199,11 @@ typedef struct hrag_fact_desc {
 
 typedef struct hrag_opts {
     int32_t max_batch;    /* largest B any call will pass (workspace is sized once)              */
-    int32_t max_topk;     /* largest k_p (retrieval_top_k); <= 2048                              */
+    int32_t max_topk;     /* largest k_p (retrieval_top_k), >= 1.  Above 2048 the final rankings */
+                          /* take K4' (hrag_topk_rows_ws) and the workspace adds its scratch,    */
+                          /* about max_batch * max_topk * 16 bytes when min(max_topk, passages)  */
+                          /* > 16384 (none at or below that, none for max_topk <= 2048);         */
+                          /* HRAG_ENOMEM if it does not fit                                      */
     int32_t slab_width;   /* PPR state slab width BC in {4,8,16,32,64}; 0 = auto                 */
     int32_t long_row_nnz; /* rows with more entries leave the G-lanes-per-row kernel and are cut  */
                           /* into wavefront-sized segments; 0 = auto (8 gather rounds)            */
@@ -395,9 +401,10 @@ hrag_status hrag_retrieve_scored(hrag_engine *e, const float *pass_scores_dev, i
                                  float *residual_out_dev, int32_t *iters_out_dev, hrag_stream stream);
 
 /* The scores of ALL passages of the engine's last hrag_retrieve / hrag_retrieve_scored (the array its top-k was taken
- * from: PPR probability, or the normalised DPR score on the fallback), fp32 [B, ld] in passage order.  For callers that
- * want more than max_topk = 2048 documents (HippoRAG.py:501-507 slices any prefix of the full ranking): sort these rows
- * with the library's ranking rule, np.argsort(x, kind="stable")[::-1].  Same stream discipline as every call. */
+ * from: PPR probability, or the normalised DPR score on the fallback), fp32 [B, ld] in passage order.  The ranking of
+ * any prefix of them (HippoRAG.py:501-507) is the call itself with k up to max_topk (any size; create the engine with
+ * max_topk = n_passages for the full ranking), or hrag_topk_rows_ws on these rows.  Same stream discipline as every
+ * call. */
 hrag_status hrag_last_doc_scores(hrag_engine *e, int32_t batch, float *out_dev, int64_t ld, hrag_stream stream);
 
 /* == dense_passage_retrieval (HippoRAG.py:1467-1502, StandardRAG.py:393-429), top-k only. */
@@ -420,7 +427,7 @@ hrag_status hrag_ppr(hrag_engine *e, const float *reset_dev, int32_t batch, floa
                      int32_t iters, float *x_out_dev, int32_t *flags_out_dev, hrag_stream stream);
 
 /* Generic row-wise top-k with the library's ranking rule (np.argsort(...)[::-1][:k]) fused with
- * the row min / max.  scores_dev fp32 [B, ld] (n valid entries per row), 1 <= k <= 2048.
+ * the row min / max.  scores_dev fp32 [B, ld] (n valid entries per row), 1 <= k <= 2048 (any k: hrag_topk_rows_ws).
  *   idx_out_dev int32 [B, k] = position + idx_offset (-1 beyond min(k, n))
  *   val_out_dev fp32 [B, k]  raw score, or (s - min) / (max - min) when normalize != 0
  *   min_out_dev / max_out_dev fp32 [B] (may be NULL).  No engine needed. */
@@ -428,6 +435,18 @@ hrag_status hrag_topk_rows(const float *scores_dev, int32_t batch, int64_t n, in
                            int32_t idx_offset, int32_t normalize, int32_t *idx_out_dev,
                            float *val_out_dev, float *min_out_dev, float *max_out_dev,
                            hrag_stream stream);
+/* The same for ANY k >= 1 (the full ranking of a row included), same output: np.argsort(x, kind="stable")[::-1][:k]
+ * exactly, so its first 2048 entries are hrag_topk_rows' at k = 2048 bit for bit.  k <= 2048 IS hrag_topk_rows (the
+ * workspace is not touched).  Beyond, K4': the exact min(k, n)-th key by radix histograms, the keys above it compacted,
+ * sorted in LDS (<= 16384 per row) or tile-sorted and merged in the workspace.  workspace_dev: 8-byte aligned,
+ * hrag_topk_rows_workspace_bytes(batch, n, k) bytes (0 -- workspace_dev may be NULL -- when k <= 2048 or
+ * min(k, n) <= 16384; else 16 * batch * round_up(min(k, n), 16384) + 256), used as scratch only: no allocation, host
+ * synchronisation or read-back inside the call (hipGraph capture safe).  batch <= 65535 when the workspace is used. */
+int64_t hrag_topk_rows_workspace_bytes(int32_t batch, int64_t n, int32_t k);
+hrag_status hrag_topk_rows_ws(const float *scores_dev, int32_t batch, int64_t n, int64_t ld, int32_t k,
+                              int32_t idx_offset, int32_t normalize, int32_t *idx_out_dev, float *val_out_dev,
+                              float *min_out_dev, float *max_out_dev, void *workspace_dev, size_t workspace_bytes,
+                              hrag_stream stream);
 
 /* ---- index-time entity KNN (retrieve_knn, utils/embed_utils.py:6-94; engine-less) ----
  * hrag_normalize_split_bf16: F.normalize (embed_utils.py:25,28) when normalize != 0, then the split
@@ -436,7 +455,8 @@ hrag_status hrag_topk_rows(const float *scores_dev, int32_t batch, int64_t n, in
  *   row stride ld; accumulate != 0 adds to out.  retrieve_knn (hipporag_amd/knn.py) runs it ONCE per query block on
  *   the split layout of hrag_split_f32 (normalize != 0: F.normalize first): [hi | lo | hi] x [qhi | qhi | qlo],
  *   fp16 halves = the fp32 product to 2^-21, on the wide-batch 256-row kernel.
- * The top-k of each score row is hrag_topk_rows (k <= 2048 covers synonymy_edge_topk = 2047). */
+ * The top-k of each score row is hrag_topk_rows (k <= 2048 covers synonymy_edge_topk = 2047), hrag_topk_rows_ws
+ * beyond (retrieve_knn accepts any k). */
 hrag_status hrag_normalize_split_bf16(const float *x_dev, int64_t rows, int32_t dim, int32_t normalize,
                                       uint16_t *hi_dev, uint16_t *lo_dev, hrag_stream stream);
 hrag_status hrag_sim_gemm(const uint16_t *emb_dev, int64_t rows, int32_t dim, const uint16_t *q_dev,
@@ -692,7 +712,8 @@ typedef struct hrag_comm {
     int32_t (*exchange_wait)(void *user, int32_t group, hrag_stream stream);
 } hrag_comm;
 
-/* bytes of caller-owned device scratch the two drivers need for `batch` queries and lists of k entries */
+/* bytes of caller-owned device scratch the two drivers need for `batch` queries and lists of k entries (k > 2048: plus
+ * the K4' scratch of the world * k -> k merge, hrag_topk_rows_workspace_bytes(batch, world * k, k)) */
 int64_t hrag_shard_workspace_bytes(hrag_engine *e, int32_t world, int32_t batch, int32_t k);
 
 /* phase A over all shards: hrag_shard_score_facts + all-gather of the candidates + MIN / MAX all-reduce + the merge:
