@@ -51,10 +51,18 @@ __device__ __forceinline__ float ordered_to_f32(uint32_t k) {
     uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
     return __uint_as_float(u);
 }
-// ranking key: score descending, then index descending  <=>  larger 64-bit key first
+// ranking key: score descending, then index descending  <=>  larger 64-bit key first.  Every NaN, whatever its sign or
+// payload, takes one value above +inf (numpy sorts NaN last, so argsort(..)[::-1] ranks them first, ties by index); that
+// value decodes (ordered_to_f32) to the canonical quiet NaN.  The smallest real key is then -inf's 0x007fffff << 32:
+// key 0 never names an element and marks an empty slot.
+constexpr uint32_t kOrderedNaN = 0xffc00000u;   // f32_to_ordered(0x7fc00000) > f32_to_ordered(+inf) = 0xff800000
 __device__ __forceinline__ uint64_t rank_key(float score, uint32_t idx) {
-    return ((uint64_t)f32_to_ordered(score) << 32) | (uint64_t)idx;
+    const uint32_t o = score != score ? kOrderedNaN : f32_to_ordered(score);
+    return ((uint64_t)o << 32) | (uint64_t)idx;
 }
+
+// max that propagates NaN (fmaxf skips it): a tile key of the fused top-k under which a tile holding a NaN ranks first
+__device__ __forceinline__ float nan_max(float a, float b) { return (b > a || b != b) ? b : a; }
 
 // Convergence contract: the running per-query maximum est[q] (float bits) is raised with atomicMax by whoever holds a
 // larger value.  The pre-check must see the other workgroups' updates -- a cached plain load keeps reading the
@@ -425,11 +433,11 @@ hrag_status launch_sim_gemm(const uint16_t *emb, int64_t rows, int32_t dim, cons
 bool sim_gemm256_serves(int64_t rows, int32_t dim, int32_t batch);
 bool sim_gemm_force_small_tiles();
 hrag_status launch_sim_gemm256(const uint16_t *emb, int64_t rows, int32_t dim, const uint16_t *q, int32_t batch,
-                               float *out, int64_t ld, float *tmax, float *tmin, hipStream_t s, int32_t dtype,
-                               int64_t row_ld = 0);
+                               float *out, int64_t ld, float *tmax, float *tmin, float *tfmax, hipStream_t s,
+                               int32_t dtype, int64_t row_ld = 0);
 
 // fused similarity + top-k for k <= 16 (no [B, rows] score matrix; bit-identical to the two-step path)
-//   ws: 2 * sim_fused_tiles(rows) * batch floats; sel: sim_fused_sel_ints(batch) ints, zeroed ONCE at allocation
+//   ws: 3 * sim_fused_tiles(rows) * batch floats (tile maxima as ranked, minima, maxima as fmaxf sees them); sel: sim_fused_sel_ints(batch) ints, zeroed ONCE at allocation
 //   (per-query records: selected tiles, arrival counter, candidate keys); mn / mx: batch floats
 int64_t sim_fused_tiles(int64_t rows);
 int64_t sim_fused_sel_ints(int32_t batch);

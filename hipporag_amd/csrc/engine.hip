@@ -643,7 +643,7 @@ static hrag_status alloc_workspace(hrag_engine *e) {
     HRAG_TRY(dev_alloc(&e->d_doc, (int64_t)B * e->ld_p));
     if (e->has_facts) HRAG_TRY(dev_alloc(&e->d_sfact, (int64_t)B * e->ld_f));
     if (e->has_facts && B > 16) {
-        HRAG_TRY(dev_alloc(&e->d_fused_ws, 2 * sim_fused_tiles(std::max<int64_t>(e->f_rows, 1)) * B));
+        HRAG_TRY(dev_alloc(&e->d_fused_ws, 3 * sim_fused_tiles(std::max<int64_t>(e->f_rows, 1)) * B));
         HRAG_TRY(dev_alloc(&e->d_fused_sel, sim_fused_sel_ints(B)));
         HRAG_HIP_TRY(hipMemset(e->d_fused_sel, 0, (size_t)sim_fused_sel_ints(B) * sizeof(int32_t)));
         HRAG_TRY(dev_alloc(&e->d_mn_f, B));

@@ -108,7 +108,7 @@ hrag_status hrag_split_f32(const float *x_dev, int64_t rows, int32_t dim, int32_
 
 int64_t hrag_sim_topk_workspace_bytes(int64_t rows, int32_t batch) {
     if (rows < 1 || batch < 1) return 0;
-    return (2 * sim_fused_tiles(rows) * (int64_t)batch + 2 * (int64_t)batch) * (int64_t)sizeof(float) +
+    return (3 * sim_fused_tiles(rows) * (int64_t)batch + 2 * (int64_t)batch) * (int64_t)sizeof(float) +
            sim_fused_sel_ints(batch) * (int64_t)sizeof(int32_t);
 }
 

@@ -49,7 +49,9 @@ constexpr int BK = 64;
 constexpr int LDS_LD = BK + 8;  // bf16 elements per LDS row (144 bytes)
 
 // TILEMAX: instead of the scores, write per (row tile, query) the max and min score of the tile
-// (tmax / tmin: [n_tiles_m][batch]) -- pass 1 of the fused fact top-k below.
+// (tmax / tmin / tfmax: [n_tiles_m][batch]) -- pass 1 of the fused fact top-k below.  tmax is the tile's ranking key:
+// NaN when the tile holds a NaN (nan_max), so that such a tile is selected first, as its NaN ranks first; tmin / tfmax are
+// fminf / fmaxf over the tile (NaN skipped), whose reductions give the row min / max that hrag_topk_rows reports.
 template <int BN, int WM, int WN, bool TILEMAX = false, bool F16 = false>
 __global__ __launch_bounds__(256) void sim_gemm_kernel(const uint16_t *__restrict__ emb,
                                                        int64_t rows, int32_t dim,
@@ -57,7 +59,8 @@ __global__ __launch_bounds__(256) void sim_gemm_kernel(const uint16_t *__restric
                                                        int32_t batch, float *__restrict__ out,
                                                        int64_t ld, int32_t n_tiles_n, int32_t accumulate,
                                                        float *__restrict__ tmax = nullptr,
-                                                       float *__restrict__ tmin = nullptr) {
+                                                       float *__restrict__ tmin = nullptr,
+                                                       float *__restrict__ tfmax = nullptr) {
     static_assert(WM * WN == 4, "4 wavefronts per workgroup");
     constexpr int MI = BM / (WM * 16);
     constexpr int NJ = BN / (WN * 16);
@@ -147,39 +150,45 @@ __global__ __launch_bounds__(256) void sim_gemm_kernel(const uint16_t *__restric
     if constexpr (TILEMAX) {
         // lane: 4 * MI rows of NJ queries; lanes l, l+16, l+32, l+48 share a query; the WM wavefronts
         // with the same wn share it too (LDS).  Rows beyond `rows` (zero-filled) are excluded.
-        __shared__ float red_mx[WM][BN], red_mn[WM][BN];
+        __shared__ float red_mx[WM][BN], red_mn[WM][BN], red_fx[WM][BN];
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
-            float mx = -INFINITY, mn = INFINITY;
+            float mx = -INFINITY, mn = INFINITY, fx = -INFINITY;
 #pragma unroll
             for (int i = 0; i < MI; ++i) {
                 const int64_t m = m0 + (wm * MI + i) * 16 + 4 * (lane >> 4);
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
                     if (m + r < rows) {
-                        mx = fmaxf(mx, acc[i][j][r]);
+                        mx = nan_max(mx, acc[i][j][r]);
                         mn = fminf(mn, acc[i][j][r]);
+                        fx = fmaxf(fx, acc[i][j][r]);
                     }
             }
-            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+            mx = nan_max(mx, __shfl_xor(mx, 16, 64));
+            mx = nan_max(mx, __shfl_xor(mx, 32, 64));
             mn = fminf(mn, __shfl_xor(mn, 16, 64));
             mn = fminf(mn, __shfl_xor(mn, 32, 64));
+            fx = fmaxf(fx, __shfl_xor(fx, 16, 64));
+            fx = fmaxf(fx, __shfl_xor(fx, 32, 64));
             if (lane < 16) {
                 red_mx[wm][(wn * NJ + j) * 16 + lane] = mx;
                 red_mn[wm][(wn * NJ + j) * 16 + lane] = mn;
+                red_fx[wm][(wn * NJ + j) * 16 + lane] = fx;
             }
         }
         __syncthreads();
         if (tid < BN && b0 + tid < batch) {
-            float mx = red_mx[0][tid], mn = red_mn[0][tid];
+            float mx = red_mx[0][tid], mn = red_mn[0][tid], fx = red_fx[0][tid];
 #pragma unroll
             for (int w = 1; w < WM; ++w) {
-                mx = fmaxf(mx, red_mx[w][tid]);
+                mx = nan_max(mx, red_mx[w][tid]);
                 mn = fminf(mn, red_mn[w][tid]);
+                fx = fmaxf(fx, red_fx[w][tid]);
             }
             tmax[(size_t)mt * batch + b0 + tid] = mx;
             tmin[(size_t)mt * batch + b0 + tid] = mn;
+            tfmax[(size_t)mt * batch + b0 + tid] = fx;
         }
         return;
     }
@@ -242,7 +251,8 @@ __device__ __forceinline__ uint64_t block_max_u64(uint64_t v, uint64_t *red, int
 constexpr int kSelRegs = 32;
 constexpr int kSelRecInts = 32 + 16 * 128 * 2;   // = kSelRec below: ints per query record of the `sel` workspace
 __global__ __launch_bounds__(256) void tile_select_kernel(const float *__restrict__ tmax,
-                                                          const float *__restrict__ tmin, int32_t n_tiles,
+                                                          const float *__restrict__ tmin,
+                                                          const float *__restrict__ tfmax, int32_t n_tiles,
                                                           int32_t batch, int32_t k, int32_t *__restrict__ sel,
                                                           float *__restrict__ mn_out, float *__restrict__ mx_out,
                                                           float cut, int32_t *__restrict__ overflow) {
@@ -250,11 +260,11 @@ __global__ __launch_bounds__(256) void tile_select_kernel(const float *__restric
     // the selected tiles stay a prefix); overflow != nullptr: overflow[b] = a (k + 1)-th tile reaches the cut as well
     // (the thresholded KNN: the caller takes the dense path for that query).  cut = -inf, overflow = nullptr: the plain top-k.
     __shared__ uint64_t red[4];
-    __shared__ float redf[4];
+    __shared__ float redf[8];
     const int b = blockIdx.x, tid = threadIdx.x;
     const bool in_regs = n_tiles <= 256 * kSelRegs;
     uint64_t keys[kSelRegs];
-    float mn = INFINITY;
+    float mn = INFINITY, mx = -INFINITY;   // the row min / max as hrag_topk_rows reports them: fminf / fmaxf, NaN skipped
 #pragma unroll
     for (int i = 0; i < kSelRegs; ++i) {
         const int t = tid + 256 * i;
@@ -262,17 +272,28 @@ __global__ __launch_bounds__(256) void tile_select_kernel(const float *__restric
         if (in_regs && t < n_tiles) {
             keys[i] = rank_key(tmax[(size_t)t * batch + b], (uint32_t)t);
             mn = fminf(mn, tmin[(size_t)t * batch + b]);
+            mx = fmaxf(mx, tfmax[(size_t)t * batch + b]);
         }
     }
     if (!in_regs)
-        for (int t = tid; t < n_tiles; t += 256) mn = fminf(mn, tmin[(size_t)t * batch + b]);
-    for (int o = 32; o > 0; o >>= 1) mn = fminf(mn, __shfl_xor(mn, o, 64));
-    if ((tid & 63) == 0) redf[tid >> 6] = mn;
+        for (int t = tid; t < n_tiles; t += 256) {
+            mn = fminf(mn, tmin[(size_t)t * batch + b]);
+            mx = fmaxf(mx, tfmax[(size_t)t * batch + b]);
+        }
+    for (int o = 32; o > 0; o >>= 1) {
+        mn = fminf(mn, __shfl_xor(mn, o, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    }
+    if ((tid & 63) == 0) {
+        redf[tid >> 6] = mn;
+        redf[4 + (tid >> 6)] = mx;
+    }
     __syncthreads();
     mn = fminf(fminf(redf[0], redf[1]), fminf(redf[2], redf[3]));
+    mx = fmaxf(fmaxf(redf[4], redf[5]), fmaxf(redf[6], redf[7]));
     uint64_t prev = ~0ull;
     for (int r = 0; r < k + (overflow ? 1 : 0); ++r) {
-        uint64_t best = 0;   // keys are > 0: ordered(x) of any non-NaN float is >= 0x00800000
+        uint64_t best = 0;   // keys are > 0: the smallest rank_key is -inf's (0x007fffff << 32)
         if (in_regs) {
 #pragma unroll
             for (int i = 0; i < kSelRegs; ++i)
@@ -292,7 +313,7 @@ __global__ __launch_bounds__(256) void tile_select_kernel(const float *__restric
         if (tid == 0) {
             sel[(size_t)b * kSelRecInts + r] = keep ? (int32_t)(uint32_t)best : -1;
             if (r == 0) {
-                mx_out[b] = best ? ordered_to_f32((uint32_t)(best >> 32)) : -INFINITY;
+                mx_out[b] = mx;
                 mn_out[b] = mn;
             }
         }
@@ -593,7 +614,7 @@ bool rescore_grouping_disabled() {
     return v;
 }
 
-// ws: 2 * tiles * batch floats (tile max / min) ; sel: sim_fused_sel_ints(batch) ints, ZEROED at allocation (per-query
+// ws: 3 * tiles * batch floats (tile max as ranked / min / max as fmaxf sees it) ; sel: sim_fused_sel_ints(batch) ints, ZEROED at allocation (per-query
 // records: selected tiles, arrival counter, candidate keys) ; mn / mx: batch floats
 hrag_status launch_sim_topk_fused(const uint16_t *emb, int64_t rows, int32_t dim, const uint16_t *q,
                                   int32_t batch, int32_t k, int32_t idx_offset, int32_t normalize,
@@ -611,7 +632,7 @@ hrag_status launch_sim_topk_fused(const uint16_t *emb, int64_t rows, int32_t dim
     if (approx_dim > 0 && !(sim_gemm256_serves(rows, approx_dim, batch) && !sim_gemm_force_small_tiles())) approx_dim = 0;
     HRAG_REQUIRE(k >= 1 && k <= kFusedMaxK && rows >= 1 && batch >= 1, "fused top-k: bad k / rows / batch");
     const int64_t tiles_m = ceil_div(rows, BM);
-    float *tmax = ws, *tmin = ws + (size_t)tiles_m * batch;
+    float *tmax = ws, *tmin = ws + (size_t)tiles_m * batch, *tfmax = tmin + (size_t)tiles_m * batch;
     const bool f16 = dtype == HRAG_FP16;
     // the same tile shapes as launch_sim_gemm (the scores do not depend on the shape: every element is
     // the same chain of 16x16x32 MFMAs in ascending k)
@@ -621,20 +642,20 @@ hrag_status launch_sim_topk_fused(const uint16_t *emb, int64_t rows, int32_t dim
         const dim3 grid((unsigned)(round_up(tiles_m, 8) * tn));                                               \
         if (f16)                                                                                              \
             hipLaunchKernelGGL((sim_gemm_kernel<BN_, WM_, WN_, true, true>), grid, dim3(256), 0, s, emb, rows, \
-                               dim, q, batch, nullptr, 0, tn, 0, tmax, tmin);                                 \
+                               dim, q, batch, nullptr, 0, tn, 0, tmax, tmin, tfmax);                          \
         else                                                                                                  \
             hipLaunchKernelGGL((sim_gemm_kernel<BN_, WM_, WN_, true, false>), grid, dim3(256), 0, s, emb, rows, \
-                               dim, q, batch, nullptr, 0, tn, 0, tmax, tmin);                                 \
+                               dim, q, batch, nullptr, 0, tn, 0, tmax, tmin, tfmax);                          \
     } while (0)
     if (approx_dim > 0)
-        HRAG_TRY(launch_sim_gemm256(emb, rows, approx_dim, q, batch, nullptr, 0, tmax, tmin, s, dtype, dim));
+        HRAG_TRY(launch_sim_gemm256(emb, rows, approx_dim, q, batch, nullptr, 0, tmax, tmin, tfmax, s, dtype, dim));
     else if (sim_gemm256_serves(rows, dim, batch) && !(sim_gemm_force_small_tiles()))
-        HRAG_TRY(launch_sim_gemm256(emb, rows, dim, q, batch, nullptr, 0, tmax, tmin, s, dtype));
+        HRAG_TRY(launch_sim_gemm256(emb, rows, dim, q, batch, nullptr, 0, tmax, tmin, tfmax, s, dtype));
     else if (batch > 64) LAUNCH_TM(128, 2, 2);
     else LAUNCH_TM(64, 4, 1);
 #undef LAUNCH_TM
     HRAG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(tile_select_kernel, dim3((unsigned)batch), dim3(256), 0, s, tmax, tmin, (int32_t)tiles_m,
+    hipLaunchKernelGGL(tile_select_kernel, dim3((unsigned)batch), dim3(256), 0, s, tmax, tmin, tfmax, (int32_t)tiles_m,
                        batch, k, sel, mn, mx, cut, overflow);
     HRAG_LAUNCH_CHECK();
     // wide batches: pass 3 grouped by tile (see pair_hist_kernel); the tile minima are dead after tile_select_kernel and
@@ -684,7 +705,7 @@ hrag_status launch_sim_gemm(const uint16_t *emb, int64_t rows, int32_t dim, cons
         return HRAG_OK;
     }
     if (!accumulate && sim_gemm256_serves(rows, dim, batch) && !sim_gemm_force_small_tiles())
-        return launch_sim_gemm256(emb, rows, dim, q, batch, out, ld, nullptr, nullptr, s, dtype);
+        return launch_sim_gemm256(emb, rows, dim, q, batch, out, ld, nullptr, nullptr, nullptr, s, dtype);
     const int64_t tiles_m = ceil_div(rows, BM);
     const bool f16 = dtype == HRAG_FP16;
 #define LAUNCH(BN_, WM_, WN_, GRID, TN)                                                                       \

@@ -80,7 +80,8 @@ __global__ __launch_bounds__(512, 1) void sim_gemm256_kernel(const uint16_t *__r
                                                              int32_t dim, const uint16_t *__restrict__ q,
                                                              int32_t batch, float *__restrict__ out, int64_t ld,
                                                              int32_t n_tiles_n, float *__restrict__ tmax,
-                                                             float *__restrict__ tmin, int64_t emb_ld, int64_t q_ld) {
+                                                             float *__restrict__ tmin, float *__restrict__ tfmax,
+                                                             int64_t emb_ld, int64_t q_ld) {
     // emb_ld / q_ld: elements between consecutive rows (>= dim).  dim < ld = a PREFIX of every row: the thresholded KNN's
     // first pass reads the hi halves of the split layout only (csrc/sim_gemm.hip launch_sim_topk_fused)
     constexpr int MI = 4, WGM = 4, WGN = 2, NW = WGM * WGN;
@@ -174,30 +175,35 @@ __global__ __launch_bounds__(512, 1) void sim_gemm256_kernel(const uint16_t *__r
 
     if constexpr (TILEMAX) {
         // waves (2 h, wn) and (2 h + 1, wn) hold the two 64-row halves of 128-row tile 2 * mt + h for their
-        // NJ * 16 queries: per-wave max / min (lanes l, l + 16, l + 32, l + 48 share a query), combined through LDS
+        // NJ * 16 queries: per-wave max / min (lanes l, l + 16, l + 32, l + 48 share a query), combined through LDS.
+        // tmax is the NaN-propagating tile key, tmin / tfmax are fminf / fmaxf (csrc/sim_gemm.hip, TILEMAX)
         __syncthreads();                                   // the stages are dead: reuse them
-        float *red = reinterpret_cast<float *>(smem);      // [2 (max, min)][WGM][BN]
+        float *red = reinterpret_cast<float *>(smem);      // [3 (max, min, fmax)][WGM][BN]
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
-            float mx = -INFINITY, mn = INFINITY;
+            float mx = -INFINITY, mn = INFINITY, fx = -INFINITY;
 #pragma unroll
             for (int i = 0; i < MI; ++i) {
                 const int64_t m = m0 + wm * (MI * 16) + i * 16 + 4 * (lane >> 4);
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
                     if (m + r < rows) {
-                        mx = fmaxf(mx, acc[i][j][r]);
+                        mx = nan_max(mx, acc[i][j][r]);
                         mn = fminf(mn, acc[i][j][r]);
+                        fx = fmaxf(fx, acc[i][j][r]);
                     }
             }
-            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+            mx = nan_max(mx, __shfl_xor(mx, 16, 64));
+            mx = nan_max(mx, __shfl_xor(mx, 32, 64));
             mn = fminf(mn, __shfl_xor(mn, 16, 64));
             mn = fminf(mn, __shfl_xor(mn, 32, 64));
+            fx = fmaxf(fx, __shfl_xor(fx, 16, 64));
+            fx = fmaxf(fx, __shfl_xor(fx, 32, 64));
             if (lane < 16) {
                 const int col = wn * (NJ * 16) + j * 16 + lane;
                 red[wm * BN + col] = mx;
                 red[(WGM + wm) * BN + col] = mn;
+                red[(2 * WGM + wm) * BN + col] = fx;
             }
         }
         __syncthreads();
@@ -206,8 +212,10 @@ __global__ __launch_bounds__(512, 1) void sim_gemm256_kernel(const uint16_t *__r
             const int64_t t128 = mt * 2 + h;
             const int gb = b0 + col;
             if (t128 * 128 < rows && gb < batch) {
-                tmax[(size_t)t128 * batch + gb] = fmaxf(red[(2 * h) * BN + col], red[(2 * h + 1) * BN + col]);
+                tmax[(size_t)t128 * batch + gb] = nan_max(red[(2 * h) * BN + col], red[(2 * h + 1) * BN + col]);
                 tmin[(size_t)t128 * batch + gb] = fminf(red[(WGM + 2 * h) * BN + col], red[(WGM + 2 * h + 1) * BN + col]);
+                tfmax[(size_t)t128 * batch + gb] =
+                    fmaxf(red[(2 * WGM + 2 * h) * BN + col], red[(2 * WGM + 2 * h + 1) * BN + col]);
             }
         }
         return;
@@ -234,10 +242,10 @@ __global__ __launch_bounds__(512, 1) void sim_gemm256_kernel(const uint16_t *__r
 
 template <int NJ, bool TILEMAX, bool F16>
 hrag_status launch256(const uint16_t *emb, int64_t rows, int32_t dim, const uint16_t *q, int32_t batch, float *out,
-                      int64_t ld, float *tmax, float *tmin, hipStream_t s, int64_t row_ld) {
+                      int64_t ld, float *tmax, float *tmin, float *tfmax, hipStream_t s, int64_t row_ld) {
     constexpr int BN = NJ * 32;
     constexpr int lds_bytes = 3 * BM2 * 128 + 2 * BN * 128;   // three embedding stages, two query stages
-    static_assert(lds_bytes >= 2 * 4 * BN * (int)sizeof(float), "the tile-max reduction reuses the stage memory");
+    static_assert(lds_bytes >= 3 * 4 * BN * (int)sizeof(float), "the tile-max reduction reuses the stage memory");
     static bool configured = false;
     auto kernel = sim_gemm256_kernel<NJ, TILEMAX, F16>;
     if (!configured) {   // > 64 KB of dynamic LDS needs the opt-in once per kernel
@@ -248,7 +256,7 @@ hrag_status launch256(const uint16_t *emb, int64_t rows, int32_t dim, const uint
     const int64_t tiles_m = ceil_div(rows, BM2);
     const int tn = (int)ceil_div(batch, BN);
     hipLaunchKernelGGL(kernel, dim3((unsigned)(round_up(tiles_m, 8) * tn)), dim3(512), lds_bytes, s, emb, rows, dim, q,
-                       batch, out, ld, tn, tmax, tmin, row_ld, row_ld);
+                       batch, out, ld, tn, tmax, tmin, tfmax, row_ld, row_ld);
     HRAG_LAUNCH_CHECK();
     return HRAG_OK;
 }
@@ -259,14 +267,15 @@ bool sim_gemm256_serves(int64_t rows, int32_t dim, int32_t batch) {
     return batch > 64 && dim % BK2 == 0 && dim >= BK2 && rows >= BM2;
 }
 
-// tmax / tmin != nullptr: pass 1 of the fused fact top-k (per 128-row tile max / min, [ceil(rows / 128)][batch])
+// tmax / tmin / tfmax != nullptr: pass 1 of the fused fact top-k (per 128-row tile max as ranked / min / max as fmaxf sees
+// it, [ceil(rows / 128)][batch])
 hrag_status launch_sim_gemm256(const uint16_t *emb, int64_t rows, int32_t dim, const uint16_t *q, int32_t batch,
-                               float *out, int64_t ld, float *tmax, float *tmin, hipStream_t s, int32_t dtype,
-                               int64_t row_ld) {
+                               float *out, int64_t ld, float *tmax, float *tmin, float *tfmax, hipStream_t s,
+                               int32_t dtype, int64_t row_ld) {
     if (row_ld <= 0) row_ld = dim;      // rows of both operands are row_ld elements apart; the product runs over the first dim
     const bool f16 = dtype == HRAG_FP16, tm = tmax != nullptr;
     const bool wide = batch > 128;
-#define GO(NJ_, TM_, F_) return launch256<NJ_, TM_, F_>(emb, rows, dim, q, batch, out, ld, tmax, tmin, s, row_ld)
+#define GO(NJ_, TM_, F_) return launch256<NJ_, TM_, F_>(emb, rows, dim, q, batch, out, ld, tmax, tmin, tfmax, s, row_ld)
     if (wide) {
         if (tm) { if (f16) GO(8, true, true); else GO(8, true, false); }
         else { if (f16) GO(8, false, true); else GO(8, false, false); }

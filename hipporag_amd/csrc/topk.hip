@@ -89,6 +89,14 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// the row min / max: fminf / fmaxf, which skip NaN -- a signalling NaN is quieted first, because v_min_f32 / v_max_f32
+// return NaN for one (IEEE mode) and the running extreme would restart after it
+__device__ __forceinline__ void minmax_add(float &mn, float &mx, float v) {
+    v = __builtin_canonicalizef(v);
+    mn = fminf(mn, v);
+    mx = fmaxf(mx, v);
+}
+
 __device__ __forceinline__ float minmax_norm(float s, float mn, float mx) {
     const float range = mx - mn;
     return range == 0.f ? 1.f : __fdiv_rn(s - mn, range);  // misc_utils.py:130-139
@@ -118,8 +126,7 @@ __global__ __launch_bounds__(TK_THREADS) void row_topk_kernel(
     uint64_t t0 = 0, t1 = 0;
     float mn = INFINITY, mx = -INFINITY;
     for_each_in_row(s, n, tid, [&](float v, uint32_t i) {
-        mn = fminf(mn, v);
-        mx = fmaxf(mx, v);
+        minmax_add(mn, mx, v);
         const uint64_t key = rank_key(v, i);
         if (key > t1) {
             if (key > t0) {
@@ -208,16 +215,19 @@ __global__ __launch_bounds__(TK_THREADS) void row_topk_kernel(
         // 1000-query KNN block.  Radix refinement instead: a 1024-bin histogram of the keys inside [lo, hi] (LDS atomics; the
         // candidate buffer lends its memory), the bin that holds the kk-th largest is the next [lo, hi]; stop as soon as
         // count(key >= lo) fits the buffer -- 10 bits per pass and no need for the exact key: 2 - 3 passes.
-        // Invariant: count(key > hi) = above < kk <= above + count(lo <= key <= hi).
+        // Invariant: count(key > hi) = above < kk <= above + count(lo <= key <= hi).  It holds at the start because hi = ~0
+        // lies above every key and thresh has >= kk keys at or above it.  (hi must not be derived from the row max: mx comes
+        // from fmaxf, which skips NaN, and the keys of NaN scores lie above rank_key(mx, ~0) -- they would never be counted.)
         unsigned int *hist = reinterpret_cast<unsigned int *>(buf);
         static_assert(TK_THREADS == 1024, "one thread per histogram bin");
-        uint64_t lo = thresh, hi = rank_key(mx, 0xffffffffu);
+        uint64_t lo = thresh, hi = ~0ull;
         unsigned int above = 0;
         for (;;) {
             const uint64_t width = hi - lo;
             int shift = 0;
             while ((width >> shift) >= 1024) ++shift;              // bins 0 .. width >> shift <= 1023
             hist[tid] = 0;
+            if (tid == 0) s_count = 0;                             // the bin search below never reads a stale count
             __syncthreads();
             for_each_in_row(s, n, tid, [&](float v, uint32_t i) {
                 const uint64_t key = rank_key(v, i);
@@ -230,7 +240,8 @@ __global__ __launch_bounds__(TK_THREADS) void row_topk_kernel(
                 hist[tid] += add;
                 __syncthreads();
             }
-            // the counts fall with b: exactly one bin b has above + hist[b] >= kk > above + hist[b + 1]
+            // the counts fall with b, above + hist[0] >= kk and above < kk: exactly one bin b has
+            // above + hist[b] >= kk > above + hist[b + 1] (bin 0 always qualifies for `here`)
             const bool here = above + hist[tid] >= (unsigned int)kk;
             const bool next = tid + 1 < TK_THREADS && above + hist[tid + 1] >= (unsigned int)kk;
             if (here && !next) s_count = (unsigned int)tid;
@@ -285,8 +296,7 @@ __global__ __launch_bounds__(TK_THREADS) void row_minmax_kernel(const float *__r
     const float *s = scores + (size_t)row * ld;
     float mn = INFINITY, mx = -INFINITY;
     for_each_in_row(s, n, tid, [&](float v, uint32_t) {
-        mn = fminf(mn, v);
-        mx = fmaxf(mx, v);
+        minmax_add(mn, mx, v);
         sum += (double)v;
     });
     mn = wave_min(mn);
@@ -449,8 +459,7 @@ __global__ __launch_bounds__(TK_THREADS) void large_select_kernel(
     uint64_t *grow = keys ? keys + (size_t)row * L : nullptr;
     float mn = INFINITY, mx = -INFINITY;
     for_each_in_row(s, n, tid, [&](float v, uint32_t i) {
-        mn = fminf(mn, v);
-        mx = fmaxf(mx, v);
+        minmax_add(mn, mx, v);
         const uint64_t key = rank_key(v, i);
         wave_append(key >= thresh, &s_count, [&](unsigned int slot) {
             if (slot < (unsigned int)kk) {

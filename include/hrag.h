@@ -29,7 +29,11 @@
  *   - all index outputs are int32, all score outputs fp32;
  *   - ranking rule everywhere: score descending, ties -> larger index first
  *     (== numpy.argsort(x, kind="stable")[::-1]; the reference's np.argsort default
- *     leaves ties undefined, HippoRAG.py:1500,1688,1746).
+ *     leaves ties undefined, HippoRAG.py:1500,1688,1746).  NaN: every NaN, whatever its
+ *     sign or payload, ranks above +inf, NaNs tie by index (numpy sorts NaN last); the
+ *     score returned for it is the canonical quiet NaN (0x7fc00000);
+ *   - row min / max (the min-max normalisation, the mn / mx outputs) are fminf / fmaxf:
+ *     NaN is skipped; a row with no number (empty, or NaN only) gives +inf / -inf.
  */
 #ifndef HRAG_H_
 #define HRAG_H_

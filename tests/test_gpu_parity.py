@@ -180,15 +180,20 @@ def test_score_facts_fused_is_bit_identical_to_gemm_plus_topk(gpu_device, rows, 
     without the [B, F] score matrix: ids and normalised scores must equal the two-step path
     (hrag_sim_scores + hrag_topk_rows) bit for bit, including duplicated rows (ties -> larger index),
     a last partial tile and fewer rows than k."""
-    import torch
-    from hipporag_amd.engine import HippoRAGEngine, topk_rows
-    from hipporag_amd.graph import build_csr
     from hipporag_amd import synth
     emb = synth.make_embeddings_np(rows, dim, seed=rows + 3)
     if rows > 300:
         emb[200:260] = emb[100:160]                      # exact ties across two tiles
         emb[-1] = emb[5]
     q, _ = synth.make_queries_np(emb, b, seed=9)
+    _fused_vs_two_step(gpu_device, emb, q, k)
+
+
+def _fused_vs_two_step(gpu_device, emb, q, k):
+    import torch
+    from hipporag_amd.engine import HippoRAGEngine, topk_rows
+    from hipporag_amd.graph import build_csr
+    rows, b = emb.shape[0], q.shape[0]
     g = build_csr(4, [0, 1], [1, 2], [1.0, 1.0])
     zeros = np.zeros(rows, np.int32)
     with HippoRAGEngine(g, np.array([3], np.int32), emb[:1], emb, zeros, zeros, np.zeros(4, np.int32),
@@ -198,9 +203,29 @@ def test_score_facts_fused_is_bit_identical_to_gemm_plus_topk(gpu_device, rows, 
         idx2, sc2 = topk_rows(raw, k, normalize=True)
         torch.cuda.synchronize()
     assert torch.equal(idx, idx2)
-    assert torch.equal(sc, sc2)
+    assert torch.equal(sc.view(torch.int32), sc2.view(torch.int32))     # bit for bit, NaN scores included
     if rows < k:
         assert (idx[:, rows:] == -1).all()
+    return idx.cpu().numpy()
+
+
+@pytest.mark.parametrize("rows,dim,b,k", [(6000, 192, 70, 5), (1000, 768, 130, 16), (40000, 256, 256, 5), (129, 72, 65, 5),
+                                          (1000, 768, 17, 16)])
+def test_score_facts_fused_is_bit_identical_to_gemm_plus_topk_with_nan_rows(gpu_device, rows, dim, b, k):
+    """The same identity when some fact embeddings hold a NaN (bf16 NaNs of both signs): every query scores those rows
+    NaN, which ranks first (larger index first), and the row max / min that normalise the rest skip it, on both paths
+    (tests/test_gpu_topk_exact.py puts a NaN in a tile whose other rows score low)."""
+    from hipporag_amd import synth
+    emb = synth.make_embeddings_np(rows, dim, seed=rows + 4)
+    q, _ = synth.make_queries_np(emb, b, seed=10)
+    nan_rows = np.array(sorted({3, rows // 2, rows - 1}))
+    emb[nan_rows, 1] = np.array([0x7FC0, 0xFFC1, 0x7F81], np.uint16)[:len(nan_rows)]
+    if rows > 300:
+        emb[300, 2] = np.uint16(0xFFC0)
+        nan_rows = np.append(nan_rows, 300)
+    idx = _fused_vs_two_step(gpu_device, emb, q, k)
+    want = np.sort(nan_rows)[::-1][:k]
+    assert (idx[:, :len(want)] == want).all()            # the NaN rows first, larger index first
 
 
 @pytest.mark.parametrize("b", [2, 12, 40, 70])

@@ -5,12 +5,18 @@ and its prefix is hrag_topk_rows' bit for bit."""
 import numpy as np
 import pytest
 
+from tests.helpers import expected_topk
+
 pytestmark = pytest.mark.gpu
+
+
+_NANS = np.array([0x7FC00000, 0xFFC00000, 0x7F800001, 0xFF800001, 0x7FFFFFFF, 0xFFFFFFFF, 0x7FC12345, 0xFF812345],
+                 np.uint32).view(np.float32)
 
 
 def _rows(batch, n, seed):
     """Row r of the batch takes distribution r % 7: random, all equal, few distinct values, ascending, descending,
-    random with +-inf, random with positive quiet NaNs."""
+    random with +-inf, random with NaNs of both signs and mixed payloads (quiet and signalling)."""
     rng = np.random.default_rng(seed)
     x = np.empty((batch, n), np.float32)
     for r in range(batch):
@@ -31,26 +37,13 @@ def _rows(batch, n, seed):
             x[r, rng.integers(0, n, max(1, n // 100))] = -np.inf
         else:
             x[r] = rng.standard_normal(n).astype(np.float32)
-            x[r, rng.integers(0, n, max(1, n // 50))] = np.float32(np.nan)   # positive quiet NaN
+            at = rng.integers(0, n, max(1, n // 50))
+            x[r, at] = _NANS[np.arange(len(at)) % len(_NANS)]
     return x
 
 
 def _expected(x, k, idx_offset):
-    """np.argsort(..., kind="stable")[::-1][:k] per row, -1 / 0 beyond n; normalised scores in float32 numpy."""
-    b, n = x.shape
-    kk = min(k, n)
-    order = np.argsort(x, axis=1, kind="stable")[:, ::-1][:, :kk]
-    raw = np.take_along_axis(x, order, axis=1)
-    mn = np.fmin.reduce(x, axis=1) if n else np.full(b, np.inf, np.float32)
-    mx = np.fmax.reduce(x, axis=1) if n else np.full(b, -np.inf, np.float32)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        rng_ = (mx - mn)[:, None]
-        norm = np.where(rng_ == 0, np.float32(1), (raw - mn[:, None]) / rng_).astype(np.float32)
-    idx = np.full((b, k), -1, np.int32)
-    idx[:, :kk] = order + idx_offset
-    val_raw, val_norm = np.zeros((b, k), np.float32), np.zeros((b, k), np.float32)
-    val_raw[:, :kk], val_norm[:, :kk] = raw, norm
-    return idx, val_raw, val_norm, mn.astype(np.float32), mx.astype(np.float32)
+    return expected_topk(x, k, idx_offset)
 
 
 def _on_device(x, ld, misalign):
@@ -127,11 +120,7 @@ def test_wide_batch(gpu_device):
 def test_prefix_and_small_k_are_hrag_topk_rows_bit_for_bit(gpu_device):
     x = _rows(14, 125000, seed=6)
     b, n = x.shape
-    # leaves out the rows with positive NaNs: hrag_topk_rows' overflow refinement starts at rank_key(max, ~0), above which
-    # NaN keys are not counted, so on such a row (k near 2048 of 125 000) its result is not the argsort and not even
-    # repeatable (a known defect of the k <= 2048 kernel, which this change leaves as it is); hrag_topk_rows_ws counts
-    # every key and is checked against numpy on those rows above
-    rows = np.array([r for r in range(b) if r % 7 != 6])
+    rows = np.arange(b)     # the NaN rows included: hrag_topk_rows' overflow refinement counts NaN keys too
     buf, ptr = _on_device(x, n, 0)
     for normalize in (0, 1):
         base = _call(ptr, b, n, n, 2048, 0, normalize, large=False)
