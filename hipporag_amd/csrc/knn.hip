@@ -43,10 +43,12 @@ __global__ __launch_bounds__(256) void normalize_split_kernel(const float *__res
     }
 }
 
-// fp32-faithful similarity (HRAG_F32_SPLIT): a vector x = hi + lo, both IEEE fp16 (11 + 11 significant bits: x to
-// 2^-22 |x|; components are <= 1 in magnitude, unit vectors), is laid out over 3 * dim fp16 elements so that ONE fp16
-// MFMA dot product of a stored row with a query is  hi.qhi + lo.qhi + hi.qlo  -- every partial product is exact in
-// the fp32 accumulator, the dropped lo.qlo term is <= 2^-22 |x||q| -- through every similarity kernel unchanged:
+// fp32-faithful similarity (HRAG_F32_SPLIT): a vector x = hi + lo, both IEEE fp16 (11 + 11 significant bits: each
+// component to max(2^-22 |v|, 2^-25) -- the absolute 2^-25 where lo, or hi, is an fp16 subnormal: |v| < 2^-3; |v| must
+// stay below 65504), is laid out over 3 * dim fp16 elements so that ONE fp16 MFMA dot product of a stored row with a
+// query is  hi.qhi + lo.qhi + hi.qlo  -- every partial product is exact in the fp32 accumulator, the dropped lo.qlo term
+// is <= 2^-22 |x||q| (+ the floor); the sum is rounded in fp32 once per MFMA step (include/hrag.h HRAG_F32_SPLIT states
+// the whole bound) -- through every similarity kernel unchanged:
 //   embedding row: [hi | lo | hi]        query: [qhi | qhi | qlo]
 // (bf16 halves, 8 + 8 bits, were tried first: 1.5e-6 off the reference's fp32 scores, enough to move the prior of
 // the lowest-ranked passages by 1e-3 relative.)  One wavefront per row.

@@ -4,8 +4,9 @@ Mirrors reference src/hipporag/utils/embed_utils.py:6-94 (the only GPU compute t
 issues: blocked ``torch.mm`` + ``torch.topk``), called by ``add_synonymy_edges``
 (HippoRAG.py:959-1020) with k = synonymy_edge_topk = 2047.  Here: L2-normalise + split into two fp16 halves
 in the layout [hi | lo | hi] (keys) / [hi | hi | lo] (queries) (csrc/knn.hip ``split3_kernel``), ONE pass of the
-wide-batch 256-row MFMA GEMM over 3 * dim elements into an fp32 score block (every product exact, the sum is the
-fp32 product to 2^-21: ``precision="f32"``, the default), exact row top-k (csrc/topk.hip; any k: beyond 2048 the
+wide-batch 256-row MFMA GEMM over 3 * dim elements into an fp32 score block (every product exact; the score is the
+product of the normalised fp32 vectors up to ~3 * 2^-22 from the layout plus the fp32 accumulation of the chain, bound in
+include/hrag.h HRAG_F32_SPLIT: ``precision="f32"``, the default), exact row top-k (csrc/topk.hip; any k: beyond 2048 the
 large-k selection K4').  Round 1 ran three
 accumulating passes of bf16 halves on the 128-row kernel (61 TFLOP/s effective).  No key blocking is needed -- a [query_batch x n_keys] fp32 block fits
 HBM comfortably -- so ``key_batch_size`` is accepted and ignored (the reference's per-block top-k
@@ -23,8 +24,9 @@ import numpy as np
 from . import _lib
 from ._lib import check
 
-# bound on |x . q - hi(x) . hi(q)| for unit vectors in the split layout: |lo| <= 2^-11 |x| per vector, two cross terms
-# (9.8e-4) + the dropped lo . lo term and the fp32 accumulation (< 1e-5): what the thresholded first pass may miss by
+# bound on |x . q - hi(x) . hi(q)| for unit vectors in the split layout: |lo| <= 2^-11 |x| + 2^-25 per component, two
+# cross terms (9.8e-4 + 2^-25 (|x|_1 + |q|_1) <= 3.8e-6 at dim 4096) + the dropped lo . lo term and the fp32 accumulation
+# of both passes (< 1e-5 in practice): what the thresholded first pass may miss by
 _PREFIX_MARGIN = 1.2e-3
 
 
@@ -40,8 +42,9 @@ def retrieve_knn(query_ids: List[str], key_ids: List[str], query_vecs, key_vecs,
     below synonymy_edge_sim_threshold, HippoRAG.py:1004-1007): the device result is cut to the longest row prefix that
     reaches it before it crosses PCIe (entries below it come back as idx -1 / score 0) -- at k = 2047 the full arrays
     are 16 KB per query and dominate the call.
-    precision: "f32" (fp16 hi + lo halves, one pass over 3 * dim: |error| ~1e-7, default; "bf16x3" is accepted as an
-    alias) or "bf16" (rounded vectors, one pass over dim, ~2e-3).
+    precision: "f32" (fp16 hi + lo halves, one pass over 3 * dim: |error| ~1e-7 typical, up to ~1e-6 on near-duplicates
+    at dim 4096 (the fp32 accumulation of 3 * dim / 32 MFMA steps), default; "bf16x3" is accepted as an alias) or "bf16"
+    (rounded vectors, one pass over dim, ~2e-3).
     """
     import torch
     if len(key_vecs) == 0:

@@ -150,8 +150,9 @@ class RetrievalConfig:
     is_directed_graph: bool = False      # :176
     # engine-only knobs (no reference analogue)
     embedding_precision: str = "f32"     # "f32": scores like the reference's fp32 np.dot (HippoRAG.py:1459,1496) -- the
-                                         # stores' fp32 vectors as hi + lo bf16, three MFMA products per element
-                                         # (HRAG_F32_SPLIT, 3x the embedding stream); "bf16": vectors rounded to bf16 (1x
+                                         # stores' fp32 vectors as hi + lo fp16, three MFMA products per element
+                                         # (HRAG_F32_SPLIT, 3x the embedding stream; unit-length vectors: include/hrag.h
+                                         # states the bound); "bf16": vectors rounded to bf16 (1x
                                          # stream; near-tied facts / passages may swap against the reference)
     ppr_iters: Optional[int] = None      # None: derived from damping (sweeps_for_damping: 20 at 0.5)
     locality: Optional[str] = "auto"     # the engine renumbers the vertices by the first passage that links them (the

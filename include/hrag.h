@@ -105,9 +105,20 @@ typedef enum hrag_dtype {
                        /* HippoRAG.py:1342-1345,1459,1496; embedding_store.py:216-221).  `data` is fp32 [rows, dim]; the  */
                        /* engine stores every vector as hi + lo (two fp16: 22 significant bits) in the layout            */
                        /* [hi | lo | hi] and a query as [qhi | qhi | qlo], so that one fp16 MFMA dot product of          */
-                       /* 3 * dim elements IS hi.qhi + lo.qhi + hi.qlo = the fp32 product up to 2^-21 |x||q| -- through  */
-                       /* kernel unchanged, at 3x the embedding stream.  Every q_*_dev pointer of such an engine is      */
-                       /* fp32 [B, dim].  Ranking with bf16-rounded embeddings instead flips near-tied facts / passages  */
+                       /* 3 * dim elements IS hi.qhi + lo.qhi + hi.qlo -- through every kernel unchanged, at 3x the      */
+                       /* embedding stream.  Every q_*_dev pointer of such an engine is fp32 [B, dim].                    */
+                       /* Accuracy against the exact product of the fp32 vectors (tests/helpers.py split_score_bound):    */
+                       /*   layout: sum_i e(x_i)|q_i| + |x_i|e(q_i) + e(x_i)e(q_i) + l(x_i)l(q_i), e(v) = max(2^-22 |v|,  */
+                       /*     2^-25) bounds |v - hi - lo|, l(v) = 2^-11 |v| + 2^-25 bounds |lo| (the dropped lo.qlo);    */
+                       /*     the 2^-25 is ABSOLUTE: lo is an fp16 subnormal below |v| = 2^-3, hi below 2^-14.  So the    */
+                       /*     layout costs ~3 * 2^-22 |x||q| only while |x||q| dominates 2^-25 (|x|_1 + |q|_1): unit     */
+                       /*     vectors (what embedding models return) keep it, vectors of norm 1e-3 at dim 4096 lose it   */
+                       /*     (~2e-5 |x||q| RMS: scale such inputs to unit length first);                                */
+                       /*   accumulation: fp32, one rounding per 32-element MFMA step: gamma_n sum|products| with        */
+                       /*     n = 3 * dim / 32 + 5 in the worst case (4.6e-5 at dim 4096); rounding to nearest makes it   */
+                       /*     a random walk in practice: ~2^-24 sqrt(2 * 3 * dim / 32) |score| over the last two thirds. */
+                       /*   Precondition: every |component| < 65504 (fp16 overflow: an infinite half, NaN scores).       */
+                       /* Ranking with bf16-rounded embeddings instead flips near-tied facts / passages                   */
                        /* (tests/test_ref_golden.py counts them on the reference-run fixture ref_synth_f32.npz)             */
     HRAG_F32_SPLIT_ROWS = 3 /* the same engine from rows that are ALREADY in the split layout: `data` is fp16             */
                        /* [rows, 3 * dim] as hrag_split_f32 / hrag_engine_gather_embeddings produce it (`dim` stays the  */
@@ -458,7 +469,8 @@ hrag_status hrag_topk_rows_ws(const float *scores_dev, int32_t batch, int64_t n,
  * hrag_sim_gemm: out[b][m] (+)= sum_k q[b][k] * emb[m][k]  (torch.mm, :53); bf16 / fp16 in (dtype), fp32 out,
  *   row stride ld; accumulate != 0 adds to out.  retrieve_knn (hipporag_amd/knn.py) runs it ONCE per query block on
  *   the split layout of hrag_split_f32 (normalize != 0: F.normalize first): [hi | lo | hi] x [qhi | qhi | qlo],
- *   fp16 halves = the fp32 product to 2^-21, on the wide-batch 256-row kernel.
+ *   fp16 halves, on the wide-batch 256-row kernel: the accuracy of HRAG_F32_SPLIT above (unit vectors after
+ *   normalisation: layout ~3 * 2^-22 + the fp32 accumulation).
  * The top-k of each score row is hrag_topk_rows (k <= 2048 covers synonymy_edge_topk = 2047), hrag_topk_rows_ws
  * beyond (retrieve_knn accepts any k). */
 hrag_status hrag_normalize_split_bf16(const float *x_dev, int64_t rows, int32_t dim, int32_t normalize,
@@ -484,7 +496,7 @@ hrag_status hrag_sim_topk(const uint16_t *emb_dev, int64_t rows, int32_t dim, co
  *   - approx_dim > 0: pass 1 (the tile maxima) runs over the first approx_dim elements of every row and query only; the
  *     caller states in `margin` a bound on |full product - prefix product|.  For the split layout of hrag_split_f32 with
  *     approx_dim = dim / 3 the prefix is hi . qhi and the rest, lo . qhi + hi . qlo, is at most 2 * 2^-11 |x| |q| = 9.8e-4
- *     for unit vectors: margin 1.2e-3, a third of the MFMA work.  approx_dim = 0: pass 1 over all of dim (margin may be 0);
+ *     for unit vectors (+ the fp16 subnormal floor 2^-25 (|x|_1 + |q|_1), 3.8e-6 at dim 4096): margin 1.2e-3, a third of the MFMA work.  approx_dim = 0: pass 1 over all of dim (margin may be 0);
  *   - pass 3 rescores the tiles that reach the cut over all `dim` elements: every returned score is the exact chain of
  *     hrag_sim_gemm, and every row with score >= min_score is returned (in score order, ahead of anything below
  *     min_score) UNLESS overflow_out_dev[b] != 0 (more than k tiles reached the cut) or the k-th returned score is itself

@@ -177,3 +177,63 @@ def test_thresholded_knn_prefix_first_pass_straddling_the_threshold(gpu_device):
         np.testing.assert_array_equal(thr_i[r, :n], full_i[r, :n])
         np.testing.assert_array_equal(thr_s[r, :n], full_s[r, :n])
         assert np.all(thr_i[r, n:] == -1) and np.all(thr_s[r, n:] == 0)
+
+
+@pytest.mark.parametrize("dim,n_keys,n_base", [(768, 200_000, 300), (4096, 40_000, 100)])
+def test_thresholded_knn_at_production_width_against_fp64(gpu_device, dim, n_keys, n_base):
+    """retrieve_knn(min_score=0.8) at the reference's widths (768; NV-Embed-v2's 4096) on 4096-query blocks -- the prefix
+    first pass over the hi . qhi third, the overflow flag and the grouped pass 3 all run -- against an fp64 KNN of the
+    fp32 inputs: neighbours planted at cosines within 5e-3 of the threshold on both sides, inside and outside the 1.2e-3
+    margin, scattered over many tiles.  Every key at or above 0.8 + bound in fp64 is returned, every returned score is
+    within the bound of its fp64 value (tests/helpers.py split_score_bound on the normalised vectors, plus 2^-21 for the
+    kernel's fp32 normalisation of both sides)."""
+    import torch
+    from hipporag_amd.knn import retrieve_knn
+    from tests.helpers import split_score_bound
+    rng = np.random.default_rng(dim)
+
+    def unit(x):
+        return x / np.linalg.norm(x, axis=-1, keepdims=True)
+
+    base = unit(rng.standard_normal((n_base, dim)))
+    rows = [base]
+    for i in range(n_base):
+        n_dup = (3, 10, 24, 40)[i % 4]
+        u = unit(rng.standard_normal((n_dup, dim)))
+        u = unit(u - (u @ base[i])[:, None] * base[i])
+        c = rng.uniform(0.795, 0.805, n_dup)[:, None]
+        rows.append(c * base[i] + np.sqrt(1 - c * c) * u)
+    planted = sum(len(r) for r in rows)
+    keys = np.concatenate(rows + [rng.standard_normal((n_keys - planted, dim))]).astype(np.float32)
+    keys *= rng.uniform(0.5, 2.0, (n_keys, 1)).astype(np.float32)          # not unit length: retrieve_knn normalises
+    perm = rng.permutation(n_keys)
+    keys = keys[perm]
+    q = np.concatenate([keys[np.argsort(perm)[:n_base]], keys[rng.integers(0, n_keys, 4200 - n_base)]])
+    idx, sc = retrieve_knn(None, None, q, keys, k=64, return_arrays=True, min_score=0.8)
+
+    kn = torch.nn.functional.normalize(torch.from_numpy(keys).to(gpu_device).double(), dim=1)
+    qn = torch.nn.functional.normalize(torch.from_numpy(q).to(gpu_device).double(), dim=1)
+    kf, qf = kn.float(), qn.float()
+    n_near_in = n_near_out = n_over16 = 0
+    for lo in range(0, len(q), 512):
+        s = qn[lo:lo + 512] @ kn.T
+        cand = torch.nonzero(s >= 0.79).cpu().numpy()
+        s_h = s[cand[:, 0], cand[:, 1]].cpu().numpy()
+        for r in np.unique(cand[:, 0]):
+            sel = cand[:, 0] == r
+            cols, s64 = cand[sel, 1], s_h[sel]
+            qi = lo + r
+            b = split_score_bound(kf[cols], qf[qi:qi + 1])[0].cpu().numpy() + 2.0 ** -21
+            got = {int(j): float(v) for j, v in zip(idx[qi], sc[qi]) if j >= 0}
+            must = cols[s64 >= 0.8 + b]
+            assert set(must.tolist()) <= set(got), (qi, sorted(set(must.tolist()) - set(got)))
+            assert all(v >= 0.8 for v in got.values())
+            at = {int(j): (float(v), float(bb)) for j, v, bb in zip(cols, s64, b)}
+            for j, v in got.items():
+                assert j in at and abs(v - at[j][0]) <= at[j][1], (qi, j, v, at.get(j))
+            near = np.abs(s64 - 0.8) < 1.2e-3
+            n_near_in += int((near & (s64 >= 0.8)).sum())
+            n_near_out += int((near & (s64 < 0.8)).sum())
+            n_over16 += int((s64 >= 0.8).sum() > 16)
+        del s
+    assert n_near_in > 0 and n_near_out > 0 and n_over16 > 0
