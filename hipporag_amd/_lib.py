@@ -114,6 +114,13 @@ SIGNATURES = {
     "hrag_topk_rows": (C.c_int, [_P, _I32, _I64, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     "hrag_topk_rows_workspace_bytes": (C.c_int64, [_I32, _I64, _I32]),
     "hrag_topk_rows_ws": (C.c_int, [_P, _I32, _I64, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "hrag_topk_rows_masked": (C.c_int, [_P, _I32, _I64, _I64, _I32, _I32, _I32, _P, _I64, _I64, _P, _P, _P, _P, _P,
+                                        C.c_size_t, _P]),
+    "hrag_retrieve_filtered": (C.c_int, [_P, _P, _I32, _P, _P, _P, _I32, _I32, _F32, _F32, _I32, _I32, _F32, _I32, _P, _P,
+                                         _P, _P, _P, _P, _P, _I64]),
+    "hrag_retrieve_scored_filtered": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _I32, _I32, _F32, _F32, _I32, _I32, _F32,
+                                                _I32, _P, _P, _P, _P, _P, _P, _P, _I64]),
+    "hrag_dense_retrieve_filtered": (C.c_int, [_P, _P, _I32, _I32, _P, _P, _P, _P, _I64]),
     "hrag_ppr_sweeps": (C.c_int, [_P, _I32, _I32, _F32, _I32, _P]),
     "hrag_ppr_layout": (C.c_int, [_P, _I32, C.POINTER(_I32), C.POINTER(_I32)]),
     "hrag_row_minmax": (C.c_int, [_P, _I32, _I64, _I64, _P, _P, _P]),
@@ -141,10 +148,13 @@ SIGNATURES = {
     "hrag_shard_ppr_decide": (C.c_int, [_P, _I32, _P]),
     "hrag_shard_ppr_gate": (C.c_int, [_P, _I32, C.POINTER(_I32), _P]),
     "hrag_shard_finish": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
+    "hrag_shard_finish_filtered": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _I64]),
     "hrag_shard_workspace_bytes": (C.c_int64, [_P, _I32, _I32, _I32]),
     "hrag_shard_score_facts_all": (C.c_int, [_P, C.POINTER(Comm), _P, _I32, _I32, _P, _I64, _P, _P, _P]),
     "hrag_shard_retrieve": (C.c_int, [_P, C.POINTER(Comm), _P, _I32, _P, _P, _P, _I32, _I32, _F32, _F32, _I32, _I32, _F32, _I32,
                                       _I32, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P]),
+    "hrag_shard_retrieve_filtered": (C.c_int, [_P, C.POINTER(Comm), _P, _I32, _P, _P, _P, _I32, _I32, _F32, _F32, _I32, _I32,
+                                               _F32, _I32, _I32, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _I64]),
     "hrag_engine_set_flags": (C.c_int, [_P, _I32, _I32]),
     "hrag_engine_gather_embeddings": (C.c_int, [_P, _I32, _P, _I64, _P, _P, _P]),
     "hrag_get_timings": (C.c_int, [_P, C.POINTER(Timings)]),

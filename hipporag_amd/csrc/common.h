@@ -458,10 +458,18 @@ enum TopkNorm { kNormNone = 0, kNormMinMax = 1 };
 // ws / ws_bytes: optional workspace (kTopkWsBytes) that lets small batches split every row over
 // several workgroups (two-level selection, same result)
 constexpr size_t kTopkWsBytes = (size_t)64 * 4096 * 8 + (size_t)64 * 64 * 8;
+// doc filter of the ranking (include/hrag.h, hrag_topk_rows_masked): element i of row r may be selected when bit
+// (bit_offset + i) of the uint32 words at words + r * ld_words is set (ld_words 0: one row for the whole batch).  A
+// masked-out element gets key 0 (an empty slot); the row min / max still cover every element
+struct TopkMask {
+    const uint32_t *words;
+    int64_t ld_words;
+    int64_t bit_offset;
+};
 hrag_status launch_row_topk(const float *scores, int32_t batch, int64_t n, int64_t ld, int32_t k,
                             int32_t idx_offset, TopkNorm norm, int32_t *idx_out, float *val_out,
                             float *mn_out, float *mx_out, hipStream_t s, void *ws = nullptr,
-                            size_t ws_bytes = 0);
+                            size_t ws_bytes = 0, const TopkMask *mask = nullptr);
 hrag_status launch_row_minmax(const float *scores, int32_t batch, int64_t n, int64_t ld,
                               float *mn_out, float *mx_out, hipStream_t s, float *sum_out = nullptr);
 // K4' (topk.hip): the same ranking and output for any k > kTopkMax.  kk = min(k, n) <= kLargeTile keys are selected,
@@ -471,7 +479,8 @@ constexpr int kLargeTile = 16384;   // keys per LDS sort (128 KiB)
 int64_t topk_large_ws_bytes(int32_t batch, int64_t n, int32_t k);
 hrag_status launch_row_topk_large(const float *scores, int32_t batch, int64_t n, int64_t ld, int32_t k,
                                   int32_t idx_offset, TopkNorm norm, int32_t *idx_out, float *val_out, float *mn_out,
-                                  float *mx_out, hipStream_t s, void *ws, size_t ws_bytes);
+                                  float *mx_out, hipStream_t s, void *ws, size_t ws_bytes,
+                                  const TopkMask *mask = nullptr);
 
 // knn.hip : fp32 rows -> the 3 * dim bf16 layout of HRAG_F32_SPLIT engines ([hi | lo | hi]; queries [hi | hi | lo])
 hrag_status launch_split3(const float *x, int64_t rows, int32_t dim, int32_t as_query, uint16_t *out, hipStream_t s,

@@ -1135,6 +1135,21 @@ hrag_status hrag_topk_rows_ws(const float *scores, int32_t batch, int64_t n, int
                                  workspace, workspace_bytes);
 }
 
+hrag_status hrag_topk_rows_masked(const float *scores, int32_t batch, int64_t n, int64_t ld, int32_t k, int32_t idx_offset,
+                                  int32_t normalize, const uint32_t *mask_dev, int64_t mask_ld_words,
+                                  int64_t mask_bit_offset, int32_t *idx_out, float *val_out, float *mn, float *mx,
+                                  void *workspace, size_t workspace_bytes, hrag_stream stream) {
+    HRAG_REQUIRE(scores && idx_out && val_out && batch >= 1 && n >= 0 && ld >= n && k >= 1, "bad argument");
+    HRAG_REQUIRE(mask_dev != nullptr, "NULL mask (hrag_topk_rows_ws ranks every element)");
+    const TopkNorm norm = normalize ? kNormMinMax : kNormNone;
+    const TopkMask m{mask_dev, mask_ld_words, mask_bit_offset};
+    if (k <= kTopkMax)   // a workspace, when given, lets a small batch split its rows as the engine's ranking does
+        return launch_row_topk(scores, batch, n, ld, k, idx_offset, norm, idx_out, val_out, mn, mx, (hipStream_t)stream,
+                               workspace, workspace_bytes, &m);
+    return launch_row_topk_large(scores, batch, n, ld, k, idx_offset, norm, idx_out, val_out, mn, mx, (hipStream_t)stream,
+                                 workspace, workspace_bytes, &m);
+}
+
 hrag_status hrag_score_facts(hrag_engine *e, const uint16_t *q, int32_t batch, int32_t k,
                              int32_t *idx_out, float *score_out, hrag_stream stream) {
     HRAG_TRY(check_batch(e, batch));
@@ -1237,8 +1252,12 @@ static hrag_status retrieve_impl(hrag_engine *e, const uint16_t *q_pass, const f
                                  const int32_t *kept_count, int32_t kf, int32_t link_top_k, float damping,
                                  float passage_node_weight, int32_t ppr_iters, int32_t ppr_max_iters, float ppr_tol,
                                  int32_t k, int32_t *doc_idx_out, float *doc_score_out, int32_t *flags_out,
-                                 float *residual_out, int32_t *iters_out, hrag_stream stream) {
+                                 float *residual_out, int32_t *iters_out, hrag_stream stream,
+                                 const uint32_t *filter, int64_t filter_ld_words) {
     HRAG_TRY(check_batch(e, batch));
+    TopkMask fm;
+    const TopkMask *mask = nullptr;
+    HRAG_TRY(doc_filter(e, filter, filter_ld_words, fm, &mask));
     HRAG_REQUIRE(ppr_tol >= 0.f && ppr_tol == ppr_tol, "ppr_tol must be >= 0");
     HRAG_REQUIRE(ppr_tol == 0.f || ppr_tol >= HRAG_PPR_TOL_MIN,
                  "ppr_tol=%g is below HRAG_PPR_TOL_MIN=%g: fp32 arithmetic leaves an error floor of %g however small the "
@@ -1419,7 +1438,7 @@ static hrag_status retrieve_impl(hrag_engine *e, const uint16_t *q_pass, const f
                                      lay, s));
     }
     HRAG_TRY(launch_flag_zero_mass(e->d_sums, batch, e->d_flags, 2, s));
-    HRAG_TRY(rank_rows(e, e->d_doc, batch, e->n_passages, k, 0, kNormNone, doc_idx_out, doc_score_out, s));
+    HRAG_TRY(rank_rows(e, e->d_doc, batch, e->n_passages, k, 0, kNormNone, doc_idx_out, doc_score_out, s, mask));
     const bool measured = f8 || est != nullptr;
     if (!f8 && est)
         HRAG_TRY(launch_ppr8_finalize(est, e->d_flags, batch, damping / (1.0f - damping), ppr_tol, sweeps_run, e->d_ctl,
@@ -1456,10 +1475,21 @@ hrag_status hrag_retrieve(hrag_engine *e, const uint16_t *q_pass, int32_t batch,
                           int32_t ppr_iters, int32_t ppr_max_iters, float ppr_tol, int32_t k, int32_t *doc_idx_out,
                           float *doc_score_out, int32_t *flags_out, float *residual_out, int32_t *iters_out,
                           hrag_stream stream) {
+    return hrag_retrieve_filtered(e, q_pass, batch, kept_idx, kept_score, kept_count, kf, link_top_k, damping,
+                                  passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol, k, doc_idx_out, doc_score_out,
+                                  flags_out, residual_out, iters_out, stream, nullptr, 0);
+}
+
+hrag_status hrag_retrieve_filtered(hrag_engine *e, const uint16_t *q_pass, int32_t batch,
+                                   const int32_t *kept_idx, const float *kept_score, const int32_t *kept_count,
+                                   int32_t kf, int32_t link_top_k, float damping, float passage_node_weight,
+                                   int32_t ppr_iters, int32_t ppr_max_iters, float ppr_tol, int32_t k, int32_t *doc_idx_out,
+                                   float *doc_score_out, int32_t *flags_out, float *residual_out, int32_t *iters_out,
+                                   hrag_stream stream, const uint32_t *filter_dev, int64_t filter_ld_words) {
     HRAG_REQUIRE(q_pass != nullptr, "NULL argument");
     return retrieve_impl(e, q_pass, nullptr, 0, batch, kept_idx, kept_score, kept_count, kf, link_top_k, damping,
                          passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol, k, doc_idx_out, doc_score_out,
-                         flags_out, residual_out, iters_out, stream);
+                         flags_out, residual_out, iters_out, stream, filter_dev, filter_ld_words);
 }
 
 hrag_status hrag_retrieve_scored(hrag_engine *e, const float *pass_scores, int64_t pass_ld, int32_t batch,
@@ -1468,10 +1498,22 @@ hrag_status hrag_retrieve_scored(hrag_engine *e, const float *pass_scores, int64
                                  int32_t ppr_iters, int32_t ppr_max_iters, float ppr_tol, int32_t k,
                                  int32_t *doc_idx_out, float *doc_score_out, int32_t *flags_out, float *residual_out,
                                  int32_t *iters_out, hrag_stream stream) {
+    return hrag_retrieve_scored_filtered(e, pass_scores, pass_ld, batch, kept_idx, kept_score, kept_count, kf, link_top_k,
+                                         damping, passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol, k, doc_idx_out,
+                                         doc_score_out, flags_out, residual_out, iters_out, stream, nullptr, 0);
+}
+
+hrag_status hrag_retrieve_scored_filtered(hrag_engine *e, const float *pass_scores, int64_t pass_ld, int32_t batch,
+                                          const int32_t *kept_idx, const float *kept_score, const int32_t *kept_count,
+                                          int32_t kf, int32_t link_top_k, float damping, float passage_node_weight,
+                                          int32_t ppr_iters, int32_t ppr_max_iters, float ppr_tol, int32_t k,
+                                          int32_t *doc_idx_out, float *doc_score_out, int32_t *flags_out,
+                                          float *residual_out, int32_t *iters_out, hrag_stream stream,
+                                          const uint32_t *filter_dev, int64_t filter_ld_words) {
     HRAG_REQUIRE(pass_scores != nullptr, "NULL argument");
     return retrieve_impl(e, nullptr, pass_scores, pass_ld, batch, kept_idx, kept_score, kept_count, kf, link_top_k,
                          damping, passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol, k, doc_idx_out, doc_score_out,
-                         flags_out, residual_out, iters_out, stream);
+                         flags_out, residual_out, iters_out, stream, filter_dev, filter_ld_words);
 }
 
 hrag_status hrag_last_doc_scores(hrag_engine *e, int32_t batch, float *out, int64_t ld, hrag_stream stream) {
@@ -1487,7 +1529,16 @@ hrag_status hrag_last_doc_scores(hrag_engine *e, int32_t batch, float *out, int6
 
 hrag_status hrag_dense_retrieve(hrag_engine *e, const uint16_t *q_pass, int32_t batch, int32_t k,
                                 int32_t *doc_idx_out, float *doc_score_out, hrag_stream stream) {
+    return hrag_dense_retrieve_filtered(e, q_pass, batch, k, doc_idx_out, doc_score_out, stream, nullptr, 0);
+}
+
+hrag_status hrag_dense_retrieve_filtered(hrag_engine *e, const uint16_t *q_pass, int32_t batch, int32_t k,
+                                         int32_t *doc_idx_out, float *doc_score_out, hrag_stream stream,
+                                         const uint32_t *filter_dev, int64_t filter_ld_words) {
     HRAG_TRY(check_batch(e, batch));
+    TopkMask fm;
+    const TopkMask *mask = nullptr;
+    HRAG_TRY(doc_filter(e, filter_dev, filter_ld_words, fm, &mask));
     HRAG_REQUIRE(q_pass && doc_idx_out && doc_score_out, "NULL argument");
     HRAG_REQUIRE(e->p_rows == e->n_passages && e->d_pemb, "hrag_dense_retrieve needs the whole passage matrix");
     HRAG_REQUIRE(k >= 1 && k <= e->max_topk, "k=%d outside [1, max_topk=%d]", k, e->max_topk);
@@ -1497,7 +1548,7 @@ hrag_status hrag_dense_retrieve(hrag_engine *e, const uint16_t *q_pass, int32_t 
     e->counters.queries.fetch_add(batch);
     HRAG_TRY(prep_query(e, q_pass, batch, s, &q_pass));
     HRAG_TRY(launch_sim_gemm(e->d_pemb, e->p_rows, e->kdim, q_pass, batch, e->d_spass, e->ld_p, s, 0, e->emb_dtype));
-    return rank_rows(e, e->d_spass, batch, e->n_passages, k, 0, kNormMinMax, doc_idx_out, doc_score_out, s);
+    return rank_rows(e, e->d_spass, batch, e->n_passages, k, 0, kNormMinMax, doc_idx_out, doc_score_out, s, mask);
 }
 
 hrag_status hrag_ppr(hrag_engine *e, const float *reset, int32_t batch, float damping, int32_t iters,

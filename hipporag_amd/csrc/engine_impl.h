@@ -307,13 +307,33 @@ struct EngineCall {
 
 // the final ranking of [batch, n] score rows (row stride ld_p): K4 for k <= kTopkMax (unchanged), K4' beyond it in the
 // scratch that alloc_workspace sized for max_batch x max_topk
+// mask: the caller's doc filter (hrag_retrieve_filtered), or nullptr for every passage
 inline hrag_status rank_rows(hrag_engine *e, const float *rows, int32_t batch, int64_t n, int32_t k, int32_t idx_offset,
-                             TopkNorm norm, int32_t *idx_out, float *val_out, hipStream_t s) {
+                             TopkNorm norm, int32_t *idx_out, float *val_out, hipStream_t s,
+                             const TopkMask *mask = nullptr) {
     if (k <= kTopkMax)
         return launch_row_topk(rows, batch, n, e->ld_p, k, idx_offset, norm, idx_out, val_out, nullptr, nullptr, s,
-                               e->d_topk_ws, kTopkWsBytes);
+                               e->d_topk_ws, kTopkWsBytes, mask);
     return launch_row_topk_large(rows, batch, n, e->ld_p, k, idx_offset, norm, idx_out, val_out, nullptr, nullptr, s,
-                                 e->d_topk_large, (size_t)e->topk_large_bytes);
+                                 e->d_topk_large, (size_t)e->topk_large_bytes, mask);
+}
+
+// the doc filter of hrag_retrieve_filtered & co. (include/hrag.h): NULL = every passage; filter_ld_words 0 (one row
+// for the batch) or >= ceil(n_passages / 32).  A row shard reads its passages' bits at p_offset.  *out is nullptr for
+// no filter, else &storage
+inline hrag_status doc_filter(const hrag_engine *e, const uint32_t *filter, int64_t filter_ld_words, TopkMask &storage,
+                              const TopkMask **out) {
+    *out = nullptr;
+    if (!filter) return HRAG_OK;
+    const int64_t words = (e->n_passages + 31) / 32;
+    if (filter_ld_words != 0 && filter_ld_words < words) {
+        set_error("filter_ld_words=%lld: 0 (one row for the batch) or >= ceil(n_passages / 32) = %lld",
+                  (long long)filter_ld_words, (long long)words);
+        return HRAG_EINVAL;
+    }
+    storage = TopkMask{filter, filter_ld_words, e->p_offset};
+    *out = &storage;
+    return HRAG_OK;
 }
 
 // the query matrix as the similarity kernels take it: the caller's pointer, or (HRAG_F32_SPLIT) its fp32 rows split

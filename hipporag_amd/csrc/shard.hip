@@ -658,7 +658,18 @@ hrag_status hrag_shard_ppr_gate(hrag_engine *e, int32_t step, int32_t *open_out,
 hrag_status hrag_shard_finish(hrag_engine *e, const float *mn, const float *mx, int32_t *flags, int32_t batch,
                               int32_t k, int32_t *idx_out, float *score_out, float *residual_out, int32_t *iters_out,
                               hrag_stream stream) {
+    return hrag_shard_finish_filtered(e, mn, mx, flags, batch, k, idx_out, score_out, residual_out, iters_out, stream,
+                                      nullptr, 0);
+}
+
+hrag_status hrag_shard_finish_filtered(hrag_engine *e, const float *mn, const float *mx, int32_t *flags, int32_t batch,
+                                       int32_t k, int32_t *idx_out, float *score_out, float *residual_out,
+                                       int32_t *iters_out, hrag_stream stream, const uint32_t *filter_dev,
+                                       int64_t filter_ld_words) {
     HRAG_TRY(shard_batch(e, batch));
+    TopkMask fm;
+    const TopkMask *mask = nullptr;   // the global filter, read at this shard's p_offset
+    HRAG_TRY(doc_filter(e, filter_dev, filter_ld_words, fm, &mask));
     HRAG_REQUIRE(mn && mx && flags && idx_out && score_out, "NULL argument");
     HRAG_REQUIRE(k >= 1 && k <= e->max_topk, "k=%d outside [1, max_topk=%d]", k, e->max_topk);
     HRAG_REQUIRE(e->p8.active && e->p8.batch == batch, "no fp8 PPR session for batch %d", batch);
@@ -674,7 +685,7 @@ hrag_status hrag_shard_finish(hrag_engine *e, const float *mn, const float *mx, 
         return launch_flag_zero_mass(e->d_sums, batch, flags, 2, s);
     }
     HRAG_TRY(ppr8_doc_scores(e, mn, mx, flags, batch, s, true));
-    HRAG_TRY(rank_rows(e, e->d_doc, batch, e->p_rows, k, (int32_t)e->p_offset, kNormNone, idx_out, score_out, s));
+    HRAG_TRY(rank_rows(e, e->d_doc, batch, e->p_rows, k, (int32_t)e->p_offset, kNormNone, idx_out, score_out, s, mask));
     BlitList out;
     out.copy(residual_out, e->d_resid, (int64_t)batch * sizeof(float));
     out.copy(iters_out, e->d_iters_used, (int64_t)batch * sizeof(int32_t));

@@ -173,6 +173,20 @@ hrag_status hrag_shard_retrieve(hrag_engine *e, const hrag_comm *comm, const uin
                                 void *state2, void *workspace, int64_t workspace_bytes, int32_t *doc_idx_out,
                                 float *doc_score_out, int32_t *flags_out, float *residual_out, int32_t *iters_out,
                                 hrag_stream stream) {
+    return hrag_shard_retrieve_filtered(e, comm, q_pass, batch, kept_idx, kept_score, kept_count, kf, link_top_k, damping,
+                                        passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol, k, n_groups, state0, state1,
+                                        state2, workspace, workspace_bytes, doc_idx_out, doc_score_out, flags_out,
+                                        residual_out, iters_out, stream, nullptr, 0);
+}
+
+hrag_status hrag_shard_retrieve_filtered(hrag_engine *e, const hrag_comm *comm, const uint16_t *q_pass, int32_t batch,
+                                         const int32_t *kept_idx, const float *kept_score, const int32_t *kept_count,
+                                         int32_t kf, int32_t link_top_k, float damping, float passage_node_weight,
+                                         int32_t ppr_iters, int32_t ppr_max_iters, float ppr_tol, int32_t k, int32_t n_groups,
+                                         void *state0, void *state1, void *state2, void *workspace, int64_t workspace_bytes,
+                                         int32_t *doc_idx_out, float *doc_score_out, int32_t *flags_out,
+                                         float *residual_out, int32_t *iters_out, hrag_stream stream,
+                                         const uint32_t *filter_dev, int64_t filter_ld_words) {
     HRAG_TRY(check_comm(comm));
     HRAG_REQUIRE(e && q_pass && kept_idx && kept_score && kept_count && state0 && state1 && state2 && workspace &&
                  doc_idx_out && doc_score_out && flags_out, "NULL argument");
@@ -279,8 +293,8 @@ hrag_status hrag_shard_retrieve(hrag_engine *e, const hrag_comm *comm, const uin
         HRAG_TRY(reduce(est, batch, HRAG_COMM_F32, HRAG_COMM_MAX));
         HRAG_TRY(hrag_shard_ppr_est(e, est, 1, stream));
     }
-    HRAG_TRY(hrag_shard_finish(e, mn, mx, flags, batch, k, lidx, lval, contract ? residual_out : nullptr,
-                               contract ? iters_out : nullptr, stream));
+    HRAG_TRY(hrag_shard_finish_filtered(e, mn, mx, flags, batch, k, lidx, lval, contract ? residual_out : nullptr,
+                                        contract ? iters_out : nullptr, stream, filter_dev, filter_ld_words));
     HRAG_TRY(merge_topk(comm, lidx, lval, batch, k, ws, nullptr, nullptr, doc_idx_out, doc_score_out, s));
     // a saturated value is raised on the shard that owns the row: every shard reports it (never clipped scores unnoticed)
     hipLaunchKernelGGL(sat_extract_kernel, dim3((unsigned)ceil_div(batch, 256)), dim3(256), 0, s, flags, batch, sat);

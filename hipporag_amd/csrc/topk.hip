@@ -80,6 +80,89 @@ __device__ __forceinline__ void for_each_in_row(const float *s, int64_t n, int t
     }
 }
 
+// ---- doc filter (TopkMask): one row of the bitset, seen from element 0 of the scores the kernel streams.  bit0 need
+// not be a multiple of 32 (row shards start at p_offset, split parts at part * plen, plen a multiple of 4)
+struct MaskRow {
+    const uint32_t *w;
+    int64_t bit0;
+    // bits of elements i .. i + 3 (every one < n: the words they name exist), bit u for element i + u
+    __device__ __forceinline__ uint32_t nibble(int64_t i) const {
+        const int64_t b = bit0 + i;
+        const int sh = (int)(b & 31);
+        uint32_t v = w[b >> 5] >> sh;
+        if (sh > 28) v |= w[(b >> 5) + 1] << (32 - sh);
+        return v;
+    }
+    __device__ __forceinline__ bool test(int64_t i) const {
+        const int64_t b = bit0 + i;
+        return (w[b >> 5] >> (b & 31)) & 1u;
+    }
+};
+
+// set bits among elements [0, n) of the row (a popcount over n / 32 words: 1/32 of the score bytes); every thread
+// gets the count.  acc: an LDS word, free again when this returns
+__device__ __forceinline__ int64_t mask_count(const MaskRow &m, int64_t n, int tid, unsigned int *acc) {
+    if (tid == 0) *acc = 0;
+    __syncthreads();
+    const int sh = (int)(m.bit0 & 31);
+    const uint32_t *w = m.w + (m.bit0 >> 5);
+    unsigned int c = 0;
+    for (int64_t t = tid; t * 32 < n; t += TK_THREADS) {
+        const int valid = n - t * 32 < 32 ? (int)(n - t * 32) : 32;   // bits at or above n are ignored
+        uint32_t v = w[t] >> sh;
+        if (sh + valid > 32) v |= w[t + 1] << (32 - sh);               // (sh > 0 here: the word exists)
+        if (valid < 32) v &= (1u << valid) - 1u;
+        c += (unsigned int)__popc(v);
+    }
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if ((tid & 63) == 0 && c) atomicAdd(acc, c);
+    __syncthreads();
+    const unsigned int r = *acc;
+    __syncthreads();
+    return (int64_t)r;
+}
+
+// for_each_in_row with the ranking key of every element: f(v, key).  Masked: a masked-out element has key 0 (no real
+// key is 0, common.h), so it never passes a threshold >= 1.  The unmasked form is for_each_in_row + rank_key as before
+template <bool kMasked, typename F>
+__device__ __forceinline__ void for_each_key(const float *s, int64_t n, int tid, const MaskRow &m, F f) {
+    if constexpr (!kMasked) {
+        for_each_in_row(s, n, tid, [&](float v, uint32_t i) { f(v, rank_key(v, i)); });
+    } else {
+        const bool vec = (reinterpret_cast<uintptr_t>(s) & 15) == 0;
+        auto four = [&](const float4 &v, uint32_t b, uint32_t bits) {   // one mask read per four scores
+            f(v.x, (bits & 1u) ? rank_key(v.x, b) : 0ull);
+            f(v.y, (bits & 2u) ? rank_key(v.y, b + 1) : 0ull);
+            f(v.z, (bits & 4u) ? rank_key(v.z, b + 2) : 0ull);
+            f(v.w, (bits & 8u) ? rank_key(v.w, b + 3) : 0ull);
+        };
+        if (vec) {
+            const int64_t n4 = n >> 2;
+            const float4 *s4 = reinterpret_cast<const float4 *>(s);
+            int64_t i = tid;
+            for (; i + 3 * TK_THREADS < n4; i += 4 * TK_THREADS) {   // the loads of for_each_in_row, bits alongside
+                const float4 v0 = s4[i], v1 = s4[i + TK_THREADS], v2 = s4[i + 2 * TK_THREADS], v3 = s4[i + 3 * TK_THREADS];
+                const uint32_t m0 = m.nibble(4 * i), m1 = m.nibble(4 * (i + TK_THREADS)),
+                               m2 = m.nibble(4 * (i + 2 * TK_THREADS)), m3 = m.nibble(4 * (i + 3 * TK_THREADS));
+                four(v0, (uint32_t)(4 * i), m0);
+                four(v1, (uint32_t)(4 * (i + TK_THREADS)), m1);
+                four(v2, (uint32_t)(4 * (i + 2 * TK_THREADS)), m2);
+                four(v3, (uint32_t)(4 * (i + 3 * TK_THREADS)), m3);
+            }
+            for (; i < n4; i += TK_THREADS) four(s4[i], (uint32_t)(4 * i), m.nibble(4 * i));
+            for (int64_t i = (n4 << 2) + tid; i < n; i += TK_THREADS) {
+                const float v = s[i];
+                f(v, m.test(i) ? rank_key(v, (uint32_t)i) : 0ull);
+            }
+        } else {
+            for (int64_t i = tid; i < n; i += TK_THREADS) {
+                const float v = s[i];
+                f(v, m.test(i) ? rank_key(v, (uint32_t)i) : 0ull);
+            }
+        }
+    }
+}
+
 __device__ __forceinline__ float wave_min(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
     return v;
@@ -105,10 +188,13 @@ __device__ __forceinline__ float minmax_norm(float s, float mn, float mx) {
 // parts > 1: workgroup (row_in * parts + part) selects from the slice [part * plen, +plen) of input
 // row row_in and writes its k candidates (global positions, raw values) as output row blockIdx.x;
 // topk_merge_kernel then picks the final k.
+// kMasked: only the elements the mask allows are ranked (a part's target is min(k, its allowed count)); the row min /
+// max still cover every element
+template <bool kMasked>
 __global__ __launch_bounds__(TK_THREADS) void row_topk_kernel(
     const float *__restrict__ scores, int64_t n_total, int64_t ld, int32_t k, int32_t idx_offset_in,
     int32_t norm, int32_t *__restrict__ idx_out, float *__restrict__ val_out,
-    float *__restrict__ mn_out, float *__restrict__ mx_out, int32_t parts, int64_t plen) {
+    float *__restrict__ mn_out, float *__restrict__ mx_out, int32_t parts, int64_t plen, TopkMask mask) {
     __shared__ uint64_t buf[TK_CAP];
     __shared__ float red_mn[TK_THREADS / 64], red_mx[TK_THREADS / 64];
     __shared__ unsigned int s_count;
@@ -120,14 +206,20 @@ __global__ __launch_bounds__(TK_THREADS) void row_topk_kernel(
     int64_t n = parts > 1 ? n_total - (int64_t)part * plen : n_total;
     n = n < 0 ? 0 : (parts > 1 && n > plen ? plen : n);
     const int32_t idx_offset = parts > 1 ? (int32_t)(part * plen) : idx_offset_in;
-    const int kk = (int)((int64_t)k < n ? (int64_t)k : n);
+    MaskRow mrow{nullptr, 0};
+    int64_t n_sel = n;   // elements that may be selected
+    if constexpr (kMasked) {
+        mrow.w = mask.words + (size_t)row_in * (size_t)mask.ld_words;
+        mrow.bit0 = mask.bit_offset + (parts > 1 ? (int64_t)part * plen : 0);
+        n_sel = mask_count(mrow, n, tid, &s_count);
+    }
+    const int kk = (int)((int64_t)k < n_sel ? (int64_t)k : n_sel);
 
     // ---- pass 1: thread-local top-2 + min / max
     uint64_t t0 = 0, t1 = 0;
     float mn = INFINITY, mx = -INFINITY;
-    for_each_in_row(s, n, tid, [&](float v, uint32_t i) {
+    for_each_key<kMasked>(s, n, tid, mrow, [&](float v, uint64_t key) {
         minmax_add(mn, mx, v);
-        const uint64_t key = rank_key(v, i);
         if (key > t1) {
             if (key > t0) {
                 t1 = t0;
@@ -187,6 +279,7 @@ __global__ __launch_bounds__(TK_THREADS) void row_topk_kernel(
     __syncthreads();
     uint64_t thresh = wave_rth[0];
     for (int w = 1; w < TK_THREADS / 64; ++w) thresh = wave_rth[w] < thresh ? wave_rth[w] : thresh;
+    if constexpr (kMasked) thresh = thresh ? thresh : 1;   // "everything" means every allowed key, never key 0
     __syncthreads();
 
     // ---- pass 2: collect candidates >= thresh (refine the bound first if they would not fit)
@@ -195,8 +288,7 @@ __global__ __launch_bounds__(TK_THREADS) void row_topk_kernel(
     auto collect = [&](uint64_t t) -> unsigned int {
         if (tid == 0) s_count = 0;
         __syncthreads();
-        for_each_in_row(s, n, tid, [&](float v, uint32_t i) {
-            const uint64_t key = rank_key(v, i);
+        for_each_key<kMasked>(s, n, tid, mrow, [&](float, uint64_t key) {
             if (key >= t) {
                 const unsigned int slot = atomicAdd(&s_count, 1u);
                 if (slot < TK_CAP) buf[slot] = key;
@@ -229,8 +321,7 @@ __global__ __launch_bounds__(TK_THREADS) void row_topk_kernel(
             hist[tid] = 0;
             if (tid == 0) s_count = 0;                             // the bin search below never reads a stale count
             __syncthreads();
-            for_each_in_row(s, n, tid, [&](float v, uint32_t i) {
-                const uint64_t key = rank_key(v, i);
+            for_each_key<kMasked>(s, n, tid, mrow, [&](float, uint64_t key) {
                 if (key >= lo && key <= hi) atomicAdd(&hist[(unsigned int)((key - lo) >> shift)], 1u);
             });
             __syncthreads();
@@ -320,7 +411,10 @@ __global__ __launch_bounds__(TK_THREADS) void row_minmax_kernel(const float *__r
     }
 }
 
-// second level of the split selection: parts * k candidates per row (keys are unique), parts * k <= TK_CAP
+// second level of the split selection: parts * k candidates per row (keys are unique), parts * k <= TK_CAP.
+// kMasked: a part with fewer than k allowed elements left -1 slots (key 0 here), which sort last: a slot whose key is 0
+// writes -1 / 0 (the row's target min(k, allowed) is then met without counting)
+template <bool kMasked>
 __global__ __launch_bounds__(TK_THREADS) void topk_merge_kernel(
     const int32_t *__restrict__ cand_idx, const float *__restrict__ cand_val,
     const float *__restrict__ part_mn, const float *__restrict__ part_mx, int32_t parts, int32_t k,
@@ -355,7 +449,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_merge_kernel(
     for (int j = tid; j < k; j += TK_THREADS) {
         int32_t idx = -1;
         float val = 0.f;
-        if (j < kk) {
+        if (j < kk && (!kMasked || buf[j] != 0)) {
             const uint64_t key = buf[j];
             idx = (int32_t)(uint32_t)key + idx_offset;
             val = ordered_to_f32((uint32_t)(key >> 32));
@@ -393,10 +487,13 @@ __device__ __forceinline__ void wave_append(bool take, unsigned int *counter, F 
     if (take) store(base + (unsigned int)__popcll(m & ((1ull << lane) - 1ull)));
 }
 
+// kMasked: kk = min(k, allowed elements of the row), the search and the compaction see allowed keys only (lo starts
+// at 1, above key 0); the row min / max still cover every element
+template <bool kMasked>
 __global__ __launch_bounds__(TK_THREADS) void large_select_kernel(
     const float *__restrict__ scores, int64_t n, int64_t ld, int32_t k, int32_t idx_offset, int32_t norm,
     int32_t *__restrict__ idx_out, float *__restrict__ val_out, float *__restrict__ mn_out, float *__restrict__ mx_out,
-    uint64_t *__restrict__ keys, int64_t L, float *__restrict__ row_mnmx) {
+    uint64_t *__restrict__ keys, int64_t L, float *__restrict__ row_mnmx, TopkMask mask) {
     extern __shared__ uint64_t lbuf[];   // kLargeTile keys (keys == nullptr), or the histogram only
     __shared__ float red_mn[TK_THREADS / 64], red_mx[TK_THREADS / 64];
     __shared__ unsigned int s_count, s_bin;
@@ -406,12 +503,19 @@ __global__ __launch_bounds__(TK_THREADS) void large_select_kernel(
     const int tid = threadIdx.x;
     const int row = blockIdx.x;
     const float *s = scores + (size_t)row * ld;
-    const int64_t kk = (int64_t)k < n ? (int64_t)k : n;
+    MaskRow mrow{nullptr, 0};
+    int64_t n_sel = n;   // elements that may be selected
+    if constexpr (kMasked) {
+        mrow.w = mask.words + (size_t)row * (size_t)mask.ld_words;
+        mrow.bit0 = mask.bit_offset;
+        n_sel = mask_count(mrow, n, tid, &s_count);
+    }
+    const int64_t kk = (int64_t)k < n_sel ? (int64_t)k : n_sel;
 
     // ---- select: the exact kk-th largest key.  Invariant: count(key > hi) = above < kk <= above + count(lo <= key <= hi)
-    uint64_t thresh = 0;
-    if (kk < n) {
-        uint64_t lo = 0, hi = ~0ull;
+    uint64_t thresh = kMasked ? 1 : 0;
+    if (kk < n_sel) {
+        uint64_t lo = kMasked ? 1 : 0, hi = ~0ull;
         unsigned int above = 0;
         for (;;) {
             const uint64_t width = hi - lo;
@@ -420,8 +524,7 @@ __global__ __launch_bounds__(TK_THREADS) void large_select_kernel(
             hist[tid] = 0;
             if (tid == 0) s_bin = 0;
             __syncthreads();
-            for_each_in_row(s, n, tid, [&](float v, uint32_t i) {
-                const uint64_t key = rank_key(v, i);
+            for_each_key<kMasked>(s, n, tid, mrow, [&](float, uint64_t key) {
                 if (key >= lo && key <= hi) atomicAdd(&hist[(unsigned int)((key - lo) >> shift)], 1u);
             });
             __syncthreads();
@@ -458,9 +561,8 @@ __global__ __launch_bounds__(TK_THREADS) void large_select_kernel(
     __syncthreads();
     uint64_t *grow = keys ? keys + (size_t)row * L : nullptr;
     float mn = INFINITY, mx = -INFINITY;
-    for_each_in_row(s, n, tid, [&](float v, uint32_t i) {
+    for_each_key<kMasked>(s, n, tid, mrow, [&](float v, uint64_t key) {
         minmax_add(mn, mx, v);
-        const uint64_t key = rank_key(v, i);
         wave_append(key >= thresh, &s_count, [&](unsigned int slot) {
             if (slot < (unsigned int)kk) {
                 if (grow) grow[slot] = key; else lbuf[slot] = key;
@@ -525,6 +627,8 @@ __global__ __launch_bounds__(TK_THREADS) void large_tile_sort_kernel(uint64_t *_
 // Thread t emits the kMergeSpan outputs starting at o0 = t * kMergeSpan; its co-rank (how many come from the first run)
 // is found by binary search, ties taken from the first run (only the zero padding repeats a key).
 // last: write the indices / scores of the outputs o < k (and -1 / 0 for kk <= o < k) instead of keys.
+// kMasked: kk is the host's min(k, n); a row with fewer allowed elements is padded with key 0, which writes -1 / 0
+template <bool kMasked>
 __global__ __launch_bounds__(TK_THREADS) void large_merge_kernel(
     const uint64_t *__restrict__ src, uint64_t *__restrict__ dst, int64_t L, int64_t w, int32_t last, int32_t k,
     int64_t kk, int32_t idx_offset, int32_t norm, const float *__restrict__ row_mnmx, int32_t *__restrict__ idx_out,
@@ -565,7 +669,7 @@ __global__ __launch_bounds__(TK_THREADS) void large_merge_kernel(
         if (o >= k) break;
         int32_t idx = -1;
         float val = 0.f;
-        if (o < kk) {
+        if (o < kk && (!kMasked || out[u] != 0)) {
             idx = (int32_t)(uint32_t)out[u] + idx_offset;
             val = ordered_to_f32((uint32_t)(out[u] >> 32));
             if (norm == kNormMinMax) val = minmax_norm(val, mn, mx);
@@ -577,11 +681,24 @@ __global__ __launch_bounds__(TK_THREADS) void large_merge_kernel(
 
 }  // namespace
 
+// a filter row must hold the bits [bit_offset, bit_offset + n); rows closer than that would overlap
+static hrag_status check_mask(const TopkMask *m, int64_t n) {
+    if (!m) return HRAG_OK;
+    HRAG_REQUIRE(m->words != nullptr, "top-k filter: NULL mask");
+    HRAG_REQUIRE(m->bit_offset >= 0, "top-k filter: bit offset %lld < 0", (long long)m->bit_offset);
+    HRAG_REQUIRE(m->ld_words == 0 || m->ld_words >= ceil_div(m->bit_offset + n, 32),
+                 "top-k filter: %lld words per row < %lld (0: one row for the batch)", (long long)m->ld_words,
+                 (long long)ceil_div(m->bit_offset + n, 32));
+    return HRAG_OK;
+}
+
 hrag_status launch_row_topk(const float *scores, int32_t batch, int64_t n, int64_t ld, int32_t k,
                             int32_t idx_offset, TopkNorm norm, int32_t *idx_out, float *val_out,
-                            float *mn_out, float *mx_out, hipStream_t s, void *ws, size_t ws_bytes) {
+                            float *mn_out, float *mx_out, hipStream_t s, void *ws, size_t ws_bytes,
+                            const TopkMask *mask) {
     HRAG_REQUIRE(k >= 1 && k <= kTopkMax, "top-k k=%d outside [1, %d]", k, kTopkMax);
     HRAG_REQUIRE(n >= 0 && n < (int64_t)0xffffffffll, "row length %lld not supported", (long long)n);
+    HRAG_TRY(check_mask(mask, n));
     if (batch == 0) return HRAG_OK;
     // one workgroup per row leaves the chip idle for a handful of rows: split long rows
     int parts = 1;
@@ -592,9 +709,14 @@ hrag_status launch_row_topk(const float *scores, int32_t batch, int64_t n, int64
         parts = std::min(parts, 64);
         while (parts > 1 && (size_t)batch * parts * ((size_t)k * 8 + 8) > ws_bytes) --parts;
     }
+    const TopkMask m = mask ? *mask : TopkMask{nullptr, 0, 0};
     if (parts <= 1) {
-        hipLaunchKernelGGL(row_topk_kernel, dim3((unsigned)batch), dim3(TK_THREADS), 0, s, scores, n, ld, k,
-                           idx_offset, (int32_t)norm, idx_out, val_out, mn_out, mx_out, 1, (int64_t)0);
+        if (mask)
+            hipLaunchKernelGGL(row_topk_kernel<true>, dim3((unsigned)batch), dim3(TK_THREADS), 0, s, scores, n, ld, k,
+                               idx_offset, (int32_t)norm, idx_out, val_out, mn_out, mx_out, 1, (int64_t)0, m);
+        else
+            hipLaunchKernelGGL(row_topk_kernel<false>, dim3((unsigned)batch), dim3(TK_THREADS), 0, s, scores, n, ld, k,
+                               idx_offset, (int32_t)norm, idx_out, val_out, mn_out, mx_out, 1, (int64_t)0, m);
         HRAG_LAUNCH_CHECK();
         return HRAG_OK;
     }
@@ -604,11 +726,19 @@ hrag_status launch_row_topk(const float *scores, int32_t batch, int64_t n, int64
     float *c_val = reinterpret_cast<float *>(c_idx + n_cand);
     float *p_mn = c_val + n_cand;
     float *p_mx = p_mn + (size_t)batch * parts;
-    hipLaunchKernelGGL(row_topk_kernel, dim3((unsigned)(batch * parts)), dim3(TK_THREADS), 0, s, scores, n, ld,
-                       k, 0, (int32_t)kNormNone, c_idx, c_val, p_mn, p_mx, parts, plen);
-    HRAG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)batch), dim3(TK_THREADS), 0, s, c_idx, c_val, p_mn, p_mx,
-                       parts, k, n, idx_offset, (int32_t)norm, idx_out, val_out, mn_out, mx_out);
+    if (mask) {
+        hipLaunchKernelGGL(row_topk_kernel<true>, dim3((unsigned)(batch * parts)), dim3(TK_THREADS), 0, s, scores, n, ld,
+                           k, 0, (int32_t)kNormNone, c_idx, c_val, p_mn, p_mx, parts, plen, m);
+        HRAG_LAUNCH_CHECK();
+        hipLaunchKernelGGL(topk_merge_kernel<true>, dim3((unsigned)batch), dim3(TK_THREADS), 0, s, c_idx, c_val, p_mn,
+                           p_mx, parts, k, n, idx_offset, (int32_t)norm, idx_out, val_out, mn_out, mx_out);
+    } else {
+        hipLaunchKernelGGL(row_topk_kernel<false>, dim3((unsigned)(batch * parts)), dim3(TK_THREADS), 0, s, scores, n, ld,
+                           k, 0, (int32_t)kNormNone, c_idx, c_val, p_mn, p_mx, parts, plen, m);
+        HRAG_LAUNCH_CHECK();
+        hipLaunchKernelGGL(topk_merge_kernel<false>, dim3((unsigned)batch), dim3(TK_THREADS), 0, s, c_idx, c_val, p_mn,
+                           p_mx, parts, k, n, idx_offset, (int32_t)norm, idx_out, val_out, mn_out, mx_out);
+    }
     HRAG_LAUNCH_CHECK();
     return HRAG_OK;
 }
@@ -623,9 +753,10 @@ int64_t topk_large_ws_bytes(int32_t batch, int64_t n, int32_t k) {
 
 hrag_status launch_row_topk_large(const float *scores, int32_t batch, int64_t n, int64_t ld, int32_t k,
                                   int32_t idx_offset, TopkNorm norm, int32_t *idx_out, float *val_out, float *mn_out,
-                                  float *mx_out, hipStream_t s, void *ws, size_t ws_bytes) {
+                                  float *mx_out, hipStream_t s, void *ws, size_t ws_bytes, const TopkMask *mask) {
     HRAG_REQUIRE(k > kTopkMax, "large top-k path for k > %d only (k=%d)", kTopkMax, k);
     HRAG_REQUIRE(n >= 0 && n < (int64_t)0xffffffffll, "row length %lld not supported", (long long)n);
+    HRAG_TRY(check_mask(mask, n));
     if (batch == 0) return HRAG_OK;
     const int64_t need = topk_large_ws_bytes(batch, n, k);
     HRAG_REQUIRE((int64_t)ws_bytes >= need && (need == 0 || ws != nullptr),
@@ -636,15 +767,19 @@ hrag_status launch_row_topk_large(const float *scores, int32_t batch, int64_t n,
     constexpr int lds_tile = kLargeTile * (int)sizeof(uint64_t);   // 128 KiB: > 64 KiB of dynamic LDS needs the opt-in
     static bool configured = false;
     if (!configured) {
-        HRAG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(large_select_kernel),
+        HRAG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(large_select_kernel<false>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds_tile));
+        HRAG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(large_select_kernel<true>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds_tile));
         HRAG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(large_tile_sort_kernel),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds_tile));
         configured = true;
     }
+    const TopkMask m = mask ? *mask : TopkMask{nullptr, 0, 0};
+    auto select = mask ? large_select_kernel<true> : large_select_kernel<false>;
     if (need == 0) {
-        hipLaunchKernelGGL(large_select_kernel, dim3((unsigned)batch), dim3(TK_THREADS), lds_tile, s, scores, n, ld, k,
-                           idx_offset, (int32_t)norm, idx_out, val_out, mn_out, mx_out, nullptr, (int64_t)0, nullptr);
+        hipLaunchKernelGGL(select, dim3((unsigned)batch), dim3(TK_THREADS), lds_tile, s, scores, n, ld, k,
+                           idx_offset, (int32_t)norm, idx_out, val_out, mn_out, mx_out, nullptr, (int64_t)0, nullptr, m);
         HRAG_LAUNCH_CHECK();
         return HRAG_OK;
     }
@@ -653,17 +788,18 @@ hrag_status launch_row_topk_large(const float *scores, int32_t batch, int64_t n,
     uint64_t *ka = static_cast<uint64_t *>(ws);
     uint64_t *kb = ka + (size_t)batch * L;
     float *row_mnmx = reinterpret_cast<float *>(kb + (size_t)batch * L);
-    hipLaunchKernelGGL(large_select_kernel, dim3((unsigned)batch), dim3(TK_THREADS), 4 * TK_THREADS, s, scores, n, ld, k,
-                       idx_offset, (int32_t)norm, idx_out, val_out, mn_out, mx_out, ka, L, row_mnmx);
+    hipLaunchKernelGGL(select, dim3((unsigned)batch), dim3(TK_THREADS), 4 * TK_THREADS, s, scores, n, ld, k,
+                       idx_offset, (int32_t)norm, idx_out, val_out, mn_out, mx_out, ka, L, row_mnmx, m);
     HRAG_LAUNCH_CHECK();
     hipLaunchKernelGGL(large_tile_sort_kernel, dim3((unsigned)(L / kLargeTile), (unsigned)batch), dim3(TK_THREADS),
                        lds_tile, s, ka, L);
     HRAG_LAUNCH_CHECK();
     const int64_t per_wg = (int64_t)TK_THREADS * kMergeSpan;
+    auto merge = mask ? large_merge_kernel<true> : large_merge_kernel<false>;
     for (int64_t w = kLargeTile; w < L; w *= 2) {
         const bool last = 2 * w >= L;
         const int64_t outs = last ? std::max<int64_t>(L, k) : L;
-        hipLaunchKernelGGL(large_merge_kernel, dim3((unsigned)ceil_div(outs, per_wg), (unsigned)batch), dim3(TK_THREADS),
+        hipLaunchKernelGGL(merge, dim3((unsigned)ceil_div(outs, per_wg), (unsigned)batch), dim3(TK_THREADS),
                            0, s, ka, kb, L, w, (int32_t)last, k, kk, idx_offset, (int32_t)norm, row_mnmx, idx_out,
                            val_out);
         HRAG_LAUNCH_CHECK();

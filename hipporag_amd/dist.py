@@ -395,15 +395,18 @@ class ShardedRetriever:
 
     def retrieve(self, q_pass, kept_idx, kept_score, kept_count, *, link_top_k=5, damping=0.5,
                  passage_node_weight=0.05, ppr_iters=20, k=200, ppr_tol=0.0, ppr_max_iters=0,
-                 check_saturation=True):
+                 check_saturation=True, doc_filter=None):
         """Returns (doc ids, doc scores, flags) -- and with ppr_tol > 0 additionally (residual, sweeps used): the
         convergence contract of hrag_retrieve on the shards.  Every shard measures the relative update of ITS
         passages; the measures are all-reduced (MAX) before every decision, so all shards run the same steps.
         check_saturation: the row shards have no wider state to repeat a batch on, so a batch that raised
         HRAG_FLAG_FP8_SATURATED (a violated scale bound: never on valid inputs) raises here instead of handing
         clipped scores on (include/hrag.h: "never return clipped scores"); it costs one host read per batch --
-        a timing loop passes False and checks the flags afterwards."""
+        a timing loop passes False and checks the flags afterwards.
+        doc_filter: the GLOBAL doc filter (engine.doc_filter_words forms, over all passages); every shard ranks only the
+        allowed passages of its slice, the merge puts a shard's -1 slots after every real entry."""
         st, c = self.st, self.comm
+        fkw = {} if doc_filter is None else {"doc_filter": doc_filter}
         b = q_pass.shape[0]
         lay, bufs = self._state(b)
         mn, mx = st.shard_passage_scores(q_pass)
@@ -449,9 +452,9 @@ class ShardedRetriever:
         if contract:
             if not est_global:
                 st.shard_ppr_est(c.all_reduce(st.shard_ppr_est(), "max"))
-            idx, val, resid, used = st.shard_finish(mn, mx, flags, k, True)
+            idx, val, resid, used = st.shard_finish(mn, mx, flags, k, True, **fkw)
         else:
-            idx, val = st.shard_finish(mn, mx, flags, k)
+            idx, val = st.shard_finish(mn, mx, flags, k, **fkw)
         top_idx, top_val = merge_ranked(c.all_gather(idx), c.all_gather(val), k, st.topk)
         sat = (flags & 8).contiguous()               # raised on the shard that owns the row that saturated
         c.all_reduce(sat, "max")
@@ -568,8 +571,9 @@ class NativeShardedRetriever:
         return idx, val
 
     def retrieve(self, q_pass, kept_idx, kept_score, kept_count, *, link_top_k=5, damping=0.5, passage_node_weight=0.05,
-                 ppr_iters=20, k=200, ppr_tol=0.0, ppr_max_iters=0, check_saturation=True):
-        """Same contract as ShardedRetriever.retrieve: (doc ids, doc scores, flags[, residual, sweeps used])."""
+                 ppr_iters=20, k=200, ppr_tol=0.0, ppr_max_iters=0, check_saturation=True, doc_filter=None):
+        """Same contract as ShardedRetriever.retrieve: (doc ids, doc scores, flags[, residual, sweeps used]);
+        doc_filter: hrag_shard_retrieve_filtered with the global filter."""
         torch = _td()[0]
         from .engine import _stream
         q = self.st.e._q(q_pass)
@@ -588,11 +592,17 @@ class NativeShardedRetriever:
         used = torch.empty((b,), dtype=torch.int32, device=dev) if contract else None
         self._regions, self._cur, self._pend = [ws] + list(bufs), (lay, bufs), {}
         self.st.e._p8_batch = b
-        self._call(self._lib.hrag_shard_retrieve, self.st.h, ctypes.byref(self._c), q.data_ptr(), b, kept_idx.data_ptr(),
-                   kept_score.data_ptr(), kept_count.data_ptr(), kept_idx.shape[1], link_top_k, damping, passage_node_weight,
-                   ppr_iters, max(ppr_max_iters, ppr_iters), ppr_tol, k, lay.n_groups, bufs[0].data_ptr(),
-                   bufs[1].data_ptr(), bufs[2].data_ptr(), ws.data_ptr(), ws.numel(), idx.data_ptr(), val.data_ptr(),
-                   flags.data_ptr(), resid.data_ptr() if contract else None, used.data_ptr() if contract else None, _stream())
+        args = (self.st.h, ctypes.byref(self._c), q.data_ptr(), b, kept_idx.data_ptr(), kept_score.data_ptr(),
+                kept_count.data_ptr(), kept_idx.shape[1], link_top_k, damping, passage_node_weight, ppr_iters,
+                max(ppr_max_iters, ppr_iters), ppr_tol, k, lay.n_groups, bufs[0].data_ptr(), bufs[1].data_ptr(),
+                bufs[2].data_ptr(), ws.data_ptr(), ws.numel(), idx.data_ptr(), val.data_ptr(), flags.data_ptr(),
+                resid.data_ptr() if contract else None, used.data_ptr() if contract else None, _stream())
+        if doc_filter is None:
+            self._call(self._lib.hrag_shard_retrieve, *args)
+        else:
+            from .engine import doc_filter_words
+            fw, fld = doc_filter_words(doc_filter, self.st.e.n_passages, b, dev)
+            self._call(self._lib.hrag_shard_retrieve_filtered, *args, fw.data_ptr(), fld)
         if check_saturation and bool((flags & 8).any()):
             raise RuntimeError("fp8 PPR state saturated on a row shard (HRAG_FLAG_FP8_SATURATED): a static scale bound "
                                "was violated; use the replica / hybrid mode for this batch")
@@ -638,11 +648,15 @@ class HybridRetriever:
         return slice(r * (batch // w), (r + 1) * (batch // w))
 
     def retrieve(self, q_pass, kept_idx, kept_score, kept_count, **kw):
-        """q_pass / kept_*: the GLOBAL batch (replicated); returns this rank's RetrieveOutput for its B / N queries."""
+        """q_pass / kept_*: the GLOBAL batch (replicated); returns this rank's RetrieveOutput for its B / N queries.
+        kw["doc_filter"] (optional): the global batch's filter; a per-query one is cut to this rank's rows."""
         torch = _td()[0]
         c, w = self.comm, self.comm.world
         b = q_pass.shape[0]
         mine = self.my_rows(b)
+        f = kw.get("doc_filter")
+        if f is not None and f.dim() == 2:
+            kw["doc_filter"] = f[mine]
         bn = b // w
         s_local = self.sim.e.sim_scores("passages", q_pass)                     # [B, Np_local]
         parts = [s_local[d * bn:(d + 1) * bn] for d in range(w)]

@@ -42,6 +42,46 @@ def _stream() -> int:
     return _torch().cuda.current_stream().cuda_stream
 
 
+def pack_mask(mask) -> np.ndarray:
+    """Host bool [..., n] -> the doc filter's bitset (include/hrag.h): uint32 [..., ceil(n / 32)], bit (j & 31) of word
+    j >> 5 set when j is allowed -- np.packbits(bitorder="little"), each row padded to 4 bytes, read little-endian."""
+    m = np.asarray(mask, dtype=bool)
+    n = m.shape[-1]
+    w = (n + 31) // 32
+    b = np.packbits(m, axis=-1, bitorder="little")
+    pad = np.zeros(m.shape[:-1] + (4 * w,), np.uint8)
+    pad[..., :b.shape[-1]] = b
+    return pad.view("<u4").astype(np.uint32, copy=False)
+
+
+def doc_filter_words(doc_filter, n: int, batch: int, device):
+    """A doc filter -- torch bool [n] or [batch, n], or the packed uint32 (or int32) words [W] or [batch, W],
+    W >= ceil(n / 32) -- as (int32 device words, filter_ld_words): ld 0 for one row shared by the batch."""
+    torch = _torch()
+    t = doc_filter if isinstance(doc_filter, torch.Tensor) else None
+    if t is None:
+        raise TypeError(f"doc_filter must be a torch tensor (bool or packed uint32), not {type(doc_filter).__name__}")
+    if t.dim() not in (1, 2) or (t.dim() == 2 and t.shape[0] != batch):
+        raise ValueError(f"doc_filter of shape {tuple(t.shape)}: [n] or [batch={batch}, n] expected")
+    words = (n + 31) // 32
+    if t.dtype == torch.bool:
+        if t.shape[-1] != n:
+            raise ValueError(f"doc_filter has {t.shape[-1]} entries, the engine ranks {n} passages")
+        bits = torch.zeros(t.shape[:-1] + (words * 32,), dtype=torch.int64, device=device)
+        bits[..., :n] = t.to(device)
+        w = (bits.view(*t.shape[:-1], words, 32) << torch.arange(32, device=device, dtype=torch.int64)).sum(-1)
+        w = torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
+    elif t.dtype == torch.int32 or str(t.dtype) == "torch.uint32":
+        if t.shape[-1] < words:
+            raise ValueError(f"packed doc_filter has {t.shape[-1]} words per row, ceil({n} / 32) = {words} needed")
+        w = t.view(torch.int32) if t.dtype != torch.int32 else t
+        w = w.to(device)
+    else:
+        raise TypeError(f"doc_filter dtype {t.dtype}: torch.bool or packed uint32 words expected")
+    w = w.contiguous()
+    return w, (0 if w.dim() == 1 else w.shape[1])
+
+
 class SplitRows:
     """Embedding rows already in an HRAG_F32_SPLIT engine's layout (fp16 [rows, 3 * dim] on the device): what
     gather_embeddings returns on such an engine, accepted by the constructor (HRAG_F32_SPLIT_ROWS)."""
@@ -450,10 +490,12 @@ class HippoRAGEngine:
     def retrieve(self, q_pass, kept_idx, kept_score, kept_count, *, link_top_k: int = 5,
                  damping: float = 0.5, passage_node_weight: float = 0.05, ppr_iters: int = 20,
                  k: int = 200, ppr_tol: float = 0.0, ppr_max_iters: int = 0,
-                 want_residual: bool = True) -> RetrieveOutput:
+                 want_residual: bool = True, doc_filter=None) -> RetrieveOutput:
         """Phase B: seeds + passage prior + PPR + ranking (DPR ranking where kept_count == 0).
         ppr_tol / ppr_max_iters: the convergence contract of include/hrag.h (0 = exactly ppr_iters sweeps);
-        the output carries the per-query residual and the sweeps that ran."""
+        the output carries the per-query residual and the sweeps that ran.
+        doc_filter: only these passages may be ranked (doc_filter_words; hrag_retrieve_filtered): each row is the first
+        min(k, allowed) allowed entries of the unfiltered ranking, then -1 / 0.  Scoring is unchanged."""
         torch = _torch()
         q = self._q(q_pass)
         b = q.shape[0]
@@ -468,17 +510,20 @@ class HippoRAGEngine:
         flags = self._empty((b,), torch.int32)
         resid = self._empty((b,), torch.float32) if want_residual or ppr_tol > 0 else None
         used = self._empty((b,), torch.int32) if resid is not None else None
-        check(self._lib.hrag_retrieve(self._handle, q.data_ptr(), b, kept_idx.data_ptr(),
-                                      kept_score.data_ptr(), kept_count.data_ptr(), kf, link_top_k,
-                                      damping, passage_node_weight, ppr_iters, max(ppr_max_iters, ppr_iters),
-                                      ppr_tol, k, idx.data_ptr(), sc.data_ptr(), flags.data_ptr(),
-                                      resid.data_ptr() if resid is not None else None,
-                                      used.data_ptr() if used is not None else None, _stream()))
+        args = (self._handle, q.data_ptr(), b, kept_idx.data_ptr(), kept_score.data_ptr(), kept_count.data_ptr(), kf,
+                link_top_k, damping, passage_node_weight, ppr_iters, max(ppr_max_iters, ppr_iters), ppr_tol, k,
+                idx.data_ptr(), sc.data_ptr(), flags.data_ptr(), resid.data_ptr() if resid is not None else None,
+                used.data_ptr() if used is not None else None, _stream())
+        if doc_filter is None:
+            check(self._lib.hrag_retrieve(*args))
+        else:
+            fw, fld = doc_filter_words(doc_filter, self.n_passages, b, self.device)
+            check(self._lib.hrag_retrieve_filtered(*args, fw.data_ptr(), fld))
         return RetrieveOutput(idx, sc, flags, resid, used)
 
     def retrieve_scored(self, pass_scores, kept_idx, kept_score, kept_count, *, link_top_k: int = 5,
                         damping: float = 0.5, passage_node_weight: float = 0.05, ppr_iters: int = 20, k: int = 200,
-                        ppr_tol: float = 0.0, ppr_max_iters: int = 0) -> RetrieveOutput:
+                        ppr_tol: float = 0.0, ppr_max_iters: int = 0, doc_filter=None) -> RetrieveOutput:
         """retrieve() with the raw passage scores fp32 [B, >= Np] supplied by the caller (hrag_retrieve_scored)."""
         torch = _torch()
         sc_in = pass_scores.to(self.device, torch.float32)
@@ -491,11 +536,15 @@ class HippoRAGEngine:
         kf = kept_idx.shape[1]
         idx, sc = self._empty((b, k), torch.int32), self._empty((b, k), torch.float32)
         flags, resid, used = self._empty((b,), torch.int32), self._empty((b,), torch.float32), self._empty((b,), torch.int32)
-        check(self._lib.hrag_retrieve_scored(self._handle, sc_in.data_ptr(), sc_in.stride(0), b, kept_idx.data_ptr(),
-                                             kept_score.data_ptr(), kept_count.data_ptr(), kf, link_top_k, damping,
-                                             passage_node_weight, ppr_iters, max(ppr_max_iters, ppr_iters), ppr_tol, k,
-                                             idx.data_ptr(), sc.data_ptr(), flags.data_ptr(), resid.data_ptr(),
-                                             used.data_ptr(), _stream()))
+        args = (self._handle, sc_in.data_ptr(), sc_in.stride(0), b, kept_idx.data_ptr(), kept_score.data_ptr(),
+                kept_count.data_ptr(), kf, link_top_k, damping, passage_node_weight, ppr_iters,
+                max(ppr_max_iters, ppr_iters), ppr_tol, k, idx.data_ptr(), sc.data_ptr(), flags.data_ptr(), resid.data_ptr(),
+                used.data_ptr(), _stream())
+        if doc_filter is None:
+            check(self._lib.hrag_retrieve_scored(*args))
+        else:
+            fw, fld = doc_filter_words(doc_filter, self.n_passages, b, self.device)
+            check(self._lib.hrag_retrieve_scored_filtered(*args, fw.data_ptr(), fld))
         return RetrieveOutput(idx, sc, flags, resid, used)
 
     def retrieve_converged(self, q_pass, kept_idx, kept_score, kept_count, *, damping: float = 0.5,
@@ -521,9 +570,14 @@ class HippoRAGEngine:
         the flags -- not for whatever was enqueued behind them -- and does the host half of the contract."""
         q = self._q(q_pass)
         kept_idx, kept_score, kept_count = (t.to(self.device) for t in (kept_idx, kept_score, kept_count))
+        doc_filter = kw.pop("doc_filter", None)
+        fw, fld = (None, 0) if doc_filter is None else doc_filter_words(doc_filter, self.n_passages, q.shape[0],
+                                                                        self.device)
 
         def run(rows=None, iters=ppr_iters, max_iters=ppr_max_iters):
             sel = slice(None) if rows is None else rows
+            if fw is not None:    # the repeats of finish() rerun rows of the batch: each keeps its own filter row
+                kw["doc_filter"] = fw if fld == 0 else fw[sel]
             o = self.retrieve(q[sel], kept_idx[sel], kept_score[sel], kept_count[sel], damping=damping,
                               ppr_iters=iters, ppr_tol=ppr_tol, ppr_max_iters=max(max_iters, iters), **kw)
             if want_all_scores:     # every passage's score (callers that want more than max_topk documents)
@@ -541,14 +595,19 @@ class HippoRAGEngine:
         check(self._lib.hrag_last_doc_scores(self._handle, batch, out.data_ptr(), self.passage_rows, _stream()))
         return out
 
-    def dense_retrieve(self, q_pass, k: int = 200):
+    def dense_retrieve(self, q_pass, k: int = 200, doc_filter=None):
         torch = _torch()
         q = self._q(q_pass)
         b = q.shape[0]
         idx = self._empty((b, k), torch.int32)
         sc = self._empty((b, k), torch.float32)
-        check(self._lib.hrag_dense_retrieve(self._handle, q.data_ptr(), b, k, idx.data_ptr(),
-                                            sc.data_ptr(), _stream()))
+        if doc_filter is None:
+            check(self._lib.hrag_dense_retrieve(self._handle, q.data_ptr(), b, k, idx.data_ptr(),
+                                                sc.data_ptr(), _stream()))
+        else:
+            fw, fld = doc_filter_words(doc_filter, self.n_passages, b, self.device)
+            check(self._lib.hrag_dense_retrieve_filtered(self._handle, q.data_ptr(), b, k, idx.data_ptr(), sc.data_ptr(),
+                                                         _stream(), fw.data_ptr(), fld))
         return idx, sc
 
     # ------------------------------------------------------------------ seams
@@ -737,17 +796,21 @@ class HippoRAGEngine:
         check(self._lib.hrag_shard_ppr_gate(self._handle, step, C.byref(o), _stream()))
         return bool(o.value)
 
-    def shard_finish(self, mn, mx, flags, k: int, want_residual: bool = False):
+    def shard_finish(self, mn, mx, flags, k: int, want_residual: bool = False, doc_filter=None):
+        """doc_filter: the GLOBAL filter ([B, n_passages of the whole index] or packed); the shard reads its slice."""
         torch = _torch()
         b = mn.shape[0]
         idx = self._empty((b, k), torch.int32)
         val = self._empty((b, k), torch.float32)
         resid = self._empty((b,), torch.float32) if want_residual else None
         used = self._empty((b,), torch.int32) if want_residual else None
-        check(self._lib.hrag_shard_finish(self._handle, mn.data_ptr(), mx.data_ptr(), flags.data_ptr(), b, k,
-                                          idx.data_ptr(), val.data_ptr(),
-                                          resid.data_ptr() if want_residual else None,
-                                          used.data_ptr() if want_residual else None, _stream()))
+        args = (self._handle, mn.data_ptr(), mx.data_ptr(), flags.data_ptr(), b, k, idx.data_ptr(), val.data_ptr(),
+                resid.data_ptr() if want_residual else None, used.data_ptr() if want_residual else None, _stream())
+        if doc_filter is None:
+            check(self._lib.hrag_shard_finish(*args))
+        else:
+            fw, fld = doc_filter_words(doc_filter, self.n_passages, b, self.device)
+            check(self._lib.hrag_shard_finish_filtered(*args, fw.data_ptr(), fld))
         return (idx, val, resid, used) if want_residual else (idx, val)
 
 
@@ -977,5 +1040,5 @@ class ShardStages(EngineStages):
     def shard_ppr_gate_open(self, step):
         return self.e.shard_ppr_gate_open(step)
 
-    def shard_finish(self, mn, mx, flags, k, want_residual=False):
-        return self.e.shard_finish(mn, mx, flags, k, want_residual)
+    def shard_finish(self, mn, mx, flags, k, want_residual=False, **kw):
+        return self.e.shard_finish(mn, mx, flags, k, want_residual, **kw)

@@ -214,6 +214,28 @@ class BatchRows(list):
     doc_score = None
 
 
+def unpack_mask(words, n: int) -> np.ndarray:
+    """The doc filter's uint32 words [..., W] (engine.pack_mask) -> bool [..., n]."""
+    w = np.ascontiguousarray(words, dtype="<u4")
+    return np.unpackbits(w.view(np.uint8), axis=-1, bitorder="little")[..., :n].astype(bool)
+
+
+def rank_allowed(full, allowed, want: int):
+    """The host form of the filtered ranking: per row, the first `want` entries of np.argsort(x, kind="stable")[::-1]
+    that `allowed` (bool [n] or [B, n]) admits, -1 / 0 beyond them -> (ids int32 [B, want], scores fp32 [B, want])."""
+    full = np.asarray(full, np.float32)
+    b = full.shape[0]
+    allowed = np.broadcast_to(np.asarray(allowed, bool), full.shape)
+    idx = np.full((b, want), -1, np.int32)
+    sc = np.zeros((b, want), np.float32)
+    for i in range(b):
+        order = np.argsort(full[i], kind="stable")[::-1]
+        order = order[allowed[i][order]][:want]
+        idx[i, :len(order)] = order
+        sc[i, :len(order)] = full[i][order]
+    return idx, sc
+
+
 def batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Sequence, rerank_filter: Callable, **kw):
     """The body of retrieve() (HippoRAG.py:459-480) for all queries at once: one (doc ids, doc scores, kept facts) per
     query.  See iter_batched_retrieve, which this flattens."""
@@ -226,7 +248,7 @@ def batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Sequenc
 def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Sequence, rerank_filter: Callable, *,
                           linking_top_k: int, damping: float, passage_node_weight: float, ppr_iters: int,
                           num_to_retrieve: int, n_passages: int, timers=None, ppr_tol: float = 0.0,
-                          ppr_max_iters: int = 0, ppr_base_iters_narrow: Optional[int] = None):
+                          ppr_max_iters: int = 0, ppr_base_iters_narrow: Optional[int] = None, doc_filter=None):
     """The body of retrieve() (HippoRAG.py:459-480), shared by the mirror class below and by
     reference_adapter.attach(): phase A on the device, the recognition-memory filter on the host (rerank_facts
     :1659-1707), phase B on the device, in batches of eng.max_batch queries.  Yields (offset of the batch, [(doc ids,
@@ -244,7 +266,9 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
     within its sweep budget are repeated -- those queries only -- on the wider state with the sweeps their
     residual asks for, so a slowly mixing graph costs time, never accuracy.
     ppr_base_iters_narrow (RetrievalConfig.ppr_base_iters_narrow): the sweeps that ALWAYS run for a batch of at most 64
-    queries under a tolerance -- the measure adds stages where the graph needs them."""
+    queries under a tolerance -- the measure adds stages where the graph needs them.
+    doc_filter: packed uint32 words (engine.pack_mask) [W] for every query or [len(queries), W]: only those passages
+    are ranked (a post-filter: the scores do not change); passed to the engine only when given."""
     import torch
     from .engine import host_copy_async, host_wait
     k_f = int(linking_top_k)
@@ -313,6 +337,9 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
             base = max(11, min(int(ppr_base_iters_narrow), ppr_iters))     # narrow batch under the contract: latency mode
         kw = dict(link_top_k=k_f, damping=damping, passage_node_weight=passage_node_weight, ppr_iters=base,
                   k=k_docs, ppr_tol=ppr_tol, ppr_max_iters=ppr_max_iters, **({"want_all_scores": True} if beyond else {}))
+        if doc_filter is not None:
+            rows_w = doc_filter if doc_filter.ndim == 1 else doc_filter[bt.lo: bt.lo + b]
+            kw["doc_filter"] = torch.from_numpy(np.ascontiguousarray(rows_w).view(np.int32))
         if two_halves:
             bt.pending = eng.retrieve_converged_start(*args, **kw)
             o = bt.pending.out
@@ -337,8 +364,12 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
             flags = out.flags.cpu().numpy()
         if beyond:
             full = out.all_scores.cpu().numpy()
-            d_idx = np.stack([np.argsort(r, kind="stable")[::-1][:want] for r in full]).astype(np.int32)
-            d_sc = np.take_along_axis(full, d_idx.astype(np.int64), axis=1)
+            if doc_filter is not None:
+                rows_w = doc_filter if doc_filter.ndim == 1 else doc_filter[bt.lo: bt.lo + len(bt.qs)]
+                d_idx, d_sc = rank_allowed(full, unpack_mask(rows_w, full.shape[1]), want)
+            else:
+                d_idx = np.stack([np.argsort(r, kind="stable")[::-1][:want] for r in full]).astype(np.int32)
+                d_sc = np.take_along_axis(full, d_idx.astype(np.int64), axis=1)
         tick("ppr_time", t0)
         rows = BatchRows()
         rows.doc_idx, rows.doc_score = d_idx, d_sc
@@ -526,6 +557,7 @@ class HippoRAG:
     def _refresh_arrays(self):
         """The engine-facing arrays from the current graph / stores (what prepare_retrieval_objects reads,
         HippoRAG.py:1287-1389)."""
+        self._filter_cache = {}          # the passage list changed: every cached doc filter bitset is stale
         g = self._graph
         self.node_name_to_vertex_idx = dict(g.index)
         csr = g.to_csr()
@@ -757,17 +789,81 @@ class HippoRAG:
         cfg = self.global_config
         return int(cfg.ppr_iters) if cfg.ppr_iters else sweeps_for_damping(cfg.damping if damping is None else damping)
 
+    # ------------------------------------------------------------------ doc filter
+    def _value_bits(self, key, value) -> np.ndarray:
+        """Packed bitset of the passages whose metadata (source_id included) has `key` == `value`; built the first time
+        it is asked for and cached until the passage list changes (_refresh_arrays)."""
+        cache = self.__dict__.setdefault("_filter_cache", {})
+        try:
+            ck = (key, value)
+            hit = cache.get(ck)
+        except TypeError:                    # an unhashable value: matched, not cached
+            ck, hit = None, None
+        if hit is None:
+            from .engine import pack_mask
+            meta = self.chunk_metadata
+            hit = pack_mask(np.fromiter((key in m and m[key] == value
+                                         for m in (meta.get(k, {}) for k in self.passage_node_keys)),
+                                        bool, len(self.passage_node_keys)))
+            if ck is not None:
+                cache[ck] = hit
+        return hit
+
+    def _filter_words(self, f) -> np.ndarray:
+        """One query's filter (a metadata dict or a bool array in passage_node_keys order) -> packed uint32 [W]."""
+        from .engine import pack_mask
+        n = len(self.passage_node_keys)
+        if isinstance(f, dict):
+            words = np.full((n + 31) // 32, 0xFFFFFFFF, np.uint32)
+            for key, values in f.items():               # keys: AND; the values of one key: OR
+                alts = values if isinstance(values, (list, tuple, set, frozenset)) else [values]
+                any_of = np.zeros_like(words)
+                for v in alts:
+                    any_of |= self._value_bits(key, v)
+                words &= any_of
+            return words
+        if isinstance(f, np.ndarray):
+            if f.dtype != bool:
+                raise TypeError(f"doc_filter array dtype {f.dtype}: a bool array over the passages is expected")
+            if f.shape != (n,):
+                raise ValueError(f"doc_filter array of shape {f.shape}: ({n},) expected (one entry per passage)")
+            return pack_mask(f)
+        raise TypeError(f"doc_filter of type {type(f).__name__}: a metadata dict, a bool numpy array, or a list of those")
+
+    def _doc_filter_words(self, doc_filter, n_queries: int) -> Optional[np.ndarray]:
+        """doc_filter as the engine takes it: None, packed [W] (one filter for the batch, sent as one broadcast row) or
+        [n_queries, W] (a list: one filter per query)."""
+        if doc_filter is None:
+            return None
+        if isinstance(doc_filter, list):
+            if len(doc_filter) != n_queries:
+                raise ValueError(f"doc_filter list of {len(doc_filter)} entries for {n_queries} queries")
+            w = (len(self.passage_node_keys) + 31) // 32
+            return (np.stack([self._filter_words(f) for f in doc_filter]) if doc_filter
+                    else np.zeros((0, w), np.uint32))
+        return self._filter_words(doc_filter)
+
+    @staticmethod
+    def _filter_rows(doc_filter, rows):
+        """The doc filter of a subset of the queries (retrieve_ircot's later steps)."""
+        return [doc_filter[i] for i in rows] if isinstance(doc_filter, list) else doc_filter
+
     # ------------------------------------------------------------------ retrieve :413-499
     def retrieve(self, queries: List[str], num_to_retrieve: Optional[int] = None,
-                 gold_docs: Optional[List[List[str]]] = None):
+                 gold_docs: Optional[List[List[str]]] = None, doc_filter=None):
+        """doc_filter: limit the ranked documents to a subset of the corpus (a post-filter: scores do not change) --
+        a metadata dict {key: value} or {key: [values]} (values of a key: any of them; keys: all of them; matched
+        against the chunk metadata, source_id included), a bool numpy array over passage_node_keys, or a list with one
+        of those per query.  Each query gets the first num_to_retrieve allowed documents of its unfiltered ranking."""
         t_start = time.time()
         cfg = self.global_config
         if num_to_retrieve is None:
             num_to_retrieve = cfg.retrieval_top_k
         self._ensure_ready()
+        words = self._doc_filter_words(doc_filter, len(queries))
         self.get_query_embeddings(queries)
         results: List[QuerySolution] = []
-        self._retrieve_into(results, queries, num_to_retrieve)
+        self._retrieve_into(results, queries, num_to_retrieve, words)
         self.all_retrieval_time += time.time() - t_start
         logger.info("Total Retrieval Time %.2fs", self.all_retrieval_time)
         logger.info("Total Recognition Memory Time %.2fs", self.rerank_time)
@@ -776,8 +872,9 @@ class HippoRAG:
             return results, self._recall(gold_docs, [r.docs for r in results])
         return results
 
-    def _retrieve_into(self, results, queries, num_to_retrieve):
+    def _retrieve_into(self, results, queries, num_to_retrieve, doc_filter=None):
         cfg = self.global_config
+        extra = {} if doc_filter is None else {"doc_filter": doc_filter}
         # batch by batch: the lists of document strings of one batch are built while the device works on the next
         for lo, rows in iter_batched_retrieve(self.engine, queries, self._q_tensor, self.facts if self.fact_node_keys else [],
                                               self.rerank_filter, linking_top_k=cfg.linking_top_k, damping=cfg.damping,
@@ -785,13 +882,14 @@ class HippoRAG:
                                               ppr_tol=cfg.ppr_tol, ppr_max_iters=cfg.ppr_max_iters,
                                               ppr_base_iters_narrow=cfg.ppr_base_iters_narrow,
                                               num_to_retrieve=num_to_retrieve, n_passages=len(self.passage_node_keys),
-                                              timers=self):
+                                              timers=self, **extra):
             with gc_paused():       # around the materialisation only: the filter (an LLM call in production) runs outside
                 results.extend(self._build_query_solutions(queries[lo: lo + len(rows)], rows, num_to_retrieve))
 
     # ------------------------------------------------------------------ retrieve_ircot :509-558
     def retrieve_ircot(self, queries: List[str], max_qa_steps: int, num_to_retrieve: Optional[int] = None,
-                       gold_docs: Optional[List[List[str]]] = None, reason_fn: Optional[Callable] = None):
+                       gold_docs: Optional[List[List[str]]] = None, reason_fn: Optional[Callable] = None,
+                       doc_filter=None):
         """Iterative retrieval: alternate retrieval and one reasoning step per query, merging the document
         scores by max (:526-543).  reason_fn(query, ranked_docs, thoughts) -> str stands for
         utils/qa_utils.reason_step (the IRCoT prompt + reader LLM are outside this package).  The reference
@@ -804,7 +902,7 @@ class HippoRAG:
             raise ValueError("retrieve_ircot with max_qa_steps > 1 needs a reason_fn (the reader LLM is outside this package)")
         if num_to_retrieve is None:
             num_to_retrieve = self.global_config.retrieval_top_k
-        first = self.retrieve(list(queries), num_to_retrieve=num_to_retrieve)
+        first = self.retrieve(list(queries), num_to_retrieve=num_to_retrieve, doc_filter=doc_filter)
         merged = [dict(zip(r.docs, r.doc_scores.tolist())) for r in first]
         meta = [dict(zip(r.docs, r.doc_metadata or [])) for r in first]
         thoughts: List[List[str]] = [[] for _ in queries]
@@ -823,7 +921,8 @@ class HippoRAG:
                 step_i.append(i)
             if not step_q:
                 break
-            for i, r in zip(step_i, self.retrieve(step_q, num_to_retrieve=num_to_retrieve)):
+            for i, r in zip(step_i, self.retrieve(step_q, num_to_retrieve=num_to_retrieve,
+                                                  doc_filter=self._filter_rows(doc_filter, step_i))):
                 for doc, score in zip(r.docs, r.doc_scores.tolist()):
                     merged[i][doc] = max(merged[i].get(doc, float("-inf")), score)
                 meta[i].update(dict(zip(r.docs, r.doc_metadata or [])))
@@ -883,11 +982,13 @@ class HippoRAG:
 
     # ------------------------------------------------------------------ retrieve_dpr :665-732
     def retrieve_dpr(self, queries: List[str], num_to_retrieve: Optional[int] = None,
-                     gold_docs: Optional[List[List[str]]] = None):
+                     gold_docs: Optional[List[List[str]]] = None, doc_filter=None):
         cfg = self.global_config
         if num_to_retrieve is None:
             num_to_retrieve = cfg.retrieval_top_k
         self._ensure_ready()
+        words = self._doc_filter_words(doc_filter, len(queries))
+        import torch
         self.get_query_embeddings(queries)
         eng = self.engine
         want = max(1, min(num_to_retrieve, len(self.passage_node_keys)))
@@ -898,11 +999,16 @@ class HippoRAG:
         from .engine import host_copy_async, host_wait
         results = []
 
+        def rows_of(lo, b):                 # the packed filter rows of queries [lo, lo + b)
+            return words if words.ndim == 1 else words[lo: lo + b]
+
         def enqueue(lo):
             qs = queries[lo: lo + eng.max_batch]
             if beyond:
                 return qs, host_copy_async(eng.sim_scores("passages", self._q_tensor(qs, "passage"))), None
-            idx, sc = eng.dense_retrieve(self._q_tensor(qs, "passage"), k=k_docs)
+            extra = {} if words is None else {
+                "doc_filter": torch.from_numpy(np.ascontiguousarray(rows_of(lo, len(qs))).view(np.int32))}
+            idx, sc = eng.dense_retrieve(self._q_tensor(qs, "passage"), k=k_docs, **extra)
             return qs, host_copy_async(idx), host_copy_async(sc)
 
         # one batch ahead of the host, like retrieve(): batch i's lists are built while the device scores batch i + 1
@@ -914,8 +1020,11 @@ class HippoRAG:
             if beyond:
                 raw = host_wait(idx_h)[:, :len(self.passage_node_keys)]
                 full = np.stack([min_max_normalize(r) for r in raw]).astype(np.float32)
-                idx = np.stack([np.argsort(r, kind="stable")[::-1][:want] for r in full]).astype(np.int32)
-                sc = np.take_along_axis(full, idx.astype(np.int64), axis=1)
+                if words is not None:
+                    idx, sc = rank_allowed(full, unpack_mask(rows_of(starts[n], len(qs)), full.shape[1]), want)
+                else:
+                    idx = np.stack([np.argsort(r, kind="stable")[::-1][:want] for r in full]).astype(np.int32)
+                    sc = np.take_along_axis(full, idx.astype(np.int64), axis=1)
             else:
                 idx, sc = host_wait(idx_h).copy(), host_wait(sc_h).copy()
             with gc_paused():
@@ -929,12 +1038,12 @@ class HippoRAG:
 
     # ------------------------------------------------------------------ rag_qa :591-663
     def rag_qa(self, queries, gold_docs: Optional[List[List[str]]] = None,
-               gold_answers: Optional[List[List[str]]] = None):
+               gold_answers: Optional[List[List[str]]] = None, doc_filter=None):
         if self.qa_fn is None:
             raise NotImplementedError("rag_qa needs a qa_fn (the reader LLM is outside this package)")
         retrieval_metrics = None
         if not isinstance(queries[0], QuerySolution):
-            out = self.retrieve(queries=queries, gold_docs=gold_docs)
+            out = self.retrieve(queries=queries, gold_docs=gold_docs, doc_filter=doc_filter)
             queries, retrieval_metrics = out if gold_docs is not None else (out, None)
         solutions, messages, metadata = self.qa_fn(queries)
         if gold_answers is not None:

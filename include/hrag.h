@@ -57,7 +57,10 @@ extern "C" {
  *        carries a margin of 16 instead of 4: 16 sweeps stand for 20 at damping 0.5 (14 before);
  *   0.8  hrag_sim_topk_min_score (the thresholded fused top-k of the index-time KNN: prefix first pass + cut);
  *        later in 0.8 (no struct layout changes; detect by the symbol): hrag_topk_rows_ws +
- *        hrag_topk_rows_workspace_bytes (any k), hrag_opts.max_topk above 2048. */
+ *        hrag_topk_rows_workspace_bytes (any k), hrag_opts.max_topk above 2048;
+ *        later in 0.8 (detect by the symbol): the doc filter -- hrag_topk_rows_masked, hrag_retrieve_filtered,
+ *        hrag_retrieve_scored_filtered, hrag_dense_retrieve_filtered, hrag_shard_finish_filtered,
+ *        hrag_shard_retrieve_filtered. */
 #define HRAG_VERSION_MAJOR 0
 #define HRAG_VERSION_MINOR 8
 
@@ -427,6 +430,37 @@ hrag_status hrag_dense_retrieve(hrag_engine *e, const uint16_t *q_pass_dev, int3
                                 int32_t k, int32_t *doc_idx_out_dev, float *doc_score_out_dev,
                                 hrag_stream stream);
 
+/* ---- doc filter: exact top-k over a caller-chosen set of passages ----
+ * A POST-filter: it decides which passages may appear in the ranked list and changes nothing else (phase A, the seeds,
+ * the passage prior, the PPR, the min-max of the dense scores over ALL passages).  Per query the result is the first
+ * min(k, |allowed|) entries of the unfiltered full ranking that are allowed, ids and scores bit-identical to those
+ * entries; the slots beyond hold -1 / 0.  Queries on the DPR fallback (flags bit 0) follow the same rule on their
+ * dense ranking.  An empty allowed set gives an all -1 row.  filter_dev == NULL is the unfiltered call, bit for bit.
+ *
+ * Mask format: a bitset of uint32 words; bit (j & 31) of word (j >> 5) is set when passage position j (the index
+ * doc_idx_out uses) is allowed -- np.packbits(mask, bitorder="little") with the row padded to 4 bytes, read as
+ * little-endian uint32.  filter_ld_words = 0: one row for the whole batch; otherwise >= ceil(n_passages / 32) words
+ * per query row (HRAG_EINVAL below that).  Bits at or above n_passages are ignored.  A row shard reads the same GLOBAL
+ * mask at bit offset p_offset (need not be a multiple of 32).  The filter costs one bit read per ranked score. */
+hrag_status hrag_retrieve_filtered(hrag_engine *e, const uint16_t *q_pass_dev, int32_t batch,
+                                   const int32_t *kept_idx_dev, const float *kept_score_dev,
+                                   const int32_t *kept_count_dev, int32_t kf, int32_t link_top_k,
+                                   float damping, float passage_node_weight, int32_t ppr_iters,
+                                   int32_t ppr_max_iters, float ppr_tol, int32_t k,
+                                   int32_t *doc_idx_out_dev, float *doc_score_out_dev,
+                                   int32_t *flags_out_dev, float *residual_out_dev, int32_t *iters_out_dev,
+                                   hrag_stream stream, const uint32_t *filter_dev, int64_t filter_ld_words);
+hrag_status hrag_retrieve_scored_filtered(hrag_engine *e, const float *pass_scores_dev, int64_t pass_ld, int32_t batch,
+                                          const int32_t *kept_idx_dev, const float *kept_score_dev,
+                                          const int32_t *kept_count_dev, int32_t kf, int32_t link_top_k, float damping,
+                                          float passage_node_weight, int32_t ppr_iters, int32_t ppr_max_iters,
+                                          float ppr_tol, int32_t k, int32_t *doc_idx_out_dev, float *doc_score_out_dev,
+                                          int32_t *flags_out_dev, float *residual_out_dev, int32_t *iters_out_dev,
+                                          hrag_stream stream, const uint32_t *filter_dev, int64_t filter_ld_words);
+hrag_status hrag_dense_retrieve_filtered(hrag_engine *e, const uint16_t *q_pass_dev, int32_t batch, int32_t k,
+                                         int32_t *doc_idx_out_dev, float *doc_score_out_dev, hrag_stream stream,
+                                         const uint32_t *filter_dev, int64_t filter_ld_words);
+
 /* ---- lower-level seams (used by the per-method adapters and by the parity tests) ---- */
 
 /* np.dot(embeddings, q.T) (HippoRAG.py:1459 / :1496): raw cosine scores.
@@ -462,6 +496,17 @@ hrag_status hrag_topk_rows_ws(const float *scores_dev, int32_t batch, int64_t n,
                               int32_t idx_offset, int32_t normalize, int32_t *idx_out_dev, float *val_out_dev,
                               float *min_out_dev, float *max_out_dev, void *workspace_dev, size_t workspace_bytes,
                               hrag_stream stream);
+/* hrag_topk_rows_ws over the elements a mask allows (the doc filter's format above; mask_dev must not be NULL): row r
+ * may select element i when bit (mask_bit_offset + i) of the words at mask_dev + r * mask_ld_words is set
+ * (mask_ld_words 0: one row for the batch, else >= ceil((mask_bit_offset + n) / 32)).  Per row: the first min(k,
+ * allowed) entries of hrag_topk_rows_ws's full ranking that are allowed, bit for bit, then -1 / 0.  min_out / max_out
+ * and normalize still use EVERY element of the row.  Any k, the workspace rule of hrag_topk_rows_ws; at k <= 2048 a
+ * workspace of at least 2 MiB is optional and lets a batch below 64 split long rows over several workgroups (the
+ * engine's ranking does; same result). */
+hrag_status hrag_topk_rows_masked(const float *scores_dev, int32_t batch, int64_t n, int64_t ld, int32_t k,
+                                  int32_t idx_offset, int32_t normalize, const uint32_t *mask_dev, int64_t mask_ld_words,
+                                  int64_t mask_bit_offset, int32_t *idx_out_dev, float *val_out_dev, float *min_out_dev,
+                                  float *max_out_dev, void *workspace_dev, size_t workspace_bytes, hrag_stream stream);
 
 /* ---- index-time entity KNN (retrieve_knn, utils/embed_utils.py:6-94; engine-less) ----
  * hrag_normalize_split_bf16: F.normalize (embed_utils.py:25,28) when normalize != 0, then the split
@@ -692,6 +737,12 @@ hrag_status hrag_shard_ppr_gate(hrag_engine *e, int32_t step, int32_t *open_out,
 hrag_status hrag_shard_finish(hrag_engine *e, const float *min_dev, const float *max_dev, int32_t *flags_dev,
                               int32_t batch, int32_t k, int32_t *idx_out_dev, float *score_out_dev,
                               float *residual_out_dev, int32_t *iters_out_dev, hrag_stream stream);
+/* hrag_shard_finish with the doc filter (the GLOBAL mask of hrag_retrieve_filtered; the shard reads it at p_offset).
+ * A shard whose slice holds no allowed passage returns all -1 rows, which the merge puts after every real entry. */
+hrag_status hrag_shard_finish_filtered(hrag_engine *e, const float *min_dev, const float *max_dev, int32_t *flags_dev,
+                                       int32_t batch, int32_t k, int32_t *idx_out_dev, float *score_out_dev,
+                                       float *residual_out_dev, int32_t *iters_out_dev, hrag_stream stream,
+                                       const uint32_t *filter_dev, int64_t filter_ld_words);
 
 /* ------------------------------------------------------------------------------------------
  * ONE CALL PER PHASE on a row shard (round 6).  The steps above leave the order of the local steps, the exchanges and the
@@ -753,6 +804,17 @@ hrag_status hrag_shard_retrieve(hrag_engine *e, const hrag_comm *comm, const uin
                                 int64_t workspace_bytes, int32_t *doc_idx_out_dev, float *doc_score_out_dev,
                                 int32_t *flags_out_dev, float *residual_out_dev, int32_t *iters_out_dev,
                                 hrag_stream stream);
+/* hrag_shard_retrieve with the doc filter (every shard passes the same global mask) = hrag_retrieve_filtered of the
+ * unsharded engine. */
+hrag_status hrag_shard_retrieve_filtered(hrag_engine *e, const hrag_comm *comm, const uint16_t *q_pass_dev, int32_t batch,
+                                         const int32_t *kept_idx_dev, const float *kept_score_dev,
+                                         const int32_t *kept_count_dev, int32_t kf, int32_t link_top_k, float damping,
+                                         float passage_node_weight, int32_t ppr_iters, int32_t ppr_max_iters,
+                                         float ppr_tol, int32_t k, int32_t n_groups, void *state0_dev, void *state1_dev,
+                                         void *state2_dev, void *workspace_dev, int64_t workspace_bytes,
+                                         int32_t *doc_idx_out_dev, float *doc_score_out_dev, int32_t *flags_out_dev,
+                                         float *residual_out_dev, int32_t *iters_out_dev, hrag_stream stream,
+                                         const uint32_t *filter_dev, int64_t filter_ld_words);
 
 /* Index update with the embeddings staying on the device (incremental index() / delete(), HippoRAG.py:262-411:
  * the reference re-reads everything from its stores in prepare_retrieval_objects): compose the embedding
