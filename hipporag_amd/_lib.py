@@ -121,6 +121,14 @@ SIGNATURES = {
     "hrag_retrieve_scored_filtered": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _I32, _I32, _F32, _F32, _I32, _I32, _F32,
                                                 _I32, _P, _P, _P, _P, _P, _P, _P, _I64]),
     "hrag_dense_retrieve_filtered": (C.c_int, [_P, _P, _I32, _I32, _P, _P, _P, _P, _I64]),
+    "hrag_engine_set_fact_sources": (C.c_int, [_P, _P, _P, _I64, _I64]),
+    "hrag_fact_mask_from_docs": (C.c_int, [_P, _I64, _I64, _I64, _I32, _P, _P, _I64, _P, _P]),
+    "hrag_score_facts_scoped": (C.c_int, [_P, _P, _I32, _I32, _P, _P, _P, _P, _I64]),
+    "hrag_retrieve_scoped": (C.c_int, [_P, _P, _I32, _P, _P, _P, _I32, _I32, _F32, _F32, _I32, _I32, _F32, _I32, _P, _P,
+                                       _P, _P, _P, _P, _P, _I64]),
+    "hrag_retrieve_scored_scoped": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _I32, _I32, _F32, _F32, _I32, _I32, _F32,
+                                              _I32, _P, _P, _P, _P, _P, _P, _P, _I64]),
+    "hrag_dense_retrieve_scoped": (C.c_int, [_P, _P, _I32, _I32, _P, _P, _P, _P, _I64]),
     "hrag_ppr_sweeps": (C.c_int, [_P, _I32, _I32, _F32, _I32, _P]),
     "hrag_ppr_layout": (C.c_int, [_P, _I32, C.POINTER(_I32), C.POINTER(_I32)]),
     "hrag_row_minmax": (C.c_int, [_P, _I32, _I64, _I64, _P, _P, _P]),

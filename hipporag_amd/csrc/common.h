@@ -461,10 +461,13 @@ constexpr size_t kTopkWsBytes = (size_t)64 * 4096 * 8 + (size_t)64 * 64 * 8;
 // doc filter of the ranking (include/hrag.h, hrag_topk_rows_masked): element i of row r may be selected when bit
 // (bit_offset + i) of the uint32 words at words + r * ld_words is set (ld_words 0: one row for the whole batch).  A
 // masked-out element gets key 0 (an empty slot); the row min / max still cover every element
+// minmax_allowed (row_topk_kernel only, the scoped fact ranking of hrag_score_facts_scoped): the row min / max cover the
+// allowed elements only
 struct TopkMask {
     const uint32_t *words;
     int64_t ld_words;
     int64_t bit_offset;
+    int32_t minmax_allowed = 0;
 };
 hrag_status launch_row_topk(const float *scores, int32_t batch, int64_t n, int64_t ld, int32_t k,
                             int32_t idx_offset, TopkNorm norm, int32_t *idx_out, float *val_out,
@@ -472,6 +475,11 @@ hrag_status launch_row_topk(const float *scores, int32_t batch, int64_t n, int64
                             size_t ws_bytes = 0, const TopkMask *mask = nullptr);
 hrag_status launch_row_minmax(const float *scores, int32_t batch, int64_t n, int64_t ld,
                               float *mn_out, float *mx_out, hipStream_t s, float *sum_out = nullptr);
+// the passage prior of a scoped call (include/hrag.h, hrag_retrieve_scoped): every row of `scores` is rewritten in place,
+// an allowed element to its min-max normalised value over the row's ALLOWED elements (a zero range gives 1), every other
+// element to 0.  The row min / max of the result are then 0 / 1 (or equal), so the prior kernels' own min-max is exact
+// identity on it
+hrag_status launch_masked_prior(float *scores, int32_t batch, int64_t n, int64_t ld, const TopkMask &mask, hipStream_t s);
 // K4' (topk.hip): the same ranking and output for any k > kTopkMax.  kk = min(k, n) <= kLargeTile keys are selected,
 // sorted and written by one kernel without workspace; larger kk take topk_large_ws_bytes of 8-byte aligned workspace
 // (two key buffers of batch x round_up(kk, kLargeTile) + the row min / max)
@@ -486,6 +494,11 @@ hrag_status launch_row_topk_large(const float *scores, int32_t batch, int64_t n,
 hrag_status launch_split3(const float *x, int64_t rows, int32_t dim, int32_t as_query, uint16_t *out, hipStream_t s,
                           int32_t normalize = 0);
 
+// seeds.hip: the fact bitset of a scoped phase A -- bit f of row r is set when one of fact f's source passages
+// pos[row_ptr[f] .. row_ptr[f + 1]) has its bit set in doc row r (doc_ld_words 0: one doc row for every output row; bits
+// read at doc_bit0 + passage; sources outside [0, n_docs) are ignored).  Output [rows, fact_words = ceil(n_facts / 32)]
+hrag_status launch_fact_mask(const uint32_t *doc, int64_t doc_ld_words, int64_t doc_bit0, int64_t n_docs, int32_t rows,
+                             const int64_t *row_ptr, const int32_t *pos, int64_t n_facts, uint32_t *out, hipStream_t s);
 // seeds.hip
 hrag_status launch_build_seeds(const int32_t *kept_idx, const float *kept_score,
                                const int32_t *kept_count, int32_t kf, int32_t link_top_k,

@@ -40,7 +40,8 @@ static void workspace_ptrs(hrag_engine *e, std::vector<void **> &out) {
                      (void **)&e->d_zmax, (void **)&e->d_mass, (void **)&e->d_prior_part, (void **)&e->d_est_f,
                      (void **)&e->d_ctl, (void **)&e->d_iters_used, (void **)&e->d_resid, (void **)&e->d_mass_tab,
                      (void **)&e->d_est_ws, (void **)&e->d_qsplit, (void **)&e->d_dyn, (void **)&e->d_mmax_ws,
-                     (void **)&e->d_mmax_word, (void **)&e->sell.lcount, (void **)&e->fsell.lcount};
+                     (void **)&e->d_mmax_word, (void **)&e->sell.lcount, (void **)&e->fsell.lcount,
+                     (void **)&e->d_fact_mask};
     out.assign(std::begin(ptrs), std::end(ptrs));
 }
 
@@ -56,7 +57,8 @@ void free_engine(hrag_engine *e) {
         void *ptrs[] = {e->d_row_ptr, e->d_col, e->d_val, e->d_row_order, e->d_seg_row, e->d_seg_begin,
                         e->d_seg_end, e->d_seg_slot, e->d_mrow_row, e->d_mrow_first, e->d_mrow_cnt,
                         e->d_passage_vertex, e->d_row_to_tele, e->d_pemb, e->d_femb, e->d_subj, e->d_obj,
-                        e->d_num_chunks, e->d_deg, e->d_pinvdeg, e->d_row_ptele, e->d_iso, e->d_piso, e->d_colmask_static};
+                        e->d_num_chunks, e->d_deg, e->d_pinvdeg, e->d_row_ptele, e->d_iso, e->d_piso, e->d_colmask_static,
+                        e->d_fsrc_ptr, e->d_fsrc_pos};
         for (void *p : ptrs)
             if (p) (void)hipFree(p);
         free_store(e->sell);
@@ -649,6 +651,7 @@ static hrag_status alloc_workspace(hrag_engine *e) {
         HRAG_TRY(dev_alloc(&e->d_mn_f, B));
         HRAG_TRY(dev_alloc(&e->d_mx_f, B));
     }
+    if (e->d_fsrc_ptr) HRAG_TRY(dev_alloc(&e->d_fact_mask, (int64_t)B * e->fact_words));   // scoped phase A
     HRAG_TRY(dev_alloc(&e->d_mn_p, B));
     HRAG_TRY(dev_alloc(&e->d_mx_p, B));
     HRAG_TRY(dev_alloc(&e->d_seed_vtx, (int64_t)B * kMaxSeeds));
@@ -1180,6 +1183,94 @@ hrag_status hrag_score_facts(hrag_engine *e, const uint16_t *q, int32_t batch, i
     return HRAG_OK;
 }
 
+hrag_status hrag_engine_set_fact_sources(hrag_engine *e, const int64_t *row_ptr, const int32_t *passage_pos,
+                                         int64_t n_facts, int64_t nnz) {
+    HRAG_REQUIRE(e != nullptr, "engine is NULL");
+    HRAG_REQUIRE(!e->borrowed, "fact sources belong to the shared index: set them on the root engine");
+    HRAG_REQUIRE(e->n_workspaces.v.load() == 0,
+                 "engine has %d live workspace(s): set the fact sources before hrag_workspace_create",
+                 e->n_workspaces.v.load());
+    HRAG_REQUIRE(e->has_facts && e->d_subj != nullptr, "engine was created without facts");
+    HRAG_REQUIRE(e->f_rows == e->n_facts && e->p_rows == e->n_passages, "fact sources need an unsharded engine");
+    HRAG_REQUIRE(n_facts == e->n_facts, "n_facts=%lld, the engine has %lld facts", (long long)n_facts,
+                 (long long)e->n_facts);
+    HRAG_REQUIRE(row_ptr != nullptr && nnz >= 0 && (nnz == 0 || passage_pos != nullptr), "NULL argument");
+    HRAG_REQUIRE(row_ptr[0] == 0 && row_ptr[n_facts] == nnz, "row_ptr must run from 0 to nnz=%lld", (long long)nnz);
+    for (int64_t f = 0; f < n_facts; ++f)
+        HRAG_REQUIRE(row_ptr[f + 1] >= row_ptr[f], "row_ptr decreases at fact %lld", (long long)f);
+    for (int64_t j = 0; j < nnz; ++j)
+        HRAG_REQUIRE(passage_pos[j] >= 0 && passage_pos[j] < e->n_passages,
+                     "passage_pos[%lld]=%d outside [0, n_passages=%lld)", (long long)j, passage_pos[j],
+                     (long long)e->n_passages);
+    HRAG_HIP_TRY(hipSetDevice(e->device));
+    HRAG_HIP_TRY(hipDeviceSynchronize());   // a call in flight may still read the table being replaced
+    for (void *p : {(void *)e->d_fsrc_ptr, (void *)e->d_fsrc_pos, (void *)e->d_fact_mask})
+        if (p) (void)hipFree(p);
+    e->d_fsrc_ptr = nullptr; e->d_fsrc_pos = nullptr; e->d_fact_mask = nullptr;
+    e->fact_words = ceil_div(n_facts, 32);
+    e->fsrc_nnz = nnz;
+    {
+        tl_alloc_bytes = &e->index_bytes;
+        struct Unbook { ~Unbook() { tl_alloc_bytes = nullptr; } } unbook;
+        HRAG_TRY(dev_upload(&e->d_fsrc_ptr, row_ptr, n_facts + 1));
+        if (nnz > 0)
+            HRAG_TRY(dev_upload(&e->d_fsrc_pos, passage_pos, nnz));
+        else
+            HRAG_TRY(dev_alloc(&e->d_fsrc_pos, 1));   // a valid pointer the kernel never reads
+    }
+    {
+        tl_alloc_bytes = &e->workspace_bytes;
+        struct Unbook { ~Unbook() { tl_alloc_bytes = nullptr; } } unbook;
+        HRAG_TRY(dev_alloc(&e->d_fact_mask, (int64_t)e->max_batch * e->fact_words));
+    }
+    return HRAG_OK;
+}
+
+hrag_status hrag_fact_mask_from_docs(const uint32_t *doc_words_dev, int64_t doc_ld_words, int64_t doc_bit_offset,
+                                     int64_t n_docs, int32_t rows, const int64_t *row_ptr_dev,
+                                     const int32_t *passage_pos_dev, int64_t n_facts, uint32_t *out_dev,
+                                     hrag_stream stream) {
+    return launch_fact_mask(doc_words_dev, doc_ld_words, doc_bit_offset, n_docs, rows, row_ptr_dev, passage_pos_dev,
+                            n_facts, out_dev, (hipStream_t)stream);
+}
+
+// phase A of the "seeds" scope: fact bitset from the doc filter, then the two-step path of hrag_score_facts (the [B, F]
+// scores + one masked top-k whose min / max cover the allowed facts only) at every batch size.  The fused path of
+// hrag_score_facts is bit-identical to the two-step one, so with every fact allowed this equals hrag_score_facts
+hrag_status hrag_score_facts_scoped(hrag_engine *e, const uint16_t *q, int32_t batch, int32_t k, int32_t *idx_out,
+                                    float *score_out, hrag_stream stream, const uint32_t *filter,
+                                    int64_t filter_ld_words) {
+    HRAG_TRY(check_batch(e, batch));
+    HRAG_REQUIRE(q && idx_out && score_out, "NULL argument");
+    HRAG_REQUIRE(filter != nullptr, "NULL filter (hrag_score_facts scores every fact)");
+    if (!e->d_fsrc_ptr) {
+        set_error("hrag_score_facts_scoped needs the fact -> passage table: call hrag_engine_set_fact_sources first");
+        return HRAG_EINVAL;
+    }
+    TopkMask dm;
+    const TopkMask *dmask = nullptr;
+    HRAG_TRY(doc_filter(e, filter, filter_ld_words, dm, &dmask));
+    HRAG_REQUIRE(k >= 1 && k <= kTopkMax, "k=%d outside [1, %d]", k, kTopkMax);
+    hipStream_t s = (hipStream_t)stream;
+    HRAG_ENGINE_CALL(e, stream);
+    e->counters.score_facts.fetch_add(1);
+    if (e->profiling) HRAG_HIP_TRY(hipEventRecord(e->ev[EV_FACT0], s));
+    const int32_t mrows = filter_ld_words == 0 ? 1 : batch;
+    HRAG_TRY(launch_fact_mask(filter, filter_ld_words, e->p_offset, e->n_passages, mrows, e->d_fsrc_ptr, e->d_fsrc_pos,
+                              e->n_facts, e->d_fact_mask, s));
+    TopkMask fm{e->d_fact_mask, filter_ld_words == 0 ? 0 : e->fact_words, 0};
+    fm.minmax_allowed = 1;
+    HRAG_TRY(prep_query(e, q, batch, s, &q));
+    HRAG_TRY(launch_sim_gemm(e->d_femb, e->f_rows, e->kdim, q, batch, e->d_sfact, e->ld_f, s, 0, e->emb_dtype));
+    HRAG_TRY(launch_row_topk(e->d_sfact, batch, e->f_rows, e->ld_f, k, 0, kNormMinMax, idx_out, score_out, nullptr,
+                             nullptr, s, e->d_topk_ws, kTopkWsBytes, &fm));
+    if (e->profiling) {
+        HRAG_HIP_TRY(hipEventRecord(e->ev[EV_FACT1], s));
+        e->have_fact_ev = true;
+    }
+    return HRAG_OK;
+}
+
 hrag_status hrag_stage_seeds(hrag_engine *e, const int32_t *kept_idx, const float *kept_score,
                              const int32_t *kept_count, int32_t kf, int32_t link_top_k, int32_t batch,
                              int32_t *seed_vtx, float *seed_w, int32_t *seed_cnt, int32_t *flags,
@@ -1253,11 +1344,12 @@ static hrag_status retrieve_impl(hrag_engine *e, const uint16_t *q_pass, const f
                                  float passage_node_weight, int32_t ppr_iters, int32_t ppr_max_iters, float ppr_tol,
                                  int32_t k, int32_t *doc_idx_out, float *doc_score_out, int32_t *flags_out,
                                  float *residual_out, int32_t *iters_out, hrag_stream stream,
-                                 const uint32_t *filter, int64_t filter_ld_words) {
+                                 const uint32_t *filter, int64_t filter_ld_words, bool scoped = false) {
     HRAG_TRY(check_batch(e, batch));
     TopkMask fm;
     const TopkMask *mask = nullptr;
     HRAG_TRY(doc_filter(e, filter, filter_ld_words, fm, &mask));
+    HRAG_REQUIRE(!scoped || mask, "NULL filter (the scoped call needs the allowed passages)");
     HRAG_REQUIRE(ppr_tol >= 0.f && ppr_tol == ppr_tol, "ppr_tol must be >= 0");
     HRAG_REQUIRE(ppr_tol == 0.f || ppr_tol >= HRAG_PPR_TOL_MIN,
                  "ppr_tol=%g is below HRAG_PPR_TOL_MIN=%g: fp32 arithmetic leaves an error floor of %g however small the "
@@ -1310,6 +1402,9 @@ static hrag_status retrieve_impl(hrag_engine *e, const uint16_t *q_pass, const f
         HRAG_TRY(prep_query(e, q_pass, batch, s, &q_pass));
         HRAG_TRY(launch_sim_gemm(e->d_pemb, e->p_rows, e->kdim, q_pass, batch, e->d_spass, e->ld_p, s, 0, e->emb_dtype));
     }
+    // "seeds" scope: the prior normalised over the allowed passages, 0 elsewhere -- the min / max below are then 0 / 1
+    // and every prior kernel's own normalisation is exact identity on these rows (include/hrag.h)
+    if (scoped) HRAG_TRY(launch_masked_prior(e->d_spass, batch, e->n_passages, e->ld_p, *mask, s));
     const bool sv_half = sv && use_sv_half(e, ppr_iters, damping);
     HRAG_TRY(launch_row_minmax(e->d_spass, batch, e->n_passages, e->ld_p, e->d_mn_p, e->d_mx_p, s,
                                (f16 || sv_half) ? e->d_ssum : nullptr));
@@ -1492,6 +1587,31 @@ hrag_status hrag_retrieve_filtered(hrag_engine *e, const uint16_t *q_pass, int32
                          flags_out, residual_out, iters_out, stream, filter_dev, filter_ld_words);
 }
 
+hrag_status hrag_retrieve_scoped(hrag_engine *e, const uint16_t *q_pass, int32_t batch, const int32_t *kept_idx,
+                                 const float *kept_score, const int32_t *kept_count, int32_t kf, int32_t link_top_k,
+                                 float damping, float passage_node_weight, int32_t ppr_iters, int32_t ppr_max_iters,
+                                 float ppr_tol, int32_t k, int32_t *doc_idx_out, float *doc_score_out, int32_t *flags_out,
+                                 float *residual_out, int32_t *iters_out, hrag_stream stream, const uint32_t *filter_dev,
+                                 int64_t filter_ld_words) {
+    HRAG_REQUIRE(q_pass != nullptr, "NULL argument");
+    return retrieve_impl(e, q_pass, nullptr, 0, batch, kept_idx, kept_score, kept_count, kf, link_top_k, damping,
+                         passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol, k, doc_idx_out, doc_score_out,
+                         flags_out, residual_out, iters_out, stream, filter_dev, filter_ld_words, true);
+}
+
+hrag_status hrag_retrieve_scored_scoped(hrag_engine *e, const float *pass_scores, int64_t pass_ld, int32_t batch,
+                                        const int32_t *kept_idx, const float *kept_score, const int32_t *kept_count,
+                                        int32_t kf, int32_t link_top_k, float damping, float passage_node_weight,
+                                        int32_t ppr_iters, int32_t ppr_max_iters, float ppr_tol, int32_t k,
+                                        int32_t *doc_idx_out, float *doc_score_out, int32_t *flags_out,
+                                        float *residual_out, int32_t *iters_out, hrag_stream stream,
+                                        const uint32_t *filter_dev, int64_t filter_ld_words) {
+    HRAG_REQUIRE(pass_scores != nullptr, "NULL argument");
+    return retrieve_impl(e, nullptr, pass_scores, pass_ld, batch, kept_idx, kept_score, kept_count, kf, link_top_k,
+                         damping, passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol, k, doc_idx_out, doc_score_out,
+                         flags_out, residual_out, iters_out, stream, filter_dev, filter_ld_words, true);
+}
+
 hrag_status hrag_retrieve_scored(hrag_engine *e, const float *pass_scores, int64_t pass_ld, int32_t batch,
                                  const int32_t *kept_idx, const float *kept_score, const int32_t *kept_count,
                                  int32_t kf, int32_t link_top_k, float damping, float passage_node_weight,
@@ -1532,9 +1652,9 @@ hrag_status hrag_dense_retrieve(hrag_engine *e, const uint16_t *q_pass, int32_t 
     return hrag_dense_retrieve_filtered(e, q_pass, batch, k, doc_idx_out, doc_score_out, stream, nullptr, 0);
 }
 
-hrag_status hrag_dense_retrieve_filtered(hrag_engine *e, const uint16_t *q_pass, int32_t batch, int32_t k,
-                                         int32_t *doc_idx_out, float *doc_score_out, hrag_stream stream,
-                                         const uint32_t *filter_dev, int64_t filter_ld_words) {
+static hrag_status dense_impl(hrag_engine *e, const uint16_t *q_pass, int32_t batch, int32_t k, int32_t *doc_idx_out,
+                              float *doc_score_out, hrag_stream stream, const uint32_t *filter_dev,
+                              int64_t filter_ld_words, bool scoped) {
     HRAG_TRY(check_batch(e, batch));
     TopkMask fm;
     const TopkMask *mask = nullptr;
@@ -1548,7 +1668,22 @@ hrag_status hrag_dense_retrieve_filtered(hrag_engine *e, const uint16_t *q_pass,
     e->counters.queries.fetch_add(batch);
     HRAG_TRY(prep_query(e, q_pass, batch, s, &q_pass));
     HRAG_TRY(launch_sim_gemm(e->d_pemb, e->p_rows, e->kdim, q_pass, batch, e->d_spass, e->ld_p, s, 0, e->emb_dtype));
+    // "seeds" scope: normalised over the allowed passages first; the ranking's own min-max is then identity
+    if (scoped) HRAG_TRY(launch_masked_prior(e->d_spass, batch, e->n_passages, e->ld_p, *mask, s));
     return rank_rows(e, e->d_spass, batch, e->n_passages, k, 0, kNormMinMax, doc_idx_out, doc_score_out, s, mask);
+}
+
+hrag_status hrag_dense_retrieve_filtered(hrag_engine *e, const uint16_t *q_pass, int32_t batch, int32_t k,
+                                         int32_t *doc_idx_out, float *doc_score_out, hrag_stream stream,
+                                         const uint32_t *filter_dev, int64_t filter_ld_words) {
+    return dense_impl(e, q_pass, batch, k, doc_idx_out, doc_score_out, stream, filter_dev, filter_ld_words, false);
+}
+
+hrag_status hrag_dense_retrieve_scoped(hrag_engine *e, const uint16_t *q_pass, int32_t batch, int32_t k,
+                                       int32_t *doc_idx_out, float *doc_score_out, hrag_stream stream,
+                                       const uint32_t *filter_dev, int64_t filter_ld_words) {
+    HRAG_REQUIRE(filter_dev != nullptr, "NULL filter (the scoped call needs the allowed passages)");
+    return dense_impl(e, q_pass, batch, k, doc_idx_out, doc_score_out, stream, filter_dev, filter_ld_words, true);
 }
 
 hrag_status hrag_ppr(hrag_engine *e, const float *reset, int32_t batch, float damping, int32_t iters,

@@ -172,6 +172,12 @@ struct hrag_engine {
     // fused fact top-k (sim_gemm.hip): tile max / min, selected tiles, global min / max per query
     float *d_fused_ws = nullptr, *d_mn_f = nullptr, *d_mx_f = nullptr;
     int32_t *d_fused_sel = nullptr;
+    // scoped doc filter (hrag_engine_set_fact_sources): fact -> source passages CSR (index half, borrowed by workspaces)
+    // and the fact bitset of the current call [max_batch][fact_words] (per handle)
+    int64_t *d_fsrc_ptr = nullptr;
+    int32_t *d_fsrc_pos = nullptr;
+    int64_t fsrc_nnz = 0, fact_words = 0;
+    uint32_t *d_fact_mask = nullptr;
     // two-stage fp16 PPR (ppr16.hip): SELL-8 matrix + fp16 state, unsharded engines with max_batch > 8
     bool f16_ready = false;   // fp16 state buffers present (max_batch > 8)
     int32_t f16_max_batch = 0;  // ... sized for this many queries (64 when the fp8 path serves the larger batches)

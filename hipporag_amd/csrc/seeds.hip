@@ -85,7 +85,52 @@ __global__ __launch_bounds__(64) void build_seeds_kernel(const int32_t *__restri
     }
 }
 
+// the fact bitset of a scoped phase A (launch_fact_mask): one thread per output word, i.e. per 32 facts, so the word is
+// assembled in a register and stored once -- no atomics.  A fact's sources are few (usually one passage): the inner loop
+// stops at the first allowed one
+__global__ __launch_bounds__(256) void fact_mask_kernel(const uint32_t *__restrict__ doc, int64_t doc_ld_words,
+                                                        int64_t doc_bit0, int64_t n_docs,
+                                                        const int64_t *__restrict__ row_ptr,
+                                                        const int32_t *__restrict__ pos, int64_t n_facts,
+                                                        int64_t fact_words, uint32_t *__restrict__ out) {
+    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int row = blockIdx.y;
+    if (w >= fact_words) return;
+    const uint32_t *d = doc + (size_t)row * (size_t)doc_ld_words;
+    const int64_t f0 = w * 32;
+    const int nf = n_facts - f0 < 32 ? (int)(n_facts - f0) : 32;
+    uint32_t bits = 0;
+    for (int j = 0; j < nf; ++j) {
+        const int64_t end = row_ptr[f0 + j + 1];
+        for (int64_t e = row_ptr[f0 + j]; e < end; ++e) {
+            const int64_t p = pos[e];
+            if (p < 0 || p >= n_docs) continue;
+            const int64_t b = doc_bit0 + p;
+            if ((d[b >> 5] >> (b & 31)) & 1u) {
+                bits |= 1u << j;
+                break;
+            }
+        }
+    }
+    out[(size_t)row * (size_t)fact_words + w] = bits;
+}
+
 }  // namespace
+
+hrag_status launch_fact_mask(const uint32_t *doc, int64_t doc_ld_words, int64_t doc_bit0, int64_t n_docs, int32_t rows,
+                             const int64_t *row_ptr, const int32_t *pos, int64_t n_facts, uint32_t *out, hipStream_t s) {
+    HRAG_REQUIRE(doc && row_ptr && out && rows >= 1 && n_facts >= 1 && n_docs >= 0 && doc_bit0 >= 0, "bad argument");
+    HRAG_REQUIRE(doc_ld_words == 0 || doc_ld_words >= ceil_div(doc_bit0 + n_docs, 32),
+                 "doc filter: %lld words per row < %lld (0: one row for every query)", (long long)doc_ld_words,
+                 (long long)ceil_div(doc_bit0 + n_docs, 32));
+    const int64_t fact_words = ceil_div(n_facts, 32);
+    HRAG_REQUIRE(fact_words <= (int64_t)256 * 0x7fffffff && rows <= 65535, "fact mask of %lld x %lld words not supported",
+                 (long long)rows, (long long)fact_words);
+    hipLaunchKernelGGL(fact_mask_kernel, dim3((unsigned)ceil_div(fact_words, 256), (unsigned)rows), dim3(256), 0, s, doc,
+                       doc_ld_words, doc_bit0, n_docs, row_ptr, pos, n_facts, fact_words, out);
+    HRAG_LAUNCH_CHECK();
+    return HRAG_OK;
+}
 
 hrag_status launch_build_seeds(const int32_t *kept_idx, const float *kept_score,
                                const int32_t *kept_count, int32_t kf, int32_t link_top_k,

@@ -189,7 +189,8 @@ __device__ __forceinline__ float minmax_norm(float s, float mn, float mx) {
 // row row_in and writes its k candidates (global positions, raw values) as output row blockIdx.x;
 // topk_merge_kernel then picks the final k.
 // kMasked: only the elements the mask allows are ranked (a part's target is min(k, its allowed count)); the row min /
-// max still cover every element
+// max still cover every element, or (mask.minmax_allowed: the scoped fact ranking) the allowed ones only -- a part
+// without any then reports +inf / -inf, which the merge's fminf / fmaxf pass over
 template <bool kMasked>
 __global__ __launch_bounds__(TK_THREADS) void row_topk_kernel(
     const float *__restrict__ scores, int64_t n_total, int64_t ld, int32_t k, int32_t idx_offset_in,
@@ -219,7 +220,7 @@ __global__ __launch_bounds__(TK_THREADS) void row_topk_kernel(
     uint64_t t0 = 0, t1 = 0;
     float mn = INFINITY, mx = -INFINITY;
     for_each_key<kMasked>(s, n, tid, mrow, [&](float v, uint64_t key) {
-        minmax_add(mn, mx, v);
+        if (!kMasked || !mask.minmax_allowed || key != 0) minmax_add(mn, mx, v);
         if (key > t1) {
             if (key > t0) {
                 t1 = t0;
@@ -409,6 +410,36 @@ __global__ __launch_bounds__(TK_THREADS) void row_minmax_kernel(const float *__r
         mx_out[row] = mx;
         if (sum_out) sum_out[row] = (float)sum;
     }
+}
+
+// the scoped passage prior (launch_masked_prior): min / max over the allowed elements of the row, then the row is
+// rewritten -- allowed: minmax_norm over them (the formula every prior kernel uses), others: 0
+__global__ __launch_bounds__(TK_THREADS) void masked_prior_kernel(float *__restrict__ scores, int64_t n, int64_t ld,
+                                                                  TopkMask mask) {
+    __shared__ float red_mn[TK_THREADS / 64], red_mx[TK_THREADS / 64];
+    const int tid = threadIdx.x;
+    const int row = blockIdx.x;
+    float *s = scores + (size_t)row * ld;
+    const MaskRow mrow{mask.words + (size_t)row * (size_t)mask.ld_words, mask.bit_offset};
+    float mn = INFINITY, mx = -INFINITY;
+    for_each_key<true>(s, n, tid, mrow, [&](float v, uint64_t key) {
+        if (key != 0) minmax_add(mn, mx, v);
+    });
+    mn = wave_min(mn);
+    mx = wave_max(mx);
+    if ((tid & 63) == 0) {
+        red_mn[tid >> 6] = mn;
+        red_mx[tid >> 6] = mx;
+    }
+    __syncthreads();
+    mn = red_mn[0];
+    mx = red_mx[0];
+    for (int w = 1; w < TK_THREADS / 64; ++w) {
+        mn = fminf(mn, red_mn[w]);
+        mx = fmaxf(mx, red_mx[w]);
+    }
+    // (no allowed element: mn / mx stay +-inf and every element is written 0 without reading them)
+    for (int64_t i = tid; i < n; i += TK_THREADS) s[i] = mrow.test(i) ? minmax_norm(s[i], mn, mx) : 0.f;
 }
 
 // second level of the split selection: parts * k candidates per row (keys are unique), parts * k <= TK_CAP.
@@ -805,6 +836,15 @@ hrag_status launch_row_topk_large(const float *scores, int32_t batch, int64_t n,
         HRAG_LAUNCH_CHECK();
         std::swap(ka, kb);
     }
+    return HRAG_OK;
+}
+
+hrag_status launch_masked_prior(float *scores, int32_t batch, int64_t n, int64_t ld, const TopkMask &mask, hipStream_t s) {
+    HRAG_REQUIRE(n >= 0 && n < (int64_t)0xffffffffll, "row length %lld not supported", (long long)n);
+    HRAG_TRY(check_mask(&mask, n));
+    if (batch == 0 || n == 0) return HRAG_OK;
+    hipLaunchKernelGGL(masked_prior_kernel, dim3((unsigned)batch), dim3(TK_THREADS), 0, s, scores, n, ld, mask);
+    HRAG_LAUNCH_CHECK();
     return HRAG_OK;
 }
 

@@ -347,6 +347,17 @@ class LocalComm:
         pass
 
 
+def refuse_seeds_scope(filter_scope: str = "ranking", scope_filter=None):
+    """The multi-GPU retrievers serve the doc filter's "ranking" scope only: a "seeds" request (include/hrag.h, scoped
+    doc filter) is refused instead of being answered with a post-filter."""
+    from .engine import FILTER_SCOPES
+    if filter_scope not in FILTER_SCOPES:
+        raise ValueError(f"filter_scope={filter_scope!r}: one of {FILTER_SCOPES} expected")
+    if filter_scope == "seeds" or scope_filter is not None:
+        raise ValueError('filter_scope="seeds" is not supported by the row-sharded / hybrid retrievers: their phase A '
+                         'and passage prior span every shard; use a single-GPU engine (HippoRAGEngine) for scoped queries')
+
+
 def merge_ranked(idx_parts, val_parts, k: int, topk):
     """Merge per-shard top-k lists (each sorted score desc, id desc; shard id ranges ascending in rank
     order) into the global top-k under the same rule.  Reversed and concatenated in rank order, "later
@@ -380,8 +391,9 @@ class ShardedRetriever:
             self._bufs[batch] = (lay, bufs)
         return self._bufs[batch]
 
-    def score_facts(self, q_fact, k: int = 5):
+    def score_facts(self, q_fact, k: int = 5, scope_filter=None):
         """Global (fact ids int32 [B, k], min-max normalised scores fp32 [B, k]), replicated."""
+        refuse_seeds_scope(scope_filter=scope_filter)
         torch = _td()[0]
         c = self.comm
         idx, val, mn, mx = self.st.shard_score_facts(q_fact, k)
@@ -395,7 +407,7 @@ class ShardedRetriever:
 
     def retrieve(self, q_pass, kept_idx, kept_score, kept_count, *, link_top_k=5, damping=0.5,
                  passage_node_weight=0.05, ppr_iters=20, k=200, ppr_tol=0.0, ppr_max_iters=0,
-                 check_saturation=True, doc_filter=None):
+                 check_saturation=True, doc_filter=None, filter_scope: str = "ranking"):
         """Returns (doc ids, doc scores, flags) -- and with ppr_tol > 0 additionally (residual, sweeps used): the
         convergence contract of hrag_retrieve on the shards.  Every shard measures the relative update of ITS
         passages; the measures are all-reduced (MAX) before every decision, so all shards run the same steps.
@@ -405,6 +417,7 @@ class ShardedRetriever:
         a timing loop passes False and checks the flags afterwards.
         doc_filter: the GLOBAL doc filter (engine.doc_filter_words forms, over all passages); every shard ranks only the
         allowed passages of its slice, the merge puts a shard's -1 slots after every real entry."""
+        refuse_seeds_scope(filter_scope)
         st, c = self.st, self.comm
         fkw = {} if doc_filter is None else {"doc_filter": doc_filter}
         b = q_pass.shape[0]
@@ -557,7 +570,8 @@ class NativeShardedRetriever:
             raise self._error
         check(st)
 
-    def score_facts(self, q_fact, k: int = 5):
+    def score_facts(self, q_fact, k: int = 5, scope_filter=None):
+        refuse_seeds_scope(scope_filter=scope_filter)
         torch = _td()[0]
         from .engine import _stream
         q = self.st.e._q(q_fact)
@@ -571,9 +585,11 @@ class NativeShardedRetriever:
         return idx, val
 
     def retrieve(self, q_pass, kept_idx, kept_score, kept_count, *, link_top_k=5, damping=0.5, passage_node_weight=0.05,
-                 ppr_iters=20, k=200, ppr_tol=0.0, ppr_max_iters=0, check_saturation=True, doc_filter=None):
+                 ppr_iters=20, k=200, ppr_tol=0.0, ppr_max_iters=0, check_saturation=True, doc_filter=None,
+                 filter_scope: str = "ranking"):
         """Same contract as ShardedRetriever.retrieve: (doc ids, doc scores, flags[, residual, sweeps used]);
         doc_filter: hrag_shard_retrieve_filtered with the global filter."""
+        refuse_seeds_scope(filter_scope)
         torch = _td()[0]
         from .engine import _stream
         q = self.st.e._q(q_pass)
@@ -629,7 +645,8 @@ class HybridRetriever:
     def __init__(self, sim, ppr, comm, pshards):
         self.sim, self.ppr, self.comm, self.pshards = sim, ppr, comm, list(pshards)
 
-    def score_facts(self, q_fact, k: int = 5):
+    def score_facts(self, q_fact, k: int = 5, scope_filter=None):
+        refuse_seeds_scope(scope_filter=scope_filter)
         torch = _td()[0]
         c = self.comm
         idx, val, mn, mx = self.sim.shard_score_facts(q_fact, k)
@@ -650,6 +667,7 @@ class HybridRetriever:
     def retrieve(self, q_pass, kept_idx, kept_score, kept_count, **kw):
         """q_pass / kept_*: the GLOBAL batch (replicated); returns this rank's RetrieveOutput for its B / N queries.
         kw["doc_filter"] (optional): the global batch's filter; a per-query one is cut to this rank's rows."""
+        refuse_seeds_scope(kw.pop("filter_scope", "ranking"))
         torch = _td()[0]
         c, w = self.comm, self.comm.world
         b = q_pass.shape[0]

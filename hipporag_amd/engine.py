@@ -54,6 +54,18 @@ def pack_mask(mask) -> np.ndarray:
     return pad.view("<u4").astype(np.uint32, copy=False)
 
 
+FILTER_SCOPES = ("ranking", "seeds")
+
+
+def check_filter_scope(filter_scope: str, doc_filter) -> bool:
+    """True for the "seeds" scope (include/hrag.h, scoped doc filter), False for "ranking" (the post-filter)."""
+    if filter_scope not in FILTER_SCOPES:
+        raise ValueError(f"filter_scope={filter_scope!r}: one of {FILTER_SCOPES} expected")
+    if filter_scope == "seeds" and doc_filter is None:
+        raise ValueError('filter_scope="seeds" needs a doc_filter (the allowed passages)')
+    return filter_scope == "seeds"
+
+
 def doc_filter_words(doc_filter, n: int, batch: int, device):
     """A doc filter -- torch bool [n] or [batch, n], or the packed uint32 (or int32) words [W] or [batch, W],
     W >= ceil(n / 32) -- as (int32 device words, filter_ld_words): ld 0 for one row shared by the batch."""
@@ -255,6 +267,8 @@ class HippoRAGEngine:
     src/hipporag/HippoRAG.py:1287-1389).  Row-sharded construction (multi-GPU): pass the row shard
     of the CSR (``CSRGraph.rows``) with ``row_offset`` and the embedding shards with their offsets.
     """
+
+    has_fact_sources = False     # set_fact_sources() was called (the scoped doc filter's phase A)
 
     def __init__(self, graph: CSRGraph, passage_vertex, passage_emb, fact_emb=None,
                  subj_vertex=None, obj_vertex=None, num_chunks=None, *, max_batch: int = 256,
@@ -476,27 +490,50 @@ class HippoRAGEngine:
         return bc.value, ns.value
 
     # ------------------------------------------------------------------ fused entry points
-    def score_facts(self, q_fact, k: int = 5):
-        """Phase A: (fact ids int32 [B,k], min-max normalised scores fp32 [B,k])."""
+    def set_fact_sources(self, row_ptr, passage_pos):
+        """The fact -> source-passage table of the scoped doc filter (hrag_engine_set_fact_sources): the sources of fact f
+        are passage_pos[row_ptr[f]:row_ptr[f + 1]] (passage positions).  On the root engine, before any workspace."""
+        if getattr(self, "_parent", None) is not None:
+            raise ValueError("fact sources belong to the shared index: set them on the root engine")
+        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
+        pp = np.ascontiguousarray(passage_pos, dtype=np.int32)
+        if rp.ndim != 1 or rp.shape[0] < 1 or pp.ndim != 1:
+            raise ValueError("row_ptr [n_facts + 1] and passage_pos [nnz] expected")
+        check(self._lib.hrag_engine_set_fact_sources(self._handle, rp.ctypes.data, pp.ctypes.data if pp.size else None,
+                                                     rp.shape[0] - 1, pp.shape[0]))
+        self.has_fact_sources = True
+
+    def score_facts(self, q_fact, k: int = 5, scope_filter=None):
+        """Phase A: (fact ids int32 [B,k], min-max normalised scores fp32 [B,k]).
+        scope_filter: a doc filter (doc_filter_words) -- the top k among the facts of those passages, normalised over
+        them (hrag_score_facts_scoped; needs set_fact_sources)."""
         torch = _torch()
         q = self._q(q_fact)
         b = q.shape[0]
         idx = self._empty((b, k), torch.int32)
         sc = self._empty((b, k), torch.float32)
-        check(self._lib.hrag_score_facts(self._handle, q.data_ptr(), b, k, idx.data_ptr(), sc.data_ptr(),
-                                         _stream()))
+        if scope_filter is None:
+            check(self._lib.hrag_score_facts(self._handle, q.data_ptr(), b, k, idx.data_ptr(), sc.data_ptr(),
+                                             _stream()))
+        else:
+            fw, fld = doc_filter_words(scope_filter, self.n_passages, b, self.device)
+            check(self._lib.hrag_score_facts_scoped(self._handle, q.data_ptr(), b, k, idx.data_ptr(), sc.data_ptr(),
+                                                    _stream(), fw.data_ptr(), fld))
         return idx, sc
 
     def retrieve(self, q_pass, kept_idx, kept_score, kept_count, *, link_top_k: int = 5,
                  damping: float = 0.5, passage_node_weight: float = 0.05, ppr_iters: int = 20,
                  k: int = 200, ppr_tol: float = 0.0, ppr_max_iters: int = 0,
-                 want_residual: bool = True, doc_filter=None) -> RetrieveOutput:
+                 want_residual: bool = True, doc_filter=None, filter_scope: str = "ranking") -> RetrieveOutput:
         """Phase B: seeds + passage prior + PPR + ranking (DPR ranking where kept_count == 0).
         ppr_tol / ppr_max_iters: the convergence contract of include/hrag.h (0 = exactly ppr_iters sweeps);
         the output carries the per-query residual and the sweeps that ran.
         doc_filter: only these passages may be ranked (doc_filter_words; hrag_retrieve_filtered): each row is the first
-        min(k, allowed) allowed entries of the unfiltered ranking, then -1 / 0.  Scoring is unchanged."""
+        min(k, allowed) allowed entries of the unfiltered ranking, then -1 / 0.  Scoring is unchanged.
+        filter_scope="seeds": the passage prior and the DPR fallback are normalised over the allowed passages as well
+        (hrag_retrieve_scoped; the kept facts should come from score_facts(scope_filter=) with the same filter)."""
         torch = _torch()
+        scoped = check_filter_scope(filter_scope, doc_filter)
         q = self._q(q_pass)
         b = q.shape[0]
         kept_idx = kept_idx.to(self.device, torch.int32).contiguous()
@@ -518,14 +555,17 @@ class HippoRAGEngine:
             check(self._lib.hrag_retrieve(*args))
         else:
             fw, fld = doc_filter_words(doc_filter, self.n_passages, b, self.device)
-            check(self._lib.hrag_retrieve_filtered(*args, fw.data_ptr(), fld))
+            fn = self._lib.hrag_retrieve_scoped if scoped else self._lib.hrag_retrieve_filtered
+            check(fn(*args, fw.data_ptr(), fld))
         return RetrieveOutput(idx, sc, flags, resid, used)
 
     def retrieve_scored(self, pass_scores, kept_idx, kept_score, kept_count, *, link_top_k: int = 5,
                         damping: float = 0.5, passage_node_weight: float = 0.05, ppr_iters: int = 20, k: int = 200,
-                        ppr_tol: float = 0.0, ppr_max_iters: int = 0, doc_filter=None) -> RetrieveOutput:
+                        ppr_tol: float = 0.0, ppr_max_iters: int = 0, doc_filter=None,
+                        filter_scope: str = "ranking") -> RetrieveOutput:
         """retrieve() with the raw passage scores fp32 [B, >= Np] supplied by the caller (hrag_retrieve_scored)."""
         torch = _torch()
+        scoped = check_filter_scope(filter_scope, doc_filter)
         sc_in = pass_scores.to(self.device, torch.float32)
         if sc_in.stride(-1) != 1:
             sc_in = sc_in.contiguous()
@@ -544,7 +584,8 @@ class HippoRAGEngine:
             check(self._lib.hrag_retrieve_scored(*args))
         else:
             fw, fld = doc_filter_words(doc_filter, self.n_passages, b, self.device)
-            check(self._lib.hrag_retrieve_scored_filtered(*args, fw.data_ptr(), fld))
+            fn = self._lib.hrag_retrieve_scored_scoped if scoped else self._lib.hrag_retrieve_scored_filtered
+            check(fn(*args, fw.data_ptr(), fld))
         return RetrieveOutput(idx, sc, flags, resid, used)
 
     def retrieve_converged(self, q_pass, kept_idx, kept_score, kept_count, *, damping: float = 0.5,
@@ -571,6 +612,7 @@ class HippoRAGEngine:
         q = self._q(q_pass)
         kept_idx, kept_score, kept_count = (t.to(self.device) for t in (kept_idx, kept_score, kept_count))
         doc_filter = kw.pop("doc_filter", None)
+        check_filter_scope(kw.get("filter_scope", "ranking"), doc_filter)   # (filter_scope travels in kw to every run)
         fw, fld = (None, 0) if doc_filter is None else doc_filter_words(doc_filter, self.n_passages, q.shape[0],
                                                                         self.device)
 
@@ -595,8 +637,10 @@ class HippoRAGEngine:
         check(self._lib.hrag_last_doc_scores(self._handle, batch, out.data_ptr(), self.passage_rows, _stream()))
         return out
 
-    def dense_retrieve(self, q_pass, k: int = 200, doc_filter=None):
+    def dense_retrieve(self, q_pass, k: int = 200, doc_filter=None, filter_scope: str = "ranking"):
+        """DPR top-k; filter_scope="seeds": normalised over the allowed passages (hrag_dense_retrieve_scoped)."""
         torch = _torch()
+        scoped = check_filter_scope(filter_scope, doc_filter)
         q = self._q(q_pass)
         b = q.shape[0]
         idx = self._empty((b, k), torch.int32)
@@ -606,8 +650,8 @@ class HippoRAGEngine:
                                                 sc.data_ptr(), _stream()))
         else:
             fw, fld = doc_filter_words(doc_filter, self.n_passages, b, self.device)
-            check(self._lib.hrag_dense_retrieve_filtered(self._handle, q.data_ptr(), b, k, idx.data_ptr(), sc.data_ptr(),
-                                                         _stream(), fw.data_ptr(), fld))
+            fn = self._lib.hrag_dense_retrieve_scoped if scoped else self._lib.hrag_dense_retrieve_filtered
+            check(fn(self._handle, q.data_ptr(), b, k, idx.data_ptr(), sc.data_ptr(), _stream(), fw.data_ptr(), fld))
         return idx, sc
 
     # ------------------------------------------------------------------ seams

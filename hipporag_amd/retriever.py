@@ -183,6 +183,9 @@ class RetrievalConfig:
                                          # undirected (config_utils.py:176), which is what the polynomial needs
     max_batch: int = 256
     slab_width: int = 0
+    doc_filter_scope: str = "ranking"    # what a doc filter limits (include/hrag.h): "ranking" -- only the ranked list (a
+                                         # post-filter); "seeds" -- also the facts phase A may pick and the passage prior,
+                                         # normalised over the allowed passages (one tenant's documents in a shared index)
 
 
 def identity_rerank_filter(query, candidate_items, candidate_indices, len_after_rerank=None):
@@ -236,6 +239,26 @@ def rank_allowed(full, allowed, want: int):
     return idx, sc
 
 
+def masked_minmax_rows(raw, allowed):
+    """The dense scores of the "seeds" scope on the host: per row, min_max_normalize over the allowed entries (a zero
+    range gives 1), 0 elsewhere."""
+    raw = np.asarray(raw, np.float32)
+    allowed = np.broadcast_to(np.asarray(allowed, bool), raw.shape)
+    out = np.zeros_like(raw)
+    for i in range(raw.shape[0]):
+        a = allowed[i]
+        if a.any():
+            out[i, a] = min_max_normalize(raw[i, a])
+    return out
+
+
+def scope_rows(doc_filter, lo: int, b: int):
+    """The packed doc filter rows of queries [lo, lo + b) as the engine takes them (int32 view)."""
+    import torch
+    rows_w = doc_filter if doc_filter.ndim == 1 else doc_filter[lo: lo + b]
+    return torch.from_numpy(np.ascontiguousarray(rows_w).view(np.int32))
+
+
 def batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Sequence, rerank_filter: Callable, **kw):
     """The body of retrieve() (HippoRAG.py:459-480) for all queries at once: one (doc ids, doc scores, kept facts) per
     query.  See iter_batched_retrieve, which this flattens."""
@@ -248,7 +271,8 @@ def batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Sequenc
 def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Sequence, rerank_filter: Callable, *,
                           linking_top_k: int, damping: float, passage_node_weight: float, ppr_iters: int,
                           num_to_retrieve: int, n_passages: int, timers=None, ppr_tol: float = 0.0,
-                          ppr_max_iters: int = 0, ppr_base_iters_narrow: Optional[int] = None, doc_filter=None):
+                          ppr_max_iters: int = 0, ppr_base_iters_narrow: Optional[int] = None, doc_filter=None,
+                          filter_scope: str = "ranking"):
     """The body of retrieve() (HippoRAG.py:459-480), shared by the mirror class below and by
     reference_adapter.attach(): phase A on the device, the recognition-memory filter on the host (rerank_facts
     :1659-1707), phase B on the device, in batches of eng.max_batch queries.  Yields (offset of the batch, [(doc ids,
@@ -268,7 +292,9 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
     ppr_base_iters_narrow (RetrievalConfig.ppr_base_iters_narrow): the sweeps that ALWAYS run for a batch of at most 64
     queries under a tolerance -- the measure adds stages where the graph needs them.
     doc_filter: packed uint32 words (engine.pack_mask) [W] for every query or [len(queries), W]: only those passages
-    are ranked (a post-filter: the scores do not change); passed to the engine only when given."""
+    are ranked (a post-filter: the scores do not change); passed to the engine only when given.
+    filter_scope="seeds": phase A takes its facts from the allowed passages and phase B normalises the passage prior over
+    them (include/hrag.h, scoped doc filter); needs doc_filter and an engine with fact sources."""
     import torch
     from .engine import host_copy_async, host_wait
     k_f = int(linking_top_k)
@@ -281,6 +307,10 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
         logger.warning("num_to_retrieve=%d exceeds the engine's max_topk=%d: %d documents per query are returned "
                        "(create the engine with a larger retrieval_top_k)", num_to_retrieve, eng.max_topk, k_docs)
     use_facts = len(facts) > 0 and k_f > 0
+    from .engine import check_filter_scope
+    scoped = doc_filter is not None and check_filter_scope(filter_scope, doc_filter)
+    if scoped and use_facts and not getattr(eng, "has_fact_sources", False):
+        raise ValueError('filter_scope="seeds" needs the fact -> passage table on the engine (set_fact_sources)')
     two_halves = hasattr(eng, "retrieve_converged_start")
     starts = list(range(0, len(queries), eng.max_batch))
 
@@ -297,7 +327,11 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
         bt.a = None
         if use_facts:
             t0 = time.time()
-            idx, sc = eng.score_facts(q_tensor(bt.qs, "triple"), k=k_f)
+            if scoped:
+                idx, sc = eng.score_facts(q_tensor(bt.qs, "triple"), k=k_f,
+                                          scope_filter=scope_rows(doc_filter, lo, len(bt.qs)))
+            else:
+                idx, sc = eng.score_facts(q_tensor(bt.qs, "triple"), k=k_f)
             bt.a = (host_copy_async(idx), host_copy_async(sc))
             tick("rerank_time", t0)
         return bt
@@ -338,8 +372,9 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
         kw = dict(link_top_k=k_f, damping=damping, passage_node_weight=passage_node_weight, ppr_iters=base,
                   k=k_docs, ppr_tol=ppr_tol, ppr_max_iters=ppr_max_iters, **({"want_all_scores": True} if beyond else {}))
         if doc_filter is not None:
-            rows_w = doc_filter if doc_filter.ndim == 1 else doc_filter[bt.lo: bt.lo + b]
-            kw["doc_filter"] = torch.from_numpy(np.ascontiguousarray(rows_w).view(np.int32))
+            kw["doc_filter"] = scope_rows(doc_filter, bt.lo, b)
+            if scoped:
+                kw["filter_scope"] = "seeds"
         if two_halves:
             bt.pending = eng.retrieve_converged_start(*args, **kw)
             o = bt.pending.out
@@ -712,10 +747,25 @@ class HippoRAG:
                                "memory = one index).  The retriever is NOT ready: free device memory (or lower "
                                "max_batch / use embedding_precision='bf16') and call prepare_retrieval_objects() "
                                f"again -- {type(exc).__name__}: {exc}") from exc
+        if has_facts and self.proc_triples_to_docs and hasattr(engine, "set_fact_sources"):   # (test doubles lack it)
+            engine.set_fact_sources(*self.fact_source_table())
         self.engine = engine
         self._engine_rows = {"passages": list(self.passage_node_keys), "facts": list(self.fact_node_keys) if has_facts else []}
         self.passage_node_idxs = a["passage_vertex"].tolist()
         self.ready_to_retrieve = True
+
+    def fact_source_table(self):
+        """The fact -> source-passage table of the scoped doc filter as a CSR in self.facts order: (row_ptr int64
+        [n_facts + 1], passage positions int32) from proc_triples_to_docs (HippoRAG.py:1353-1361), positions in
+        passage_node_keys order -- rebuilt from the dicts, so it follows delete()'s renumbering."""
+        pos_of = {k: i for i, k in enumerate(self.passage_node_keys)}
+        row_ptr = np.zeros(len(self.facts) + 1, np.int64)
+        pos = []
+        for f, fact in enumerate(self.facts):
+            src = sorted(pos_of[k] for k in self.proc_triples_to_docs.get(fact, ()) if k in pos_of)
+            pos.extend(src)
+            row_ptr[f + 1] = len(pos)
+        return row_ptr, np.asarray(pos, np.int32)
 
     # ------------------------------------------------------------------ HippoRAG.py:1391-1425
     def get_query_embeddings(self, queries: List):
@@ -843,6 +893,18 @@ class HippoRAG:
                     else np.zeros((0, w), np.uint32))
         return self._filter_words(doc_filter)
 
+    def _scope(self, filter_scope, doc_filter) -> str:
+        """The doc filter's scope of a call: the argument, else RetrievalConfig.doc_filter_scope; "ranking" without a
+        filter."""
+        from .engine import FILTER_SCOPES
+        scope = self.global_config.doc_filter_scope if filter_scope is None else filter_scope
+        if scope not in FILTER_SCOPES:
+            raise ValueError(f"filter_scope={scope!r}: one of {FILTER_SCOPES} expected")
+        if scope == "seeds" and doc_filter is not None and self.fact_node_keys and not self.proc_triples_to_docs:
+            raise ValueError('filter_scope="seeds" needs the facts\' source passages (proc_triples_to_docs): index with '
+                             'index_from_openie')
+        return "ranking" if doc_filter is None else scope
+
     @staticmethod
     def _filter_rows(doc_filter, rows):
         """The doc filter of a subset of the queries (retrieve_ircot's later steps)."""
@@ -850,20 +912,24 @@ class HippoRAG:
 
     # ------------------------------------------------------------------ retrieve :413-499
     def retrieve(self, queries: List[str], num_to_retrieve: Optional[int] = None,
-                 gold_docs: Optional[List[List[str]]] = None, doc_filter=None):
+                 gold_docs: Optional[List[List[str]]] = None, doc_filter=None, filter_scope: Optional[str] = None):
         """doc_filter: limit the ranked documents to a subset of the corpus (a post-filter: scores do not change) --
         a metadata dict {key: value} or {key: [values]} (values of a key: any of them; keys: all of them; matched
         against the chunk metadata, source_id included), a bool numpy array over passage_node_keys, or a list with one
-        of those per query.  Each query gets the first num_to_retrieve allowed documents of its unfiltered ranking."""
+        of those per query.  Each query gets the first num_to_retrieve allowed documents of its unfiltered ranking.
+        filter_scope (default RetrievalConfig.doc_filter_scope): "ranking" as above; "seeds" -- the facts that seed the
+        graph search come from the allowed documents and the dense prior is normalised over them as well (one tenant's
+        documents inside a shared index: the ranking no longer depends on the other tenants' documents)."""
         t_start = time.time()
         cfg = self.global_config
         if num_to_retrieve is None:
             num_to_retrieve = cfg.retrieval_top_k
         self._ensure_ready()
+        scope = self._scope(filter_scope, doc_filter)
         words = self._doc_filter_words(doc_filter, len(queries))
         self.get_query_embeddings(queries)
         results: List[QuerySolution] = []
-        self._retrieve_into(results, queries, num_to_retrieve, words)
+        self._retrieve_into(results, queries, num_to_retrieve, words, scope)
         self.all_retrieval_time += time.time() - t_start
         logger.info("Total Retrieval Time %.2fs", self.all_retrieval_time)
         logger.info("Total Recognition Memory Time %.2fs", self.rerank_time)
@@ -872,9 +938,9 @@ class HippoRAG:
             return results, self._recall(gold_docs, [r.docs for r in results])
         return results
 
-    def _retrieve_into(self, results, queries, num_to_retrieve, doc_filter=None):
+    def _retrieve_into(self, results, queries, num_to_retrieve, doc_filter=None, filter_scope: str = "ranking"):
         cfg = self.global_config
-        extra = {} if doc_filter is None else {"doc_filter": doc_filter}
+        extra = {} if doc_filter is None else {"doc_filter": doc_filter, "filter_scope": filter_scope}
         # batch by batch: the lists of document strings of one batch are built while the device works on the next
         for lo, rows in iter_batched_retrieve(self.engine, queries, self._q_tensor, self.facts if self.fact_node_keys else [],
                                               self.rerank_filter, linking_top_k=cfg.linking_top_k, damping=cfg.damping,
@@ -889,7 +955,7 @@ class HippoRAG:
     # ------------------------------------------------------------------ retrieve_ircot :509-558
     def retrieve_ircot(self, queries: List[str], max_qa_steps: int, num_to_retrieve: Optional[int] = None,
                        gold_docs: Optional[List[List[str]]] = None, reason_fn: Optional[Callable] = None,
-                       doc_filter=None):
+                       doc_filter=None, filter_scope: Optional[str] = None):
         """Iterative retrieval: alternate retrieval and one reasoning step per query, merging the document
         scores by max (:526-543).  reason_fn(query, ranked_docs, thoughts) -> str stands for
         utils/qa_utils.reason_step (the IRCoT prompt + reader LLM are outside this package).  The reference
@@ -902,7 +968,8 @@ class HippoRAG:
             raise ValueError("retrieve_ircot with max_qa_steps > 1 needs a reason_fn (the reader LLM is outside this package)")
         if num_to_retrieve is None:
             num_to_retrieve = self.global_config.retrieval_top_k
-        first = self.retrieve(list(queries), num_to_retrieve=num_to_retrieve, doc_filter=doc_filter)
+        first = self.retrieve(list(queries), num_to_retrieve=num_to_retrieve, doc_filter=doc_filter,
+                              filter_scope=filter_scope)
         merged = [dict(zip(r.docs, r.doc_scores.tolist())) for r in first]
         meta = [dict(zip(r.docs, r.doc_metadata or [])) for r in first]
         thoughts: List[List[str]] = [[] for _ in queries]
@@ -922,7 +989,8 @@ class HippoRAG:
             if not step_q:
                 break
             for i, r in zip(step_i, self.retrieve(step_q, num_to_retrieve=num_to_retrieve,
-                                                  doc_filter=self._filter_rows(doc_filter, step_i))):
+                                                  doc_filter=self._filter_rows(doc_filter, step_i),
+                                                  filter_scope=filter_scope)):
                 for doc, score in zip(r.docs, r.doc_scores.tolist()):
                     merged[i][doc] = max(merged[i].get(doc, float("-inf")), score)
                 meta[i].update(dict(zip(r.docs, r.doc_metadata or [])))
@@ -982,11 +1050,14 @@ class HippoRAG:
 
     # ------------------------------------------------------------------ retrieve_dpr :665-732
     def retrieve_dpr(self, queries: List[str], num_to_retrieve: Optional[int] = None,
-                     gold_docs: Optional[List[List[str]]] = None, doc_filter=None):
+                     gold_docs: Optional[List[List[str]]] = None, doc_filter=None, filter_scope: Optional[str] = None):
+        """Dense retrieval; doc_filter / filter_scope as in retrieve() ("seeds": the scores are normalised over the
+        allowed passages)."""
         cfg = self.global_config
         if num_to_retrieve is None:
             num_to_retrieve = cfg.retrieval_top_k
         self._ensure_ready()
+        scope = self._scope(filter_scope, doc_filter)
         words = self._doc_filter_words(doc_filter, len(queries))
         import torch
         self.get_query_embeddings(queries)
@@ -1007,7 +1078,8 @@ class HippoRAG:
             if beyond:
                 return qs, host_copy_async(eng.sim_scores("passages", self._q_tensor(qs, "passage"))), None
             extra = {} if words is None else {
-                "doc_filter": torch.from_numpy(np.ascontiguousarray(rows_of(lo, len(qs))).view(np.int32))}
+                "doc_filter": torch.from_numpy(np.ascontiguousarray(rows_of(lo, len(qs))).view(np.int32)),
+                "filter_scope": scope}
             idx, sc = eng.dense_retrieve(self._q_tensor(qs, "passage"), k=k_docs, **extra)
             return qs, host_copy_async(idx), host_copy_async(sc)
 
@@ -1019,7 +1091,10 @@ class HippoRAG:
             pending = enqueue(starts[n + 1]) if n + 1 < len(starts) else None
             if beyond:
                 raw = host_wait(idx_h)[:, :len(self.passage_node_keys)]
-                full = np.stack([min_max_normalize(r) for r in raw]).astype(np.float32)
+                if scope == "seeds":
+                    full = masked_minmax_rows(raw, unpack_mask(rows_of(starts[n], len(qs)), raw.shape[1]))
+                else:
+                    full = np.stack([min_max_normalize(r) for r in raw]).astype(np.float32)
                 if words is not None:
                     idx, sc = rank_allowed(full, unpack_mask(rows_of(starts[n], len(qs)), full.shape[1]), want)
                 else:
@@ -1038,12 +1113,12 @@ class HippoRAG:
 
     # ------------------------------------------------------------------ rag_qa :591-663
     def rag_qa(self, queries, gold_docs: Optional[List[List[str]]] = None,
-               gold_answers: Optional[List[List[str]]] = None, doc_filter=None):
+               gold_answers: Optional[List[List[str]]] = None, doc_filter=None, filter_scope: Optional[str] = None):
         if self.qa_fn is None:
             raise NotImplementedError("rag_qa needs a qa_fn (the reader LLM is outside this package)")
         retrieval_metrics = None
         if not isinstance(queries[0], QuerySolution):
-            out = self.retrieve(queries=queries, gold_docs=gold_docs, doc_filter=doc_filter)
+            out = self.retrieve(queries=queries, gold_docs=gold_docs, doc_filter=doc_filter, filter_scope=filter_scope)
             queries, retrieval_metrics = out if gold_docs is not None else (out, None)
         solutions, messages, metadata = self.qa_fn(queries)
         if gold_answers is not None:

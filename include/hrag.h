@@ -60,7 +60,10 @@ extern "C" {
  *        hrag_topk_rows_workspace_bytes (any k), hrag_opts.max_topk above 2048;
  *        later in 0.8 (detect by the symbol): the doc filter -- hrag_topk_rows_masked, hrag_retrieve_filtered,
  *        hrag_retrieve_scored_filtered, hrag_dense_retrieve_filtered, hrag_shard_finish_filtered,
- *        hrag_shard_retrieve_filtered. */
+ *        hrag_shard_retrieve_filtered;
+ *        later in 0.8 (detect by the symbol): the scoped doc filter -- hrag_engine_set_fact_sources,
+ *        hrag_fact_mask_from_docs, hrag_score_facts_scoped, hrag_retrieve_scoped, hrag_retrieve_scored_scoped,
+ *        hrag_dense_retrieve_scoped. */
 #define HRAG_VERSION_MAJOR 0
 #define HRAG_VERSION_MINOR 8
 
@@ -460,6 +463,74 @@ hrag_status hrag_retrieve_scored_filtered(hrag_engine *e, const float *pass_scor
 hrag_status hrag_dense_retrieve_filtered(hrag_engine *e, const uint16_t *q_pass_dev, int32_t batch, int32_t k,
                                          int32_t *doc_idx_out_dev, float *doc_score_out_dev, hrag_stream stream,
                                          const uint32_t *filter_dev, int64_t filter_ld_words);
+
+/* ---- scoped doc filter: the seeds and the passage prior come from the allowed passages ----
+ * The doc filter above hides passages from the ranked list; the "seeds" scope also takes the query's evidence from them
+ * only -- one tenant's documents inside a shared index.  For a query whose allowed passage set is A (same mask format
+ * and filter_ld_words rule as above):
+ *   phase A   hrag_score_facts_scoped: a fact is allowed when at least one passage it was extracted from is in A (the
+ *             fact -> source table of hrag_engine_set_fact_sources; a fact without a source is never allowed).  The top
+ *             k facts are taken among the allowed ones, their scores min-max normalised over the allowed facts' raw
+ *             scores (a zero range gives 1).  Fewer than k allowed facts: the row ends in -1 / 0; none: all -1 -- a
+ *             kept_count of 0 then sends the query to the DPR fallback of phase B (HippoRAG.py:467-469).
+ *   prior     hrag_retrieve_scoped & co.: the raw passage scores are min-max normalised over A only (zero range: 1);
+ *             passages outside A get prior 0.  Everything derived from the prior (its mass, the fp16 / fp8 scales)
+ *             is derived from that masked prior.
+ *   seeds     built from the kept facts exactly as in hrag_retrieve.  The divisor num_chunks of a phrase stays its
+ *             GLOBAL count of chunks (a choice: the index has one ent_node_to_chunk_ids, not one per tenant).
+ *   PPR       the whole graph, unchanged.  On an index that is a disjoint union of corpora (no shared entity, no edge
+ *             between them) a scoped query over one corpus therefore sees exactly what an index of that corpus alone
+ *             gives: the reset vector lives in its component and dangling mass returns to the reset vector.
+ *   ranking   post-filtered by A exactly as hrag_retrieve_filtered.  DPR fallback / hrag_dense_retrieve_scoped: the
+ *             dense ranking of A, normalised over A.
+ *   empty A   the row is all -1 / 0 (no fault, no assert).
+ * hrag_last_doc_scores after a scoped call: the PPR scores of every passage -- those outside A included, which can
+ * receive mass through the graph -- or, on the DPR fallback, the dense score normalised over A and 0 outside it; with
+ * an empty A the row carries no meaning.
+ * A NULL filter is HRAG_EINVAL on the scoped calls (the unscoped calls are the "every passage" form). */
+
+/* The fact -> source-passage table (proc_triples_to_docs, HippoRAG.py:1353-1361) as a CSR over host arrays: the
+ * sources of fact f are passage_pos[row_ptr[f] .. row_ptr[f + 1]), passage positions in [0, n_passages).  n_facts must
+ * be the engine's fact count.  Part of the shared index: call it on a root engine before any workspace is created
+ * (HRAG_EINVAL after); workspaces created later borrow the table and get their own fact-mask buffer.  Calling it again
+ * (still without workspaces) replaces the table.  An engine that never calls it allocates nothing for it. */
+hrag_status hrag_engine_set_fact_sources(hrag_engine *e, const int64_t *row_ptr, const int32_t *passage_pos,
+                                         int64_t n_facts, int64_t nnz);
+
+/* Test seam of the scoped phase A's first kernel: out_dev uint32 [rows, ceil(n_facts / 32)] (the mask format above),
+ * bit f of row r set when one of fact f's sources (device CSR row_ptr_dev int64 [n_facts + 1], passage_pos_dev int32)
+ * has bit (doc_bit_offset + passage) set in doc row r (doc_ld_words 0: one doc row for every output row, else >=
+ * ceil((doc_bit_offset + n_docs) / 32)).  Sources outside [0, n_docs) count as not allowed. */
+hrag_status hrag_fact_mask_from_docs(const uint32_t *doc_words_dev, int64_t doc_ld_words, int64_t doc_bit_offset,
+                                     int64_t n_docs, int32_t rows, const int64_t *row_ptr_dev,
+                                     const int32_t *passage_pos_dev, int64_t n_facts, uint32_t *out_dev,
+                                     hrag_stream stream);
+
+/* hrag_score_facts over the facts of the allowed passages (phase A above).  Without fact sources: HRAG_EINVAL. */
+hrag_status hrag_score_facts_scoped(hrag_engine *e, const uint16_t *q_fact_dev, int32_t batch, int32_t k,
+                                    int32_t *fact_idx_out_dev, float *fact_score_out_dev, hrag_stream stream,
+                                    const uint32_t *filter_dev, int64_t filter_ld_words);
+
+/* hrag_retrieve_filtered / hrag_retrieve_scored_filtered / hrag_dense_retrieve_filtered in the "seeds" scope (prior,
+ * fallback and ranking above; the kept facts are the caller's -- from hrag_score_facts_scoped with the same filter). */
+hrag_status hrag_retrieve_scoped(hrag_engine *e, const uint16_t *q_pass_dev, int32_t batch,
+                                 const int32_t *kept_idx_dev, const float *kept_score_dev,
+                                 const int32_t *kept_count_dev, int32_t kf, int32_t link_top_k,
+                                 float damping, float passage_node_weight, int32_t ppr_iters,
+                                 int32_t ppr_max_iters, float ppr_tol, int32_t k,
+                                 int32_t *doc_idx_out_dev, float *doc_score_out_dev,
+                                 int32_t *flags_out_dev, float *residual_out_dev, int32_t *iters_out_dev,
+                                 hrag_stream stream, const uint32_t *filter_dev, int64_t filter_ld_words);
+hrag_status hrag_retrieve_scored_scoped(hrag_engine *e, const float *pass_scores_dev, int64_t pass_ld, int32_t batch,
+                                        const int32_t *kept_idx_dev, const float *kept_score_dev,
+                                        const int32_t *kept_count_dev, int32_t kf, int32_t link_top_k, float damping,
+                                        float passage_node_weight, int32_t ppr_iters, int32_t ppr_max_iters,
+                                        float ppr_tol, int32_t k, int32_t *doc_idx_out_dev, float *doc_score_out_dev,
+                                        int32_t *flags_out_dev, float *residual_out_dev, int32_t *iters_out_dev,
+                                        hrag_stream stream, const uint32_t *filter_dev, int64_t filter_ld_words);
+hrag_status hrag_dense_retrieve_scoped(hrag_engine *e, const uint16_t *q_pass_dev, int32_t batch, int32_t k,
+                                       int32_t *doc_idx_out_dev, float *doc_score_out_dev, hrag_stream stream,
+                                       const uint32_t *filter_dev, int64_t filter_ld_words);
 
 /* ---- lower-level seams (used by the per-method adapters and by the parity tests) ---- */
 
