@@ -163,6 +163,12 @@ SIGNATURES = {
                                       _I32, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P]),
     "hrag_shard_retrieve_filtered": (C.c_int, [_P, C.POINTER(Comm), _P, _I32, _P, _P, _P, _I32, _I32, _F32, _F32, _I32, _I32,
                                                _F32, _I32, _I32, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _I64]),
+    "hrag_shard_score_facts_scoped": (C.c_int, [_P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _I64]),
+    "hrag_shard_passage_scores_scoped": (C.c_int, [_P, _P, _I32, _P, _P, _P, _P, _I64]),
+    "hrag_shard_mask_prior": (C.c_int, [_P, _P, _P, _I32, _P, _P, _P, _P, _I64]),
+    "hrag_shard_score_facts_all_scoped": (C.c_int, [_P, C.POINTER(Comm), _P, _I32, _I32, _P, _I64, _P, _P, _P, _P, _I64]),
+    "hrag_shard_retrieve_scoped": (C.c_int, [_P, C.POINTER(Comm), _P, _I32, _P, _P, _P, _I32, _I32, _F32, _F32, _I32, _I32,
+                                             _F32, _I32, _I32, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _I64]),
     "hrag_engine_set_flags": (C.c_int, [_P, _I32, _I32]),
     "hrag_engine_gather_embeddings": (C.c_int, [_P, _I32, _P, _I64, _P, _P, _P]),
     "hrag_get_timings": (C.c_int, [_P, C.POINTER(Timings)]),

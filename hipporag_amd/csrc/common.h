@@ -480,6 +480,14 @@ hrag_status launch_row_minmax(const float *scores, int32_t batch, int64_t n, int
 // element to 0.  The row min / max of the result are then 0 / 1 (or equal), so the prior kernels' own min-max is exact
 // identity on it
 hrag_status launch_masked_prior(float *scores, int32_t batch, int64_t n, int64_t ld, const TopkMask &mask, hipStream_t s);
+// the same prior on a row shard, split where the statistics cross the shards (hrag_shard_passage_scores_scoped /
+// hrag_shard_mask_prior): launch_masked_stats writes the row min / max over the ALLOWED elements (+inf / -inf: none);
+// launch_masked_prior_ext rewrites every row with the supplied (all-reduced) allowed min / max exactly as
+// launch_masked_prior does and writes the min / max of the rewritten row (mn_in / mx_in may alias mn_out / mx_out)
+hrag_status launch_masked_stats(const float *scores, int32_t batch, int64_t n, int64_t ld, const TopkMask &mask,
+                                float *mn_out, float *mx_out, hipStream_t s);
+hrag_status launch_masked_prior_ext(float *scores, int32_t batch, int64_t n, int64_t ld, const TopkMask &mask,
+                                    const float *mn_in, const float *mx_in, float *mn_out, float *mx_out, hipStream_t s);
 // K4' (topk.hip): the same ranking and output for any k > kTopkMax.  kk = min(k, n) <= kLargeTile keys are selected,
 // sorted and written by one kernel without workspace; larger kk take topk_large_ws_bytes of 8-byte aligned workspace
 // (two key buffers of batch x round_up(kk, kLargeTile) + the row min / max)

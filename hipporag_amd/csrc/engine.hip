@@ -1191,7 +1191,6 @@ hrag_status hrag_engine_set_fact_sources(hrag_engine *e, const int64_t *row_ptr,
                  "engine has %d live workspace(s): set the fact sources before hrag_workspace_create",
                  e->n_workspaces.v.load());
     HRAG_REQUIRE(e->has_facts && e->d_subj != nullptr, "engine was created without facts");
-    HRAG_REQUIRE(e->f_rows == e->n_facts && e->p_rows == e->n_passages, "fact sources need an unsharded engine");
     HRAG_REQUIRE(n_facts == e->n_facts, "n_facts=%lld, the engine has %lld facts", (long long)n_facts,
                  (long long)e->n_facts);
     HRAG_REQUIRE(row_ptr != nullptr && nnz >= 0 && (nnz == 0 || passage_pos != nullptr), "NULL argument");
@@ -1207,21 +1206,27 @@ hrag_status hrag_engine_set_fact_sources(hrag_engine *e, const int64_t *row_ptr,
     for (void *p : {(void *)e->d_fsrc_ptr, (void *)e->d_fsrc_pos, (void *)e->d_fact_mask})
         if (p) (void)hipFree(p);
     e->d_fsrc_ptr = nullptr; e->d_fsrc_pos = nullptr; e->d_fact_mask = nullptr;
-    e->fact_words = ceil_div(n_facts, 32);
-    e->fsrc_nnz = nnz;
+    // a row shard keeps the rows of its owned facts [f_offset, f_offset + f_rows), rebased to start at 0; the passage
+    // positions stay global (the doc filter is the global one).  An unsharded engine owns every row: the whole table
+    const int64_t f0 = e->f_offset, f1 = e->f_offset + e->f_rows;
+    const int64_t base = row_ptr[f0], own_nnz = row_ptr[f1] - base;
+    std::vector<int64_t> own_ptr((size_t)e->f_rows + 1);
+    for (int64_t f = f0; f <= f1; ++f) own_ptr[(size_t)(f - f0)] = row_ptr[f] - base;
+    e->fact_words = ceil_div(e->f_rows, 32);
+    e->fsrc_nnz = own_nnz;
     {
         tl_alloc_bytes = &e->index_bytes;
         struct Unbook { ~Unbook() { tl_alloc_bytes = nullptr; } } unbook;
-        HRAG_TRY(dev_upload(&e->d_fsrc_ptr, row_ptr, n_facts + 1));
-        if (nnz > 0)
-            HRAG_TRY(dev_upload(&e->d_fsrc_pos, passage_pos, nnz));
+        HRAG_TRY(dev_upload(&e->d_fsrc_ptr, own_ptr.data(), e->f_rows + 1));
+        if (own_nnz > 0)
+            HRAG_TRY(dev_upload(&e->d_fsrc_pos, passage_pos + base, own_nnz));
         else
             HRAG_TRY(dev_alloc(&e->d_fsrc_pos, 1));   // a valid pointer the kernel never reads
     }
     {
         tl_alloc_bytes = &e->workspace_bytes;
         struct Unbook { ~Unbook() { tl_alloc_bytes = nullptr; } } unbook;
-        HRAG_TRY(dev_alloc(&e->d_fact_mask, (int64_t)e->max_batch * e->fact_words));
+        HRAG_TRY(dev_alloc(&e->d_fact_mask, (int64_t)e->max_batch * e->fact_words));   // (f_rows 0: none)
     }
     return HRAG_OK;
 }
@@ -1247,6 +1252,7 @@ hrag_status hrag_score_facts_scoped(hrag_engine *e, const uint16_t *q, int32_t b
         set_error("hrag_score_facts_scoped needs the fact -> passage table: call hrag_engine_set_fact_sources first");
         return HRAG_EINVAL;
     }
+    HRAG_TRY(refuse_row_shard(e, "hrag_score_facts_scoped", true));
     TopkMask dm;
     const TopkMask *dmask = nullptr;
     HRAG_TRY(doc_filter(e, filter, filter_ld_words, dm, &dmask));
@@ -1593,7 +1599,8 @@ hrag_status hrag_retrieve_scoped(hrag_engine *e, const uint16_t *q_pass, int32_t
                                  float ppr_tol, int32_t k, int32_t *doc_idx_out, float *doc_score_out, int32_t *flags_out,
                                  float *residual_out, int32_t *iters_out, hrag_stream stream, const uint32_t *filter_dev,
                                  int64_t filter_ld_words) {
-    HRAG_REQUIRE(q_pass != nullptr, "NULL argument");
+    HRAG_REQUIRE(e != nullptr && q_pass != nullptr, "NULL argument");
+    HRAG_TRY(refuse_row_shard(e, "hrag_retrieve_scoped", false));
     return retrieve_impl(e, q_pass, nullptr, 0, batch, kept_idx, kept_score, kept_count, kf, link_top_k, damping,
                          passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol, k, doc_idx_out, doc_score_out,
                          flags_out, residual_out, iters_out, stream, filter_dev, filter_ld_words, true);
@@ -1606,7 +1613,8 @@ hrag_status hrag_retrieve_scored_scoped(hrag_engine *e, const float *pass_scores
                                         int32_t *doc_idx_out, float *doc_score_out, int32_t *flags_out,
                                         float *residual_out, int32_t *iters_out, hrag_stream stream,
                                         const uint32_t *filter_dev, int64_t filter_ld_words) {
-    HRAG_REQUIRE(pass_scores != nullptr, "NULL argument");
+    HRAG_REQUIRE(e != nullptr && pass_scores != nullptr, "NULL argument");
+    HRAG_TRY(refuse_row_shard(e, "hrag_retrieve_scored_scoped", false));
     return retrieve_impl(e, nullptr, pass_scores, pass_ld, batch, kept_idx, kept_score, kept_count, kf, link_top_k,
                          damping, passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol, k, doc_idx_out, doc_score_out,
                          flags_out, residual_out, iters_out, stream, filter_dev, filter_ld_words, true);
@@ -1682,7 +1690,8 @@ hrag_status hrag_dense_retrieve_filtered(hrag_engine *e, const uint16_t *q_pass,
 hrag_status hrag_dense_retrieve_scoped(hrag_engine *e, const uint16_t *q_pass, int32_t batch, int32_t k,
                                        int32_t *doc_idx_out, float *doc_score_out, hrag_stream stream,
                                        const uint32_t *filter_dev, int64_t filter_ld_words) {
-    HRAG_REQUIRE(filter_dev != nullptr, "NULL filter (the scoped call needs the allowed passages)");
+    HRAG_REQUIRE(e != nullptr && filter_dev != nullptr, "NULL argument / NULL filter (the scoped call needs the allowed passages)");
+    HRAG_TRY(refuse_row_shard(e, "hrag_dense_retrieve_scoped", false));
     return dense_impl(e, q_pass, batch, k, doc_idx_out, doc_score_out, stream, filter_dev, filter_ld_words, true);
 }
 

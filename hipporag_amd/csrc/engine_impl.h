@@ -327,6 +327,17 @@ inline hrag_status rank_rows(hrag_engine *e, const float *rows, int32_t batch, i
 // the doc filter of hrag_retrieve_filtered & co. (include/hrag.h): NULL = every passage; filter_ld_words 0 (one row
 // for the batch) or >= ceil(n_passages / 32).  A row shard reads its passages' bits at p_offset.  *out is nullptr for
 // no filter, else &storage
+// the single-engine scoped calls (hrag_score_facts_scoped, hrag_retrieve_scoped & co.) on a row shard: its fact table,
+// scores and statistics cover its own slice only, so the scope's min / max need the shard steps and their all-reduces.
+// facts: phase A (a slice of the fact rows), else phase B (a slice of the graph rows or of the passages)
+inline hrag_status refuse_row_shard(const hrag_engine *e, const char *what, bool facts) {
+    if (facts ? e->f_rows == e->n_facts : (e->p_rows == e->n_passages && e->n_rows == e->V)) return HRAG_OK;
+    set_error("%s on a row-shard engine: its min / max span every shard -- use hrag_shard_score_facts_scoped, "
+              "hrag_shard_passage_scores_scoped and hrag_shard_mask_prior, or the drivers "
+              "hrag_shard_score_facts_all_scoped / hrag_shard_retrieve_scoped", what);
+    return HRAG_EINVAL;
+}
+
 inline hrag_status doc_filter(const hrag_engine *e, const uint32_t *filter, int64_t filter_ld_words, TopkMask &storage,
                               const TopkMask **out) {
     *out = nullptr;

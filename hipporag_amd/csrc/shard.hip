@@ -581,6 +581,72 @@ hrag_status hrag_shard_passage_scores(hrag_engine *e, const uint16_t *q, int32_t
     return launch_row_minmax(e->d_spass, batch, e->p_rows, e->ld_p, mn_out, mx_out, s);
 }
 
+// ---- the "seeds" scope on a row shard (include/hrag.h): the scoped single-engine calls with their min / max split
+//      into this shard's part and an all-reduce by the host
+hrag_status hrag_shard_score_facts_scoped(hrag_engine *e, const uint16_t *q, int32_t batch, int32_t k, int32_t *idx_out,
+                                          float *score_out, float *mn_out, float *mx_out, hrag_stream stream,
+                                          const uint32_t *filter, int64_t filter_ld_words) {
+    HRAG_TRY(shard_batch(e, batch));
+    HRAG_REQUIRE(q && idx_out && score_out && mn_out && mx_out, "NULL argument");
+    HRAG_REQUIRE(filter != nullptr, "NULL filter (hrag_shard_score_facts scores every fact)");
+    HRAG_REQUIRE(k >= 1 && k <= kTopkMax, "k=%d outside [1, %d]", k, kTopkMax);
+    HRAG_REQUIRE(e->d_subj != nullptr, "engine was created without facts");
+    if (!e->d_fsrc_ptr) {
+        set_error("hrag_shard_score_facts_scoped needs the fact -> passage table: call hrag_engine_set_fact_sources first");
+        return HRAG_EINVAL;
+    }
+    TopkMask dm;
+    const TopkMask *dmask = nullptr;   // (validates filter_ld_words against the global passage count)
+    HRAG_TRY(doc_filter(e, filter, filter_ld_words, dm, &dmask));
+    hipStream_t s = (hipStream_t)stream;
+    if (e->f_rows == 0) {
+        HRAG_TRY(launch_fill_i32(idx_out, -1, (int64_t)batch * k, s));
+        HRAG_HIP_TRY(hipMemsetAsync(score_out, 0, (size_t)batch * k * sizeof(float), s));
+        return fill_minmax_neutral(mn_out, mx_out, batch, s);
+    }
+    // the owned facts' bitset from the GLOBAL doc filter: the table holds the owned rows with global passage positions
+    const int32_t mrows = filter_ld_words == 0 ? 1 : batch;
+    HRAG_TRY(launch_fact_mask(filter, filter_ld_words, 0, e->n_passages, mrows, e->d_fsrc_ptr, e->d_fsrc_pos, e->f_rows,
+                              e->d_fact_mask, s));
+    TopkMask fm{e->d_fact_mask, filter_ld_words == 0 ? 0 : e->fact_words, 0};
+    fm.minmax_allowed = 1;   // a row without an allowed fact: -1 / 0 and +inf / -inf, the all-reduce's neutral values
+    HRAG_TRY(prep_query(e, q, batch, s, &q));
+    HRAG_TRY(launch_sim_gemm(e->d_femb, e->f_rows, e->kdim, q, batch, e->d_sfact, e->ld_f, s, 0, e->emb_dtype));
+    return launch_row_topk(e->d_sfact, batch, e->f_rows, e->ld_f, k, (int32_t)e->f_offset, kNormNone, idx_out,
+                           score_out, mn_out, mx_out, s, e->d_topk_ws, kTopkWsBytes, &fm);
+}
+
+hrag_status hrag_shard_passage_scores_scoped(hrag_engine *e, const uint16_t *q, int32_t batch, float *mn_out,
+                                             float *mx_out, hrag_stream stream, const uint32_t *filter,
+                                             int64_t filter_ld_words) {
+    HRAG_TRY(shard_batch(e, batch));
+    HRAG_REQUIRE(q && mn_out && mx_out, "NULL argument");
+    HRAG_REQUIRE(filter != nullptr, "NULL filter (hrag_shard_passage_scores covers every passage)");
+    HRAG_REQUIRE(e->shard_aligned, "the passage embedding shard must hold exactly the passages of the owned rows");
+    TopkMask dm;
+    const TopkMask *mask = nullptr;   // the global filter, read at this shard's p_offset
+    HRAG_TRY(doc_filter(e, filter, filter_ld_words, dm, &mask));
+    hipStream_t s = (hipStream_t)stream;
+    if (e->p_rows == 0) return fill_minmax_neutral(mn_out, mx_out, batch, s);
+    HRAG_REQUIRE(e->d_pemb != nullptr, "engine has no passage embeddings (created for hrag_retrieve_scored)");
+    HRAG_TRY(prep_query(e, q, batch, s, &q));
+    HRAG_TRY(launch_sim_gemm(e->d_pemb, e->p_rows, e->kdim, q, batch, e->d_spass, e->ld_p, s, 0, e->emb_dtype));
+    return launch_masked_stats(e->d_spass, batch, e->p_rows, e->ld_p, *mask, mn_out, mx_out, s);
+}
+
+hrag_status hrag_shard_mask_prior(hrag_engine *e, const float *mn, const float *mx, int32_t batch, float *mn_out,
+                                  float *mx_out, hrag_stream stream, const uint32_t *filter, int64_t filter_ld_words) {
+    HRAG_TRY(shard_batch(e, batch));
+    HRAG_REQUIRE(mn && mx && mn_out && mx_out, "NULL argument");
+    HRAG_REQUIRE(filter != nullptr, "NULL filter (the scoped prior needs the allowed passages)");
+    TopkMask dm;
+    const TopkMask *mask = nullptr;
+    HRAG_TRY(doc_filter(e, filter, filter_ld_words, dm, &mask));
+    hipStream_t s = (hipStream_t)stream;
+    if (e->p_rows == 0) return fill_minmax_neutral(mn_out, mx_out, batch, s);
+    return launch_masked_prior_ext(e->d_spass, batch, e->p_rows, e->ld_p, *mask, mn, mx, mn_out, mx_out, s);
+}
+
 hrag_status hrag_shard_prior_stats(hrag_engine *e, const float *mn, const float *mx, float passage_node_weight,
                                    const int32_t *flags, int32_t batch, float *zmax_out, double *mass_out,
                                    hrag_stream stream) {

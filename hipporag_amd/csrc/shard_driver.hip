@@ -145,11 +145,18 @@ int64_t hrag_shard_workspace_bytes(hrag_engine *e, int32_t world, int32_t batch,
     return n;
 }
 
-hrag_status hrag_shard_score_facts_all(hrag_engine *e, const hrag_comm *comm, const uint16_t *q_fact, int32_t batch, int32_t k,
-                                       void *workspace, int64_t workspace_bytes, int32_t *idx_out, float *score_out,
-                                       hrag_stream stream) {
+}  // extern "C"
+
+namespace {
+
+// phase A of a row shard: local candidates (scoped: among the allowed facts, min / max over them), the global min / max,
+// the merge
+hrag_status score_facts_all(hrag_engine *e, const hrag_comm *comm, const uint16_t *q_fact, int32_t batch, int32_t k,
+                            void *workspace, int64_t workspace_bytes, int32_t *idx_out, float *score_out,
+                            hrag_stream stream, bool scoped, const uint32_t *filter_dev, int64_t filter_ld_words) {
     HRAG_TRY(check_comm(comm));
     HRAG_REQUIRE(e && q_fact && workspace && idx_out && score_out && k >= 1, "bad argument");
+    HRAG_REQUIRE(!scoped || filter_dev, "NULL filter (the scoped call needs the allowed passages)");
     HRAG_REQUIRE(workspace_bytes >= hrag_shard_workspace_bytes(e, comm->world, batch, k), "workspace too small: %lld < %lld bytes",
                  (long long)workspace_bytes, (long long)hrag_shard_workspace_bytes(e, comm->world, batch, k));
     hipStream_t s = (hipStream_t)stream;
@@ -158,12 +165,34 @@ hrag_status hrag_shard_score_facts_all(hrag_engine *e, const hrag_comm *comm, co
     int32_t *lidx = ws.take<int32_t>((int64_t)batch * k);
     float *lval = ws.take<float>((int64_t)batch * k);
     HRAG_REQUIRE(mn && mx && lidx && lval, "workspace too small");
-    HRAG_TRY(hrag_shard_score_facts(e, q_fact, batch, k, lidx, lval, mn, mx, stream));
+    if (scoped)
+        HRAG_TRY(hrag_shard_score_facts_scoped(e, q_fact, batch, k, lidx, lval, mn, mx, stream, filter_dev, filter_ld_words));
+    else
+        HRAG_TRY(hrag_shard_score_facts(e, q_fact, batch, k, lidx, lval, mn, mx, stream));
     if (comm->world > 1) {
         COMM_TRY(comm->all_reduce(comm->user, mn, batch, HRAG_COMM_F32, HRAG_COMM_MIN, stream), "all_reduce");
         COMM_TRY(comm->all_reduce(comm->user, mx, batch, HRAG_COMM_F32, HRAG_COMM_MAX, stream), "all_reduce");
     }
     return merge_topk(comm, lidx, lval, batch, k, ws, mn, mx, idx_out, score_out, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+hrag_status hrag_shard_score_facts_all(hrag_engine *e, const hrag_comm *comm, const uint16_t *q_fact, int32_t batch, int32_t k,
+                                       void *workspace, int64_t workspace_bytes, int32_t *idx_out, float *score_out,
+                                       hrag_stream stream) {
+    return score_facts_all(e, comm, q_fact, batch, k, workspace, workspace_bytes, idx_out, score_out, stream, false,
+                           nullptr, 0);
+}
+
+hrag_status hrag_shard_score_facts_all_scoped(hrag_engine *e, const hrag_comm *comm, const uint16_t *q_fact, int32_t batch,
+                                              int32_t k, void *workspace, int64_t workspace_bytes, int32_t *idx_out,
+                                              float *score_out, hrag_stream stream, const uint32_t *filter_dev,
+                                              int64_t filter_ld_words) {
+    return score_facts_all(e, comm, q_fact, batch, k, workspace, workspace_bytes, idx_out, score_out, stream, true,
+                           filter_dev, filter_ld_words);
 }
 
 hrag_status hrag_shard_retrieve(hrag_engine *e, const hrag_comm *comm, const uint16_t *q_pass, int32_t batch,
@@ -179,17 +208,22 @@ hrag_status hrag_shard_retrieve(hrag_engine *e, const hrag_comm *comm, const uin
                                         residual_out, iters_out, stream, nullptr, 0);
 }
 
-hrag_status hrag_shard_retrieve_filtered(hrag_engine *e, const hrag_comm *comm, const uint16_t *q_pass, int32_t batch,
-                                         const int32_t *kept_idx, const float *kept_score, const int32_t *kept_count,
-                                         int32_t kf, int32_t link_top_k, float damping, float passage_node_weight,
-                                         int32_t ppr_iters, int32_t ppr_max_iters, float ppr_tol, int32_t k, int32_t n_groups,
-                                         void *state0, void *state1, void *state2, void *workspace, int64_t workspace_bytes,
-                                         int32_t *doc_idx_out, float *doc_score_out, int32_t *flags_out,
-                                         float *residual_out, int32_t *iters_out, hrag_stream stream,
-                                         const uint32_t *filter_dev, int64_t filter_ld_words) {
+}  // extern "C"
+
+namespace {
+
+// phase B of a row shard (hrag_shard_retrieve_filtered / hrag_shard_retrieve_scoped)
+hrag_status shard_retrieve(hrag_engine *e, const hrag_comm *comm, const uint16_t *q_pass, int32_t batch,
+                           const int32_t *kept_idx, const float *kept_score, const int32_t *kept_count, int32_t kf,
+                           int32_t link_top_k, float damping, float passage_node_weight, int32_t ppr_iters,
+                           int32_t ppr_max_iters, float ppr_tol, int32_t k, int32_t n_groups, void *state0, void *state1,
+                           void *state2, void *workspace, int64_t workspace_bytes, int32_t *doc_idx_out,
+                           float *doc_score_out, int32_t *flags_out, float *residual_out, int32_t *iters_out,
+                           hrag_stream stream, const uint32_t *filter_dev, int64_t filter_ld_words, bool scoped) {
     HRAG_TRY(check_comm(comm));
     HRAG_REQUIRE(e && q_pass && kept_idx && kept_score && kept_count && state0 && state1 && state2 && workspace &&
                  doc_idx_out && doc_score_out && flags_out, "NULL argument");
+    HRAG_REQUIRE(!scoped || filter_dev, "NULL filter (the scoped call needs the allowed passages)");
     HRAG_REQUIRE(workspace_bytes >= hrag_shard_workspace_bytes(e, comm->world, batch, k), "workspace too small: %lld < %lld bytes",
                  (long long)workspace_bytes, (long long)hrag_shard_workspace_bytes(e, comm->world, batch, k));
     const int32_t w = comm->world;
@@ -223,7 +257,17 @@ hrag_status hrag_shard_retrieve_filtered(hrag_engine *e, const hrag_comm *comm, 
     HRAG_HIP_TRY(hipMemsetAsync(sc, 0, (size_t)batch * sizeof(int32_t), s));
     HRAG_HIP_TRY(hipMemsetAsync(flags, 0, (size_t)batch * sizeof(int32_t), s));
     // ---- similarity of the owned passages, the reset vector's statistics over ALL shards
-    HRAG_TRY(hrag_shard_passage_scores(e, q_pass, batch, mn, mx, stream));
+    if (scoped) {
+        // "seeds" scope: the min / max over the ALLOWED passages of every shard (zmax / est are free until the prior
+        // statistics), the owned rows rewritten with them, then the min / max of the rewritten rows over every shard --
+        // what hrag_retrieve_scoped's launch_row_minmax sees after its masked prior
+        HRAG_TRY(hrag_shard_passage_scores_scoped(e, q_pass, batch, zmax, est, stream, filter_dev, filter_ld_words));
+        HRAG_TRY(reduce(zmax, batch, HRAG_COMM_F32, HRAG_COMM_MIN));
+        HRAG_TRY(reduce(est, batch, HRAG_COMM_F32, HRAG_COMM_MAX));
+        HRAG_TRY(hrag_shard_mask_prior(e, zmax, est, batch, mn, mx, stream, filter_dev, filter_ld_words));
+    } else {
+        HRAG_TRY(hrag_shard_passage_scores(e, q_pass, batch, mn, mx, stream));
+    }
     HRAG_TRY(reduce(mn, batch, HRAG_COMM_F32, HRAG_COMM_MIN));
     HRAG_TRY(reduce(mx, batch, HRAG_COMM_F32, HRAG_COMM_MAX));
     HRAG_TRY(hrag_stage_seeds(e, kept_idx, kept_score, kept_count, kf, link_top_k, batch, sv, sw, sc, flags, stream));
@@ -303,6 +347,38 @@ hrag_status hrag_shard_retrieve_filtered(hrag_engine *e, const hrag_comm *comm, 
     hipLaunchKernelGGL(sat_merge_kernel, dim3((unsigned)ceil_div(batch, 256)), dim3(256), 0, s, flags, sat, batch, flags_out);
     HRAG_LAUNCH_CHECK();
     return HRAG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+hrag_status hrag_shard_retrieve_filtered(hrag_engine *e, const hrag_comm *comm, const uint16_t *q_pass, int32_t batch,
+                                         const int32_t *kept_idx, const float *kept_score, const int32_t *kept_count,
+                                         int32_t kf, int32_t link_top_k, float damping, float passage_node_weight,
+                                         int32_t ppr_iters, int32_t ppr_max_iters, float ppr_tol, int32_t k, int32_t n_groups,
+                                         void *state0, void *state1, void *state2, void *workspace, int64_t workspace_bytes,
+                                         int32_t *doc_idx_out, float *doc_score_out, int32_t *flags_out,
+                                         float *residual_out, int32_t *iters_out, hrag_stream stream,
+                                         const uint32_t *filter_dev, int64_t filter_ld_words) {
+    return shard_retrieve(e, comm, q_pass, batch, kept_idx, kept_score, kept_count, kf, link_top_k, damping,
+                          passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol, k, n_groups, state0, state1, state2,
+                          workspace, workspace_bytes, doc_idx_out, doc_score_out, flags_out, residual_out, iters_out,
+                          stream, filter_dev, filter_ld_words, false);
+}
+
+hrag_status hrag_shard_retrieve_scoped(hrag_engine *e, const hrag_comm *comm, const uint16_t *q_pass, int32_t batch,
+                                         const int32_t *kept_idx, const float *kept_score, const int32_t *kept_count,
+                                         int32_t kf, int32_t link_top_k, float damping, float passage_node_weight,
+                                         int32_t ppr_iters, int32_t ppr_max_iters, float ppr_tol, int32_t k, int32_t n_groups,
+                                         void *state0, void *state1, void *state2, void *workspace, int64_t workspace_bytes,
+                                         int32_t *doc_idx_out, float *doc_score_out, int32_t *flags_out,
+                                         float *residual_out, int32_t *iters_out, hrag_stream stream,
+                                         const uint32_t *filter_dev, int64_t filter_ld_words) {
+    return shard_retrieve(e, comm, q_pass, batch, kept_idx, kept_score, kept_count, kf, link_top_k, damping,
+                          passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol, k, n_groups, state0, state1, state2,
+                          workspace, workspace_bytes, doc_idx_out, doc_score_out, flags_out, residual_out, iters_out,
+                          stream, filter_dev, filter_ld_words, true);
 }
 
 }  // extern "C"

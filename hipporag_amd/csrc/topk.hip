@@ -442,6 +442,51 @@ __global__ __launch_bounds__(TK_THREADS) void masked_prior_kernel(float *__restr
     for (int64_t i = tid; i < n; i += TK_THREADS) s[i] = mrow.test(i) ? minmax_norm(s[i], mn, mx) : 0.f;
 }
 
+// the scoped passage prior of a row shard (launch_masked_stats, launch_masked_prior_ext): the two halves of
+// masked_prior_kernel with the statistics crossing the shards in between.
+//   kRewrite false: mn_out / mx_out = min / max over the allowed elements of the row (+inf / -inf: none), row untouched;
+//   kRewrite true:  the row rewritten with the GLOBAL allowed min / max mn_in / mx_in (allowed: minmax_norm, others: 0),
+//                   mn_out / mx_out = min / max of the rewritten row.  mn_in / mx_in may alias mn_out / mx_out: every
+//                   thread reads them before the barrier that precedes the write
+template <bool kRewrite>
+__global__ __launch_bounds__(TK_THREADS) void masked_rows_kernel(float *__restrict__ scores, int64_t n, int64_t ld,
+                                                                 TopkMask mask, const float *mn_in, const float *mx_in,
+                                                                 float *mn_out, float *mx_out) {
+    __shared__ float red_mn[TK_THREADS / 64], red_mx[TK_THREADS / 64];
+    const int tid = threadIdx.x;
+    const int row = blockIdx.x;
+    float *s = scores + (size_t)row * ld;
+    const MaskRow mrow{mask.words + (size_t)row * (size_t)mask.ld_words, mask.bit_offset};
+    float mn = INFINITY, mx = -INFINITY;
+    if constexpr (kRewrite) {
+        const float lo = mn_in[row], hi = mx_in[row];
+        for (int64_t i = tid; i < n; i += TK_THREADS) {
+            const float v = mrow.test(i) ? minmax_norm(s[i], lo, hi) : 0.f;
+            s[i] = v;
+            minmax_add(mn, mx, v);
+        }
+    } else {
+        for_each_key<true>(s, n, tid, mrow, [&](float v, uint64_t key) {
+            if (key != 0) minmax_add(mn, mx, v);
+        });
+    }
+    mn = wave_min(mn);
+    mx = wave_max(mx);
+    if ((tid & 63) == 0) {
+        red_mn[tid >> 6] = mn;
+        red_mx[tid >> 6] = mx;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < TK_THREADS / 64; ++w) {
+            mn = fminf(mn, red_mn[w]);
+            mx = fmaxf(mx, red_mx[w]);
+        }
+        mn_out[row] = mn;
+        mx_out[row] = mx;
+    }
+}
+
 // second level of the split selection: parts * k candidates per row (keys are unique), parts * k <= TK_CAP.
 // kMasked: a part with fewer than k allowed elements left -1 slots (key 0 here), which sort last: a slot whose key is 0
 // writes -1 / 0 (the row's target min(k, allowed) is then met without counting)
@@ -844,6 +889,29 @@ hrag_status launch_masked_prior(float *scores, int32_t batch, int64_t n, int64_t
     HRAG_TRY(check_mask(&mask, n));
     if (batch == 0 || n == 0) return HRAG_OK;
     hipLaunchKernelGGL(masked_prior_kernel, dim3((unsigned)batch), dim3(TK_THREADS), 0, s, scores, n, ld, mask);
+    HRAG_LAUNCH_CHECK();
+    return HRAG_OK;
+}
+
+hrag_status launch_masked_stats(const float *scores, int32_t batch, int64_t n, int64_t ld, const TopkMask &mask,
+                                float *mn_out, float *mx_out, hipStream_t s) {
+    HRAG_REQUIRE(n >= 1 && n < (int64_t)0xffffffffll, "row length %lld not supported", (long long)n);
+    HRAG_TRY(check_mask(&mask, n));
+    if (batch == 0) return HRAG_OK;
+    hipLaunchKernelGGL(masked_rows_kernel<false>, dim3((unsigned)batch), dim3(TK_THREADS), 0, s,
+                       const_cast<float *>(scores), n, ld, mask, (const float *)nullptr, (const float *)nullptr, mn_out,
+                       mx_out);
+    HRAG_LAUNCH_CHECK();
+    return HRAG_OK;
+}
+
+hrag_status launch_masked_prior_ext(float *scores, int32_t batch, int64_t n, int64_t ld, const TopkMask &mask,
+                                    const float *mn_in, const float *mx_in, float *mn_out, float *mx_out, hipStream_t s) {
+    HRAG_REQUIRE(n >= 1 && n < (int64_t)0xffffffffll, "row length %lld not supported", (long long)n);
+    HRAG_TRY(check_mask(&mask, n));
+    if (batch == 0) return HRAG_OK;
+    hipLaunchKernelGGL(masked_rows_kernel<true>, dim3((unsigned)batch), dim3(TK_THREADS), 0, s, scores, n, ld, mask,
+                       mn_in, mx_in, mn_out, mx_out);
     HRAG_LAUNCH_CHECK();
     return HRAG_OK;
 }

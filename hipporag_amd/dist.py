@@ -147,19 +147,29 @@ def shard_index(csr, passage_vertex, world: int, subj_vertex=None, obj_vertex=No
 
 
 def build_shard_engine(sidx: ShardedIndex, pass_emb, fact_emb, rank: int, max_batch: int, max_topk: int,
-                       flags: int = 0, sell_seg_len: int = 0):
-    """The engine of shard `rank` of a ShardedIndex (full embedding matrices are sliced here)."""
+                       flags: int = 0, sell_seg_len: int = 0, fact_sources=None):
+    """The engine of shard `rank` of a ShardedIndex (full embedding matrices are sliced here).
+    fact_sources: (row_ptr, passage_pos), the fact -> source-passage table in GLOBAL fact order and passage positions
+    (HippoRAGEngine.set_fact_sources) -- shard_index keeps both orders, so the table applies unchanged; the shard engine
+    keeps the rows of its facts and can then serve the doc filter's "seeds" scope."""
     from .engine import HippoRAGEngine
     rps = sidx.rows_per_shard
     p_lo, p_hi = sidx.passages[rank]
     f_lo, f_hi = sidx.facts[rank]
     has_facts = fact_emb is not None and sidx.subj_vertex is not None
-    return HippoRAGEngine(sidx.csr.rows(rank * rps, (rank + 1) * rps), sidx.passage_vertex, pass_emb[p_lo:p_hi],
+    eng = HippoRAGEngine(sidx.csr.rows(rank * rps, (rank + 1) * rps), sidx.passage_vertex, pass_emb[p_lo:p_hi],
                           fact_emb[f_lo:f_hi] if has_facts else None, sidx.subj_vertex if has_facts else None,
                           sidx.obj_vertex if has_facts else None, sidx.num_chunks if has_facts else None,
                           max_batch=max_batch, max_topk=max_topk, row_offset=rank * rps, passage_offset=p_lo,
                           fact_offset=f_lo, n_passages=len(sidx.passage_vertex),
                           n_facts=sidx.facts[-1][1] if has_facts else None, flags=flags, sell_seg_len=sell_seg_len)
+    if fact_sources is not None:
+        try:
+            eng.set_fact_sources(*fact_sources)
+        except BaseException:
+            eng.close()
+            raise
+    return eng
 
 
 class TorchComm:
@@ -358,6 +368,18 @@ def refuse_seeds_scope(filter_scope: str = "ranking", scope_filter=None):
                          'and passage prior span every shard; use a single-GPU engine (HippoRAGEngine) for scoped queries')
 
 
+def serve_seeds_scope(stages, filter_scope: str = "ranking", scope_filter=None) -> bool:
+    """True when a multi-GPU retriever serves this call in the "seeds" scope: its shard engine has the fact sources
+    (build_shard_engine(fact_sources=)).  Without them the request is refused exactly as refuse_seeds_scope does."""
+    if not getattr(stages, "has_fact_sources", False):
+        refuse_seeds_scope(filter_scope, scope_filter)
+        return False
+    from .engine import FILTER_SCOPES
+    if filter_scope not in FILTER_SCOPES:
+        raise ValueError(f"filter_scope={filter_scope!r}: one of {FILTER_SCOPES} expected")
+    return filter_scope == "seeds" or scope_filter is not None
+
+
 def merge_ranked(idx_parts, val_parts, k: int, topk):
     """Merge per-shard top-k lists (each sorted score desc, id desc; shard id ranges ascending in rank
     order) into the global top-k under the same rule.  Reversed and concatenated in rank order, "later
@@ -392,11 +414,14 @@ class ShardedRetriever:
         return self._bufs[batch]
 
     def score_facts(self, q_fact, k: int = 5, scope_filter=None):
-        """Global (fact ids int32 [B, k], min-max normalised scores fp32 [B, k]), replicated."""
-        refuse_seeds_scope(scope_filter=scope_filter)
+        """Global (fact ids int32 [B, k], min-max normalised scores fp32 [B, k]), replicated.
+        scope_filter: the GLOBAL doc filter of the "seeds" scope -- the top k among the facts of the allowed passages,
+        normalised over them (= HippoRAGEngine.score_facts(scope_filter=); needs the shard engine's fact sources)."""
+        scoped = serve_seeds_scope(getattr(self, "st", None), scope_filter=scope_filter)
         torch = _td()[0]
         c = self.comm
-        idx, val, mn, mx = self.st.shard_score_facts(q_fact, k)
+        idx, val, mn, mx = (self.st.shard_score_facts(q_fact, k, scope_filter=scope_filter) if scoped
+                            else self.st.shard_score_facts(q_fact, k))
         idx_all, val_all = c.all_gather(idx), c.all_gather(val)
         c.all_reduce(mn, "min")
         c.all_reduce(mx, "max")
@@ -416,13 +441,24 @@ class ShardedRetriever:
         clipped scores on (include/hrag.h: "never return clipped scores"); it costs one host read per batch --
         a timing loop passes False and checks the flags afterwards.
         doc_filter: the GLOBAL doc filter (engine.doc_filter_words forms, over all passages); every shard ranks only the
-        allowed passages of its slice, the merge puts a shard's -1 slots after every real entry."""
-        refuse_seeds_scope(filter_scope)
+        allowed passages of its slice, the merge puts a shard's -1 slots after every real entry.
+        filter_scope="seeds": the passage prior and the DPR fallback normalised over the allowed passages of every shard
+        (= HippoRAGEngine.retrieve(filter_scope="seeds"); the kept facts from score_facts(scope_filter=))."""
+        scoped = serve_seeds_scope(getattr(self, "st", None), filter_scope)
+        if scoped:
+            from .engine import check_filter_scope
+            check_filter_scope(filter_scope, doc_filter)
         st, c = self.st, self.comm
         fkw = {} if doc_filter is None else {"doc_filter": doc_filter}
         b = q_pass.shape[0]
         lay, bufs = self._state(b)
-        mn, mx = st.shard_passage_scores(q_pass)
+        if scoped:      # the allowed min / max over every shard, the owned rows rewritten, their min / max over every shard
+            amn, amx = st.shard_passage_scores(q_pass, scope_filter=doc_filter)
+            c.all_reduce(amn, "min")
+            c.all_reduce(amx, "max")
+            mn, mx = st.shard_mask_prior(amn, amx, doc_filter)
+        else:
+            mn, mx = st.shard_passage_scores(q_pass)
         c.all_reduce(mn, "min")
         c.all_reduce(mx, "max")
         sv, sw, sc, flags = st.seeds(kept_idx, kept_score, kept_count, link_top_k)
@@ -571,7 +607,8 @@ class NativeShardedRetriever:
         check(st)
 
     def score_facts(self, q_fact, k: int = 5, scope_filter=None):
-        refuse_seeds_scope(scope_filter=scope_filter)
+        """scope_filter: hrag_shard_score_facts_all_scoped with the global filter."""
+        scoped = serve_seeds_scope(getattr(self, "st", None), scope_filter=scope_filter)
         torch = _td()[0]
         from .engine import _stream
         q = self.st.e._q(q_fact)
@@ -580,16 +617,25 @@ class NativeShardedRetriever:
         idx = torch.empty((b, k), dtype=torch.int32, device=self.st.device)
         val = torch.empty((b, k), dtype=torch.float32, device=self.st.device)
         self._regions = [ws]
-        self._call(self._lib.hrag_shard_score_facts_all, self.st.h, ctypes.byref(self._c), q.data_ptr(), b, k, ws.data_ptr(),
-                   ws.numel(), idx.data_ptr(), val.data_ptr(), _stream())
+        args = (self.st.h, ctypes.byref(self._c), q.data_ptr(), b, k, ws.data_ptr(), ws.numel(), idx.data_ptr(),
+                val.data_ptr(), _stream())
+        if scoped:
+            from .engine import doc_filter_words
+            fw, fld = doc_filter_words(scope_filter, self.st.e.n_passages, b, self.st.device)
+            self._call(self._lib.hrag_shard_score_facts_all_scoped, *args, fw.data_ptr(), fld)
+        else:
+            self._call(self._lib.hrag_shard_score_facts_all, *args)
         return idx, val
 
     def retrieve(self, q_pass, kept_idx, kept_score, kept_count, *, link_top_k=5, damping=0.5, passage_node_weight=0.05,
                  ppr_iters=20, k=200, ppr_tol=0.0, ppr_max_iters=0, check_saturation=True, doc_filter=None,
                  filter_scope: str = "ranking"):
         """Same contract as ShardedRetriever.retrieve: (doc ids, doc scores, flags[, residual, sweeps used]);
-        doc_filter: hrag_shard_retrieve_filtered with the global filter."""
-        refuse_seeds_scope(filter_scope)
+        doc_filter: hrag_shard_retrieve_filtered with the global filter (filter_scope="seeds": hrag_shard_retrieve_scoped)."""
+        scoped = serve_seeds_scope(getattr(self, "st", None), filter_scope)
+        if scoped:
+            from .engine import check_filter_scope
+            check_filter_scope(filter_scope, doc_filter)
         torch = _td()[0]
         from .engine import _stream
         q = self.st.e._q(q_pass)
@@ -618,7 +664,8 @@ class NativeShardedRetriever:
         else:
             from .engine import doc_filter_words
             fw, fld = doc_filter_words(doc_filter, self.st.e.n_passages, b, dev)
-            self._call(self._lib.hrag_shard_retrieve_filtered, *args, fw.data_ptr(), fld)
+            fn = self._lib.hrag_shard_retrieve_scoped if scoped else self._lib.hrag_shard_retrieve_filtered
+            self._call(fn, *args, fw.data_ptr(), fld)
         if check_saturation and bool((flags & 8).any()):
             raise RuntimeError("fp8 PPR state saturated on a row shard (HRAG_FLAG_FP8_SATURATED): a static scale bound "
                                "was violated; use the replica / hybrid mode for this batch")
@@ -646,10 +693,12 @@ class HybridRetriever:
         self.sim, self.ppr, self.comm, self.pshards = sim, ppr, comm, list(pshards)
 
     def score_facts(self, q_fact, k: int = 5, scope_filter=None):
-        refuse_seeds_scope(scope_filter=scope_filter)
+        """scope_filter: the "seeds" scope's phase A over the embedding shards (as ShardedRetriever.score_facts)."""
+        scoped = serve_seeds_scope(getattr(self, "sim", None), scope_filter=scope_filter)
         torch = _td()[0]
         c = self.comm
-        idx, val, mn, mx = self.sim.shard_score_facts(q_fact, k)
+        idx, val, mn, mx = (self.sim.shard_score_facts(q_fact, k, scope_filter=scope_filter) if scoped
+                            else self.sim.shard_score_facts(q_fact, k))
         idx_all, val_all = c.all_gather(idx), c.all_gather(val)
         c.all_reduce(mn, "min")
         c.all_reduce(mx, "max")
@@ -666,8 +715,12 @@ class HybridRetriever:
 
     def retrieve(self, q_pass, kept_idx, kept_score, kept_count, **kw):
         """q_pass / kept_*: the GLOBAL batch (replicated); returns this rank's RetrieveOutput for its B / N queries.
-        kw["doc_filter"] (optional): the global batch's filter; a per-query one is cut to this rank's rows."""
-        refuse_seeds_scope(kw.pop("filter_scope", "ranking"))
+        kw["doc_filter"] (optional): the global batch's filter; a per-query one is cut to this rank's rows.
+        kw["filter_scope"]="seeds": hrag_retrieve_scored_scoped on this rank's rows (the prior masked over the allowed
+        passages of the all-to-all'd score rows); needs the fact sources on the embedding shard, like score_facts."""
+        scope = kw.pop("filter_scope", "ranking")
+        if serve_seeds_scope(getattr(self, "sim", None), scope):
+            kw["filter_scope"] = scope
         torch = _td()[0]
         c, w = self.comm, self.comm.world
         b = q_pass.shape[0]
@@ -685,13 +738,15 @@ class HybridRetriever:
 
 def run_local_shards(world: int, sidx: "ShardedIndex", pass_emb, fact_emb, q_fact, q_pass, retrieve_kw: dict,
                      groups: int, device, max_topk: int, filter_fn=None, timings: Optional[dict] = None,
-                     sell_seg_len: int = 0, native: bool = False):
+                     sell_seg_len: int = 0, native: bool = False, fact_sources=None):
     """All `world` shards of `sidx` as threads of THIS process on ONE device, meeting at barriers (LocalComm) and
     sharing the three e4m3 state buffers: the emulated gather SURVEY.md 8(e) prescribes.  Returns rank 0's
     (fact idx, fact score, doc idx, doc score, flags) as numpy arrays after checking that every rank computed the
     same replicated result.  Used by tests/test_gpu_shard.py and by `bench.py --config cfg4local` (the parity-checked
     form of BASELINE configs[3] when only one GPU is at hand).  native: the host loop inside the library
-    (NativeShardedRetriever: hrag_shard_retrieve calling back into LocalComm from every shard thread)."""
+    (NativeShardedRetriever: hrag_shard_retrieve calling back into LocalComm from every shard thread).
+    fact_sources: (row_ptr, passage_pos) for build_shard_engine; with retrieve_kw["filter_scope"] == "seeds" phase A
+    then takes scope_filter=retrieve_kw["doc_filter"]."""
     import threading
     torch = _td()[0]
     from .engine import ShardStages
@@ -702,14 +757,14 @@ def run_local_shards(world: int, sidx: "ShardedIndex", pass_emb, fact_emb, q_fac
         try:
             torch.cuda.set_device(device)
             eng = build_shard_engine(sidx, pass_emb, fact_emb, rank, max_batch=b, max_topk=max_topk,
-                                     sell_seg_len=sell_seg_len)
+                                     sell_seg_len=sell_seg_len, fact_sources=fact_sources)
             rs = (NativeShardedRetriever if native else ShardedRetriever)(ShardStages(eng), LocalComm(rank, world, shared),
                                                                           groups=groups)
             torch.cuda.synchronize()
             shared["_barrier"].wait()
             t0 = time.perf_counter()
-            idx, sc = rs.score_facts(q_fact, k=5)
-            cnt = torch.full((b,), 5, dtype=torch.int32, device=device)
+            idx, sc = rs.score_facts(q_fact, k=5, **_phase_a_scope(retrieve_kw))
+            cnt = _kept_count(idx, retrieve_kw)
             if filter_fn is not None:
                 idx, sc, cnt = filter_fn(idx, sc)
             d_idx, d_sc, flags = rs.retrieve(q_pass, idx, sc, cnt, **retrieve_kw)[:3]   # ppr_tol > 0: + (residual, sweeps)
@@ -739,6 +794,20 @@ def run_local_shards(world: int, sidx: "ShardedIndex", pass_emb, fact_emb, q_fac
     return results[0]
 
 
+def _phase_a_scope(retrieve_kw: dict) -> dict:
+    """score_facts' keyword for phase B's scope: the "seeds" scope takes phase A from the same doc filter."""
+    return {"scope_filter": retrieve_kw["doc_filter"]} if retrieve_kw.get("filter_scope") == "seeds" else {}
+
+
+def _kept_count(idx, retrieve_kw: dict):
+    """Facts kept per query: all 5 candidates -- in the "seeds" scope the valid ones (a row with fewer allowed facts
+    ends in -1)."""
+    torch = _td()[0]
+    if retrieve_kw.get("filter_scope") == "seeds":
+        return (idx >= 0).sum(1).to(torch.int32)
+    return torch.full((idx.shape[0],), 5, dtype=torch.int32, device=idx.device)
+
+
 def build_ppr_engine(graph, passage_vertex, subj_vertex, obj_vertex, num_chunks, dim: int, max_batch: int,
                      max_topk: int, flags: int = 0):
     """The PPR side of the hybrid mode: the whole graph + the fact lookup arrays, NO embeddings."""
@@ -748,10 +817,11 @@ def build_ppr_engine(graph, passage_vertex, subj_vertex, obj_vertex, num_chunks,
 
 
 def run_local_hybrid(world: int, kg_arrays: dict, sidx: "ShardedIndex", pass_emb, fact_emb, q_fact, q_pass,
-                     retrieve_kw: dict, device, max_topk: int, timings: Optional[dict] = None):
+                     retrieve_kw: dict, device, max_topk: int, timings: Optional[dict] = None, fact_sources=None):
     """The hybrid mode with all `world` ranks as threads of this process on ONE device (LocalComm).  kg_arrays: the
     ORIGINAL index (csr, passage_vertex, subj_vertex, obj_vertex, num_chunks) for the PPR engines.  Returns, in
-    query order, (fact idx, fact score) of the global batch and the concatenated per-rank (doc idx, doc score, flags)."""
+    query order, (fact idx, fact score) of the global batch and the concatenated per-rank (doc idx, doc score, flags).
+    fact_sources: as in run_local_shards (the embedding shards' fact -> source-passage table)."""
     import threading
     torch = _td()[0]
     from .engine import ShardStages
@@ -762,7 +832,8 @@ def run_local_hybrid(world: int, kg_arrays: dict, sidx: "ShardedIndex", pass_emb
     def worker(rank):
         try:
             torch.cuda.set_device(device)
-            sim = build_shard_engine(sidx, pass_emb, fact_emb, rank, max_batch=b, max_topk=max_topk)
+            sim = build_shard_engine(sidx, pass_emb, fact_emb, rank, max_batch=b, max_topk=max_topk,
+                                     fact_sources=fact_sources)
             ppr = build_ppr_engine(kg_arrays["csr"], kg_arrays["passage_vertex"], kg_arrays["subj_vertex"],
                                    kg_arrays["obj_vertex"], kg_arrays["num_chunks"], sim.dim, max_batch=bn,
                                    max_topk=max_topk)
@@ -770,8 +841,8 @@ def run_local_hybrid(world: int, kg_arrays: dict, sidx: "ShardedIndex", pass_emb
             torch.cuda.synchronize()
             shared["_barrier"].wait()
             t0 = time.perf_counter()
-            idx, sc = hy.score_facts(q_fact, k=5)
-            cnt = torch.full((b,), 5, dtype=torch.int32, device=device)
+            idx, sc = hy.score_facts(q_fact, k=5, **_phase_a_scope(retrieve_kw))
+            cnt = _kept_count(idx, retrieve_kw)
             out = hy.retrieve(q_pass, idx, sc, cnt, **retrieve_kw)
             torch.cuda.synchronize()
             if timings is not None and rank == 0:

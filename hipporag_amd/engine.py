@@ -761,8 +761,10 @@ class HippoRAGEngine:
         check(self._lib.hrag_shard_layout_query(self._handle, batch, groups, C.byref(lay)))
         return lay
 
-    def shard_score_facts(self, q_fact, k: int = 5):
-        """Local phase A: (global fact ids [B,k], RAW scores [B,k], local min [B], local max [B])."""
+    def shard_score_facts(self, q_fact, k: int = 5, scope_filter=None):
+        """Local phase A: (global fact ids [B,k], RAW scores [B,k], local min [B], local max [B]).
+        scope_filter: the GLOBAL doc filter (doc_filter_words forms over every passage) -- the "seeds" scope: only the
+        owned facts with an allowed source, min / max over them (hrag_shard_score_facts_scoped; set_fact_sources)."""
         torch = _torch()
         q = self._q(q_fact)
         b = q.shape[0]
@@ -770,19 +772,41 @@ class HippoRAGEngine:
         val = self._empty((b, k), torch.float32)
         mn = self._empty((b,), torch.float32)
         mx = self._empty((b,), torch.float32)
-        check(self._lib.hrag_shard_score_facts(self._handle, q.data_ptr(), b, k, idx.data_ptr(), val.data_ptr(),
-                                               mn.data_ptr(), mx.data_ptr(), _stream()))
+        args = (self._handle, q.data_ptr(), b, k, idx.data_ptr(), val.data_ptr(), mn.data_ptr(), mx.data_ptr(), _stream())
+        if scope_filter is None:
+            check(self._lib.hrag_shard_score_facts(*args))
+        else:
+            fw, fld = doc_filter_words(scope_filter, self.n_passages, b, self.device)
+            check(self._lib.hrag_shard_score_facts_scoped(*args, fw.data_ptr(), fld))
         return idx, val, mn, mx
 
-    def shard_passage_scores(self, q_pass):
+    def shard_passage_scores(self, q_pass, scope_filter=None):
+        """(local min [B], local max [B]) of the owned passage scores; scope_filter (the GLOBAL doc filter): over the
+        allowed owned passages only (hrag_shard_passage_scores_scoped; +inf / -inf where there are none)."""
         torch = _torch()
         q = self._q(q_pass)
         b = q.shape[0]
         mn = self._empty((b,), torch.float32)
         mx = self._empty((b,), torch.float32)
-        check(self._lib.hrag_shard_passage_scores(self._handle, q.data_ptr(), b, mn.data_ptr(), mx.data_ptr(),
-                                                  _stream()))
+        args = (self._handle, q.data_ptr(), b, mn.data_ptr(), mx.data_ptr(), _stream())
+        if scope_filter is None:
+            check(self._lib.hrag_shard_passage_scores(*args))
+        else:
+            fw, fld = doc_filter_words(scope_filter, self.n_passages, b, self.device)
+            check(self._lib.hrag_shard_passage_scores_scoped(*args, fw.data_ptr(), fld))
         return mn, mx
+
+    def shard_mask_prior(self, mn, mx, scope_filter):
+        """The "seeds" prior on the owned passages from the all-reduced allowed min / max (hrag_shard_mask_prior):
+        returns the local (min [B], max [B]) of the rewritten scores, to be all-reduced in turn."""
+        torch = _torch()
+        b = mn.shape[0]
+        mn_out = self._empty((b,), torch.float32)
+        mx_out = self._empty((b,), torch.float32)
+        fw, fld = doc_filter_words(scope_filter, self.n_passages, b, self.device)
+        check(self._lib.hrag_shard_mask_prior(self._handle, mn.data_ptr(), mx.data_ptr(), b, mn_out.data_ptr(),
+                                              mx_out.data_ptr(), _stream(), fw.data_ptr(), fld))
+        return mn_out, mx_out
 
     def shard_prior_stats(self, mn, mx, passage_node_weight: float, flags):
         torch = _torch()
@@ -1057,11 +1081,18 @@ class ShardStages(EngineStages):
     def new_state(self, lay):           # one e4m3 state buffer, zero (row V of every group must stay zero)
         return _torch().zeros((lay.state_bytes,), dtype=_torch().uint8, device=self.device)
 
-    def shard_score_facts(self, q_fact, k):
-        return self.e.shard_score_facts(q_fact, k)
+    @property
+    def has_fact_sources(self) -> bool:     # the "seeds" scope can be served (set_fact_sources on the shard engine)
+        return self.e.has_fact_sources
 
-    def shard_passage_scores(self, q_pass):
-        return self.e.shard_passage_scores(q_pass)
+    def shard_score_facts(self, q_fact, k, scope_filter=None):
+        return self.e.shard_score_facts(q_fact, k, scope_filter)
+
+    def shard_passage_scores(self, q_pass, scope_filter=None):
+        return self.e.shard_passage_scores(q_pass, scope_filter)
+
+    def shard_mask_prior(self, mn, mx, scope_filter):
+        return self.e.shard_mask_prior(mn, mx, scope_filter)
 
     def shard_prior_stats(self, mn, mx, weight, flags):
         return self.e.shard_prior_stats(mn, mx, weight, flags)

@@ -63,7 +63,10 @@ extern "C" {
  *        hrag_shard_retrieve_filtered;
  *        later in 0.8 (detect by the symbol): the scoped doc filter -- hrag_engine_set_fact_sources,
  *        hrag_fact_mask_from_docs, hrag_score_facts_scoped, hrag_retrieve_scoped, hrag_retrieve_scored_scoped,
- *        hrag_dense_retrieve_scoped. */
+ *        hrag_dense_retrieve_scoped;
+ *        later in 0.8 (detect by the symbol): the scoped doc filter on row shards -- hrag_shard_score_facts_scoped,
+ *        hrag_shard_passage_scores_scoped, hrag_shard_mask_prior, hrag_shard_score_facts_all_scoped,
+ *        hrag_shard_retrieve_scoped (hrag_engine_set_fact_sources then accepts a row-shard engine). */
 #define HRAG_VERSION_MAJOR 0
 #define HRAG_VERSION_MINOR 8
 
@@ -493,7 +496,8 @@ hrag_status hrag_dense_retrieve_filtered(hrag_engine *e, const uint16_t *q_pass_
  * sources of fact f are passage_pos[row_ptr[f] .. row_ptr[f + 1]), passage positions in [0, n_passages).  n_facts must
  * be the engine's fact count.  Part of the shared index: call it on a root engine before any workspace is created
  * (HRAG_EINVAL after); workspaces created later borrow the table and get their own fact-mask buffer.  Calling it again
- * (still without workspaces) replaces the table.  An engine that never calls it allocates nothing for it. */
+ * (still without workspaces) replaces the table.  An engine that never calls it allocates nothing for it.  A row-shard
+ * engine takes the same global table and keeps the rows of its owned facts (hrag_shard_score_facts_scoped). */
 hrag_status hrag_engine_set_fact_sources(hrag_engine *e, const int64_t *row_ptr, const int32_t *passage_pos,
                                          int64_t n_facts, int64_t nnz);
 
@@ -731,6 +735,11 @@ hrag_status hrag_stage_doc_scores(hrag_engine *e, const float *x_dev, const doub
  *             n_steps x n_groups x hrag_shard_ppr_sweep -> exchange group g of state[*exchange_out]
  *                 (n_steps = ppr_iters without a tolerance; measuring steps: est all-reduce + hrag_shard_ppr_decide)
  *             hrag_shard_finish -> gather + merge the local top-k lists
+ * Per batch, "seeds" scope (the scoped doc filter above; every shard passes the same GLOBAL filter):
+ *             hrag_shard_score_facts_scoped -> gather + merge candidates, min / max all-reduce (as unscoped)
+ *             hrag_shard_passage_scores_scoped -> all-reduce MIN / MAX of the allowed min / max
+ *             hrag_shard_mask_prior(those) -> all-reduce MIN / MAX of its min / max; then everything from
+ *                 hrag_stage_seeds on as above, with these min / max and hrag_shard_finish_filtered
  * ------------------------------------------------------------------------------------------ */
 #define HRAG_FLAG_FP8_SATURATED 8
 
@@ -815,6 +824,34 @@ hrag_status hrag_shard_finish_filtered(hrag_engine *e, const float *min_dev, con
                                        float *residual_out_dev, int32_t *iters_out_dev, hrag_stream stream,
                                        const uint32_t *filter_dev, int64_t filter_ld_words);
 
+/* The "seeds" scope on a row shard (the scoped doc filter above, split where its statistics cross the shards).  The
+ * filter is the GLOBAL one (filter_ld_words as in hrag_retrieve_filtered; NULL: HRAG_EINVAL).  The result of the recipe
+ * above equals hrag_score_facts_scoped / hrag_retrieve_scoped of the unsharded engine bit for bit.
+ * hrag_engine_set_fact_sources on a row shard takes the same GLOBAL table; the shard keeps the rows of its owned facts
+ * (passage positions stay global).  The single-engine scoped calls return HRAG_EINVAL on a row shard.
+ *   hrag_shard_score_facts_scoped     hrag_shard_score_facts among the owned facts that have an allowed source passage:
+ *                                     RAW scores (global fact ids), min / max over those facts only; a shard without
+ *                                     any (or without fact rows) returns -1 / 0 and +inf / -inf, the all-reduce's
+ *                                     neutral values.  Needs hrag_engine_set_fact_sources.
+ *   hrag_shard_passage_scores_scoped  the owned passage scores (kept inside the engine) + their min / max over the
+ *                                     ALLOWED owned passages (none: +inf / -inf).
+ *   hrag_shard_mask_prior             min_dev / max_dev = the all-reduced values of the previous step: rewrites the
+ *                                     owned scores as hrag_retrieve_scoped's prior (allowed: (s - min) / (max - min), a
+ *                                     zero range gives 1; others: 0) and returns the min / max of the rewritten rows
+ *                                     (no owned passage: +inf / -inf).  Their all-reduce is what hrag_shard_prior_stats,
+ *                                     hrag_shard_ppr_begin and hrag_shard_finish_filtered take.  min_out / max_out may
+ *                                     be min_dev / max_dev. */
+hrag_status hrag_shard_score_facts_scoped(hrag_engine *e, const uint16_t *q_fact_dev, int32_t batch, int32_t k,
+                                          int32_t *idx_out_dev, float *score_out_dev, float *min_out_dev,
+                                          float *max_out_dev, hrag_stream stream, const uint32_t *filter_dev,
+                                          int64_t filter_ld_words);
+hrag_status hrag_shard_passage_scores_scoped(hrag_engine *e, const uint16_t *q_pass_dev, int32_t batch,
+                                             float *min_out_dev, float *max_out_dev, hrag_stream stream,
+                                             const uint32_t *filter_dev, int64_t filter_ld_words);
+hrag_status hrag_shard_mask_prior(hrag_engine *e, const float *min_dev, const float *max_dev, int32_t batch,
+                                  float *min_out_dev, float *max_out_dev, hrag_stream stream, const uint32_t *filter_dev,
+                                  int64_t filter_ld_words);
+
 /* ------------------------------------------------------------------------------------------
  * ONE CALL PER PHASE on a row shard (round 6).  The steps above leave the order of the local steps, the exchanges and the
  * all-reduces to the host (hipporag_amd/dist.py ShardedRetriever is that host loop, ~100 lines per phase).  The two
@@ -886,6 +923,22 @@ hrag_status hrag_shard_retrieve_filtered(hrag_engine *e, const hrag_comm *comm, 
                                          int32_t *doc_idx_out_dev, float *doc_score_out_dev, int32_t *flags_out_dev,
                                          float *residual_out_dev, int32_t *iters_out_dev, hrag_stream stream,
                                          const uint32_t *filter_dev, int64_t filter_ld_words);
+/* The drivers in the "seeds" scope (the recipe above inside the library; same arguments as hrag_shard_score_facts_all /
+ * hrag_shard_retrieve_filtered, the same workspace; NULL filter: HRAG_EINVAL) = hrag_score_facts_scoped /
+ * hrag_retrieve_scoped of the unsharded engine. */
+hrag_status hrag_shard_score_facts_all_scoped(hrag_engine *e, const hrag_comm *comm, const uint16_t *q_fact_dev,
+                                              int32_t batch, int32_t k, void *workspace_dev, int64_t workspace_bytes,
+                                              int32_t *idx_out_dev, float *score_out_dev, hrag_stream stream,
+                                              const uint32_t *filter_dev, int64_t filter_ld_words);
+hrag_status hrag_shard_retrieve_scoped(hrag_engine *e, const hrag_comm *comm, const uint16_t *q_pass_dev, int32_t batch,
+                                       const int32_t *kept_idx_dev, const float *kept_score_dev,
+                                       const int32_t *kept_count_dev, int32_t kf, int32_t link_top_k, float damping,
+                                       float passage_node_weight, int32_t ppr_iters, int32_t ppr_max_iters,
+                                       float ppr_tol, int32_t k, int32_t n_groups, void *state0_dev, void *state1_dev,
+                                       void *state2_dev, void *workspace_dev, int64_t workspace_bytes,
+                                       int32_t *doc_idx_out_dev, float *doc_score_out_dev, int32_t *flags_out_dev,
+                                       float *residual_out_dev, int32_t *iters_out_dev, hrag_stream stream,
+                                       const uint32_t *filter_dev, int64_t filter_ld_words);
 
 /* Index update with the embeddings staying on the device (incremental index() / delete(), HippoRAG.py:262-411:
  * the reference re-reads everything from its stores in prepare_retrieval_objects): compose the embedding
