@@ -64,6 +64,18 @@ __device__ __forceinline__ uint64_t rank_key(float score, uint32_t idx) {
 // max that propagates NaN (fmaxf skips it): a tile key of the fused top-k under which a tile holding a NaN ranks first
 __device__ __forceinline__ float nan_max(float a, float b) { return (b > a || b != b) ? b : a; }
 
+// One entry of the reset vector as the PPR may read it: NaN, negative and zero become +0 (HippoRAG.py:1735 sanitises
+// the reset vector before igraph sees it; -0 -> +0 only makes the bits unique)
+__device__ __forceinline__ float sanitise_reset(float v) { return v > 0.f ? v : 0.f; }
+
+// One entry of the passage prior, the formula of every kernel that forms it (HippoRAG.py:1626-1635):
+// minmax(s) * weight with minmax = (s - mn) / (mx - mn), a zero range giving 1 (misc_utils.py:130-139), IEEE division
+// like numpy; then sanitised.  NaN / +-inf scores give NaN here ((inf - mn) / inf), i.e. a prior of 0
+__device__ __forceinline__ float prior_entry(float s, float mn, float mx, float weight) {
+    const float range = mx - mn;
+    return sanitise_reset((range == 0.f ? 1.f : __fdiv_rn(s - mn, range)) * weight);
+}
+
 // Convergence contract: the running per-query maximum est[q] (float bits) is raised with atomicMax by whoever holds a
 // larger value.  The pre-check must see the other workgroups' updates -- a cached plain load keeps reading the
 // initial 0 and every lane of every wavefront would issue its atomic (measured: +0.3 ms on a 1 ms sweep) -- so it is
@@ -175,9 +187,11 @@ struct Ppr16Args {
 hrag_status launch_ppr16_sweep(const Ppr16Args &a, int mode, int n_slabs, int nt, bool main_only,
                                hipStream_t s);
 hrag_status launch_ppr16_init(const Ppr16Args &a, int n_slabs, hipStream_t s);  // y = f16(v)
-hrag_status launch_ppr16_scale(const float *mn, const float *mx, const float *ssum, int64_t n_passages,
+// qscale[q] from the sum of the sanitised passage prior of scores fp32 [B, ld] + the seeds; part: kP8PriorSplit * batch
+// doubles of scratch
+hrag_status launch_ppr16_scale(const float *scores, int64_t ld, int64_t n_passages, const float *mn, const float *mx,
                                float passage_weight, const float *seed_w, const int32_t *seed_cnt,
-                               const int32_t *flags, int32_t batch, float *qscale, hipStream_t s);
+                               const int32_t *flags, int32_t batch, double *part, float *qscale, hipStream_t s);
 // bc: columns per teleport row (64 on the fp16 path, BP on the small-batch path); qscale may be null
 // row_offset / n_rows: the owned vertex range (row_slot is indexed by LOCAL row); n_passages = owned passages
 hrag_status launch_ppr16_seed_rows(const int32_t *seed_vtx, const float *seed_w, const int32_t *seed_cnt,
@@ -474,7 +488,7 @@ hrag_status launch_row_topk(const float *scores, int32_t batch, int64_t n, int64
                             float *mn_out, float *mx_out, hipStream_t s, void *ws = nullptr,
                             size_t ws_bytes = 0, const TopkMask *mask = nullptr);
 hrag_status launch_row_minmax(const float *scores, int32_t batch, int64_t n, int64_t ld,
-                              float *mn_out, float *mx_out, hipStream_t s, float *sum_out = nullptr);
+                              float *mn_out, float *mx_out, hipStream_t s);
 // the passage prior of a scoped call (include/hrag.h, hrag_retrieve_scoped): every row of `scores` is rewritten in place,
 // an allowed element to its min-max normalised value over the row's ALLOWED elements (a zero range gives 1), every other
 // element to 0.  The row min / max of the result are then 0 / 1 (or equal), so the prior kernels' own min-max is exact

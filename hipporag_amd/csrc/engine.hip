@@ -31,7 +31,7 @@ static void workspace_ptrs(hrag_engine *e, std::vector<void **> &out) {
                      (void **)&e->d_seed_vtx, (void **)&e->d_seed_cnt, (void **)&e->d_flags, (void **)&e->d_seed_w,
                      (void **)&e->d_colsum_partial, (void **)&e->d_sums, (void **)&e->d_partial16, (void **)&e->d_h16[0],
                      (void **)&e->d_h16[1], (void **)&e->d_h16[2], (void **)&e->d_h16[3], (void **)&e->d_tele16,
-                     (void **)&e->d_row_slot, (void **)&e->d_qscale, (void **)&e->d_ssum, (void **)&e->d_tele_sv,
+                     (void **)&e->d_row_slot, (void **)&e->d_qscale, (void **)&e->d_prior_sum, (void **)&e->d_tele_sv,
                      (void **)&e->d_partial_sv, (void **)&e->d_topk_ws, (void **)&e->d_topk_large, (void **)&e->d_R8, (void **)&e->d_rho8,
                      (void **)&e->d_partial8, (void **)&e->d_fused_ws, (void **)&e->d_mn_f, (void **)&e->d_mx_f,
                      (void **)&e->d_fused_sel, (void **)&e->d_xp8, (void **)&e->d_colmask, (void **)&e->d_stagep,
@@ -592,7 +592,7 @@ static hrag_status alloc_workspace(hrag_engine *e) {
     }
     if (e->want_sell && !(e->want_f16 || e->f8_ready)) {   // small-batch-only engine: per-query scale of the fp16 state
         HRAG_TRY(dev_alloc(&e->d_qscale, B));
-        HRAG_TRY(dev_alloc(&e->d_ssum, B));
+        HRAG_TRY(dev_alloc(&e->d_prior_sum, (int64_t)kP8PriorSplit * B));
     }
     if (e->want_f16 || e->f8_ready) {
         // teleport rows of the fp16 and fp8 paths: the owned passages, then the seed rows (fp32, 64-query slabs)
@@ -601,7 +601,7 @@ static hrag_status alloc_workspace(hrag_engine *e) {
         HRAG_TRY(dev_alloc(&e->d_tele16, (int64_t)ns * e->tele16_rows * 64));
         HRAG_HIP_TRY(hipMemset(e->d_tele16, 0, (size_t)ns * e->tele16_rows * 64 * sizeof(float)));
         HRAG_TRY(dev_alloc(&e->d_qscale, B));
-        HRAG_TRY(dev_alloc(&e->d_ssum, B));
+        HRAG_TRY(dev_alloc(&e->d_prior_sum, (int64_t)kP8PriorSplit * B));
     }
     if (e->want_f16) {
         const int ns = n_slabs64(B);
@@ -1412,8 +1412,7 @@ static hrag_status retrieve_impl(hrag_engine *e, const uint16_t *q_pass, const f
     // and every prior kernel's own normalisation is exact identity on these rows (include/hrag.h)
     if (scoped) HRAG_TRY(launch_masked_prior(e->d_spass, batch, e->n_passages, e->ld_p, *mask, s));
     const bool sv_half = sv && use_sv_half(e, ppr_iters, damping);
-    HRAG_TRY(launch_row_minmax(e->d_spass, batch, e->n_passages, e->ld_p, e->d_mn_p, e->d_mx_p, s,
-                               (f16 || sv_half) ? e->d_ssum : nullptr));
+    HRAG_TRY(launch_row_minmax(e->d_spass, batch, e->n_passages, e->ld_p, e->d_mn_p, e->d_mx_p, s));
     if (prof) HRAG_HIP_TRY(hipEventRecord(e->ev[EV_SIM], s));
     // reset vector: entity seeds + passage prior (HippoRAG.py:1574-1638)
     if (e->d_subj) {
@@ -1436,8 +1435,8 @@ static hrag_status retrieve_impl(hrag_engine *e, const uint16_t *q_pass, const f
     } else if (f16) {
         // v is scaled per query by a power of two so that every iterate fits fp16 (ppr16.hip); the seeds
         // become extra teleport rows, i.e. v is one array that every sweep reads identically
-        HRAG_TRY(launch_ppr16_scale(e->d_mn_p, e->d_mx_p, e->d_ssum, e->n_passages, passage_node_weight,
-                                    e->d_seed_w, e->d_seed_cnt, e->d_flags, batch, e->d_qscale, s));
+        HRAG_TRY(launch_ppr16_scale(e->d_spass, e->ld_p, e->n_passages, e->d_mn_p, e->d_mx_p, passage_node_weight,
+                                    e->d_seed_w, e->d_seed_cnt, e->d_flags, batch, e->d_prior_sum, e->d_qscale, s));
         HRAG_TRY(launch_rows_to_slab(e->d_spass, e->ld_p, e->n_passages, batch, kMinMaxScale, e->d_mn_p,
                                      e->d_mx_p, passage_node_weight, e->d_flags, e->d_tele16, lay, s,
                                      e->tele16_rows, e->d_qscale));
@@ -1459,8 +1458,9 @@ static hrag_status retrieve_impl(hrag_engine *e, const uint16_t *q_pass, const f
         // fp16 state v carries the per-query power-of-two scale of ppr16.hip (every iterate fits fp16)
         const float *qs = nullptr;
         if (sv_half) {
-            HRAG_TRY(launch_ppr16_scale(e->d_mn_p, e->d_mx_p, e->d_ssum, e->n_passages, passage_node_weight,
-                                        e->d_seed_w, e->d_seed_cnt, e->d_flags, batch, e->d_qscale, s));
+            HRAG_TRY(launch_ppr16_scale(e->d_spass, e->ld_p, e->n_passages, e->d_mn_p, e->d_mx_p, passage_node_weight,
+                                        e->d_seed_w, e->d_seed_cnt, e->d_flags, batch, e->d_prior_sum,
+                                        e->d_qscale, s));
             qs = e->d_qscale;
         }
         HRAG_TRY(launch_ppr_sv_tele(e->d_spass, e->ld_p, e->n_passages, batch, e->d_mn_p, e->d_mx_p,

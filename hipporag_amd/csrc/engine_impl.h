@@ -190,7 +190,8 @@ struct hrag_engine {
     float *d_tele16 = nullptr;      // fp32 [n_slabs64][tele16_rows][64]: passages, then seed rows
     int64_t tele16_rows = 0;
     int32_t *d_row_slot = nullptr;  // [V] per-batch copy of d_row_to_tele with the seed rows patched in
-    float *d_qscale = nullptr, *d_ssum = nullptr;
+    float *d_qscale = nullptr;
+    double *d_prior_sum = nullptr;   // kP8PriorSplit * B partial sums of the prior (launch_ppr16_scale)
     // staged fp8 PPR (ppr8.hip): SELL-8 over the OWNED rows with the row-normalised values, fp32 residual on
     // the owned rows, three e4m3 state buffers; needs hrag_graph_desc.col_sum.  Serves hrag_retrieve for
     // batches > 64 on an unsharded engine and the hrag_shard_* entry points on a row shard.

@@ -2,8 +2,9 @@
 // reference hands vectors to run_ppr, HippoRAG.py:1709-1711) and the engine's PPR slab layout
 // [n_slabs][n][BC], with the element-wise stages of the path fused into the copy:
 //   rows_to_slab  kSanitize   : reset_prob NaN / negative -> 0              (HippoRAG.py:1735)
-//                 kMinMaxScale: passage_weights = minmax(dpr) * passage_node_weight
-//                               (utils/misc_utils.py:130-139, HippoRAG.py:1627-1633)
+//                 kMinMaxScale: passage_weights = minmax(dpr) * passage_node_weight, sanitised like the
+//                               rest of the reset vector (utils/misc_utils.py:130-139, HippoRAG.py:1627-1633,
+//                               :1735; common.h prior_entry)
 //   slab_to_rows              : doc_scores = pagerank[passage_node_idxs] with the final
 //                               normalisation sum(x) = 1 (HippoRAG.py:1745), or the normalised
 //                               DPR scores for queries on the DPR fallback (:467-469).
@@ -45,7 +46,7 @@ __global__ __launch_bounds__(256) void rows_to_slab_kernel(
             if (mode == kSanitize) {
                 v = (v != v || v < 0.f) ? 0.f : v;
             } else {
-                v = minmax_norm(v, mn[q], mx[q]) * scale;
+                v = prior_entry(v, mn[q], mx[q], scale);
                 if (qscale) v *= qscale[q];  // a power of two: exact
             }
         }

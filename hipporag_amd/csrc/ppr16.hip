@@ -365,19 +365,40 @@ __global__ __launch_bounds__(256) void ppr16_init_kernel(const Ppr16Args a) {
 
 // Per-query scale s_q (a power of two) such that sum(v_q) * s_q is in (2^14, 2^15]: every entry of
 // every iterate is then <= 2^15 < 65504 (the leaky iteration never gains mass).
-//   total_q = passage_node_weight * sum_p minmax(score_qp) + sum_j seed_w[q][j]
-__global__ void ppr16_scale_kernel(const float *mn, const float *mx, const float *ssum, int64_t n_passages,
-                                   float passage_weight, const float *seed_w, const int32_t *seed_cnt,
+//   total_q = sum_p prior_entry(score_qp) + sum_j seed_w[q][j]
+// The passage part is the sum of the very entries rows_to_slab / the sv teleport kernel write (sanitised), added in a
+// fixed order: ppr16_prior_sum_kernel's partials (grid (kP8PriorSplit, B), a strided slice each), then the final
+// kernel adds them in block order.  A closed form from the raw row sum would turn NaN / +-inf scores into a NaN total.
+__global__ __launch_bounds__(256) void ppr16_prior_sum_kernel(const float *__restrict__ scores, int64_t ld, int64_t n,
+                                                              const float *__restrict__ mn, const float *__restrict__ mx,
+                                                              float weight, const int32_t *__restrict__ flags,
+                                                              int32_t batch, double *__restrict__ part) {
+    __shared__ double red[256];
+    const int q = blockIdx.y, tid = threadIdx.x;
+    double sum = 0.0;
+    if (!(flags[q] & 1)) {
+        const float lo = mn[q], hi = mx[q];
+        const float *row = scores + (size_t)q * ld;
+        for (int64_t p = (int64_t)blockIdx.x * 256 + tid; p < n; p += (int64_t)kP8PriorSplit * 256)
+            sum += (double)prior_entry(row[p], lo, hi, weight);
+    }
+    red[tid] = sum;
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if (tid < st) red[tid] += red[tid + st];
+        __syncthreads();
+    }
+    if (tid == 0) part[(size_t)blockIdx.x * batch + q] = red[0];
+}
+
+__global__ void ppr16_scale_kernel(const double *part, const float *seed_w, const int32_t *seed_cnt,
                                    const int32_t *flags, int32_t batch, float *qscale) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= batch) return;
     double total = 0.0;
     if (!(flags[q] & 1)) {
-        const double range = (double)mx[q] - (double)mn[q];
-        const double norm_sum = range == 0.0 ? (double)n_passages
-                                             : ((double)ssum[q] - (double)n_passages * (double)mn[q]) / range;
-        total = (double)passage_weight * fmax(norm_sum, 0.0);
-        for (int j = 0; j < seed_cnt[q]; ++j) total += fmax((double)seed_w[q * kMaxSeeds + j], 0.0);
+        for (int b = 0; b < kP8PriorSplit; ++b) total += part[(size_t)b * batch + q];
+        for (int j = 0; j < seed_cnt[q]; ++j) total += (double)sanitise_reset(seed_w[q * kMaxSeeds + j]);
     }
     float s = 1.f;
     if (total > 0.0 && total < 1e300) {
@@ -460,11 +481,15 @@ hrag_status launch_ppr16_init(const Ppr16Args &a, int n_slabs, hipStream_t s) {
     return HRAG_OK;
 }
 
-hrag_status launch_ppr16_scale(const float *mn, const float *mx, const float *ssum, int64_t n_passages,
+hrag_status launch_ppr16_scale(const float *scores, int64_t ld, int64_t n_passages, const float *mn, const float *mx,
                                float passage_weight, const float *seed_w, const int32_t *seed_cnt,
-                               const int32_t *flags, int32_t batch, float *qscale, hipStream_t s) {
-    hipLaunchKernelGGL(ppr16_scale_kernel, dim3((unsigned)ceil_div(batch, 64)), dim3(64), 0, s, mn, mx,
-                       ssum, n_passages, passage_weight, seed_w, seed_cnt, flags, batch, qscale);
+                               const int32_t *flags, int32_t batch, double *part, float *qscale, hipStream_t s) {
+    if (batch == 0) return HRAG_OK;
+    hipLaunchKernelGGL(ppr16_prior_sum_kernel, dim3(kP8PriorSplit, (unsigned)batch), dim3(256), 0, s, scores, ld,
+                       n_passages, mn, mx, passage_weight, flags, batch, part);
+    HRAG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ppr16_scale_kernel, dim3((unsigned)ceil_div(batch, 64)), dim3(64), 0, s, part, seed_w,
+                       seed_cnt, flags, batch, qscale);
     HRAG_LAUNCH_CHECK();
     return HRAG_OK;
 }

@@ -824,7 +824,7 @@ __global__ __launch_bounds__(256) void ppr8_init_kernel(const Ppr8Args a, float 
 
 // Per-query statistics of the passage prior over the owned passages, one streaming pass:
 //   zmax = max_p minmax(score_qp) / d_p  (the passage part of the bound that fixes the query's scale),
-//   mass = sum_p v_p with v_p = float(minmax(score_qp) * weight) exactly as rows_to_slab forms it, and
+//   mass = sum_p v_p with v_p = prior_entry(score_qp) exactly as rows_to_slab forms it (sanitised), and
 //   the same sum over the passages whose vertex has no edges.
 // Grid (kP8PriorSplit, B).  The maxima are combined with an integer atomicMax on the bits of the
 // non-negative floats (order-preserving: independent of the arrival order); the sums go through
@@ -846,8 +846,8 @@ __global__ __launch_bounds__(256) void ppr8_prior_kernel(const float *__restrict
         const float *row = scores + (size_t)q * ld;
         for (int64_t p = (int64_t)blockIdx.x * 256 + tid; p < p_rows; p += (int64_t)kP8PriorSplit * 256) {
             const float nrm = range == 0.f ? 1.f : __fdiv_rn(row[p] - lo, range);
-            best = fmaxf(best, nrm * pinvdeg[p]);
-            const float v = nrm * weight;
+            best = fmaxf(best, nrm * pinvdeg[p]);           // (fmaxf skips a NaN: the entry is 0 below)
+            const float v = sanitise_reset(nrm * weight);    // = prior_entry(row[p], mn, mx, weight)
             sum += (double)v;
             if (piso[p]) siso += (double)v;
         }

@@ -302,7 +302,7 @@ __device__ __forceinline__ float sv_minmax_norm(float s, float mn, float mx) {
     return range == 0.f ? 1.f : __fdiv_rn(s - mn, range);   // misc_utils.py:130-139
 }
 
-// passage prior (HippoRAG.py:1626-1635) into tele[p][b]; columns >= batch and DPR-fallback queries are 0
+// passage prior (HippoRAG.py:1626-1635, sanitised: common.h prior_entry) into tele[p][b]; columns >= batch and DPR-fallback queries are 0
 template <int BP>
 __global__ __launch_bounds__(256) void ppr_sv_tele_kernel(const float *scores, int64_t ld, int64_t n,
                                                           int32_t batch, const float *mn, const float *mx,
@@ -314,7 +314,7 @@ __global__ __launch_bounds__(256) void ppr_sv_tele_kernel(const float *scores, i
     for (int b = 0; b < BP; ++b) {
         float v = 0.f;
         if (b < batch && !(flags && (flags[b] & 1))) {
-            v = sv_minmax_norm(scores[(size_t)b * ld + p], mn[b], mx[b]) * weight;
+            v = prior_entry(scores[(size_t)b * ld + p], mn[b], mx[b], weight);
             if (qscale) v *= qscale[b];      // a power of two: exact
         }
         tele[(size_t)p * BP + b] = v;

@@ -8,9 +8,11 @@
 //       phrase_weights[vertex] += w ; number_of_occurs[vertex] += 1  (fp64)      (:1603-1604)
 //   phrase_weights /= number_of_occurs                                           (:1608)
 //   keep the link_top_k heaviest phrases (stable: ties keep first-occurrence order; the reference
-//   order is that of a Python set, i.e. undefined)                               (:1528)
-//   flag bit2 when a kept phrase has weight exactly 0 -- the reference's
+//   order is that of a Python set, i.e. undefined); a NaN mean ranks above every number, like the
+//   top-k's NaN (include/hrag.h)                                                 (:1528)
+//   flag bit2 when a kept phrase has weight exactly +-0 -- the reference's
 //   assert np.count_nonzero(...) == len(linking_score_map) would fire            (:1541)
+//   seed_w is stored sanitised: NaN / negative (and -0) -> +0, as the reference's reset vector is (:1735)
 // At most 2 * kf <= 32 (fact, side) entries per query: lane i of a query's half-wavefront holds entry i (fact i / 2,
 // subject before object); the reference's dict is a pass of 32 shuffles (sum and count of the entries with the same
 // vertex, in entry order = the order the reference adds them up), the stable selection another one (rank = entries
@@ -60,12 +62,16 @@ __global__ __launch_bounds__(64) void build_seeds_kernel(const int32_t *__restri
     }
     const bool rep = v >= 0 && first == i;               // this lane speaks for its phrase
     const double mean = rep ? wsum / (double)occ : 0.0;
-    // stable selection: heavier first, ties in first-occurrence order
+    // stable selection: heavier first, every NaN above every number, ties (NaN with NaN included) in first-occurrence
+    // order -- a strict total order on the representatives, so the ranks are a permutation of [0, m)
+    const bool nan_me = mean != mean;
     int rank = 0;
     for (int j = 0; j < 32; ++j) {
         const double mj = __shfl(mean, base + j, 64);
         const int rj = __shfl((int)rep, base + j, 64);
-        if (rj && j != i && (mj > mean || (mj == mean && j < i))) rank += 1;
+        const bool nan_j = mj != mj;
+        const bool before = nan_j ? (!nan_me || j < i) : (!nan_me && (mj > mean || (mj == mean && j < i)));
+        if (rj && j != i && before) rank += 1;
     }
     const unsigned long long reps = __builtin_amdgcn_ballot_w64(rep);
     const int m = __builtin_popcountll((reps >> base) & 0xffffffffull);
@@ -73,7 +79,7 @@ __global__ __launch_bounds__(64) void build_seeds_kernel(const int32_t *__restri
     const bool kept = rep && rank < keep;
     if (kept) {
         seed_vtx[q * kMaxSeeds + rank] = v;
-        seed_w[q * kMaxSeeds + rank] = (float)mean;
+        seed_w[q * kMaxSeeds + rank] = sanitise_reset((float)mean);
     }
     const unsigned long long zero_kept = __builtin_amdgcn_ballot_w64(kept && mean == 0.0);
     if (qv && i == 0) {

@@ -1004,13 +1004,20 @@ class EngineStages:
         return row_minmax(scores)
 
     # --- reset vector
-    def seeds(self, kept_idx, kept_score, kept_count, link_top_k):
+    def seeds(self, kept_idx, kept_score, kept_count, link_top_k, out=None):
+        """hrag_stage_seeds -> (seed_vtx, seed_w, seed_cnt, flags), into fresh zeroed buffers or into out= (the same
+        four tensors: int32 [B, 32], fp32 [B, 32], int32 [B], int32 [B]; flags is read-modify-written)."""
         torch = _torch()
         b, kf = kept_idx.shape
-        sv = torch.zeros((b, SEED_STRIDE), dtype=torch.int32, device=self.device)
-        sw = torch.zeros((b, SEED_STRIDE), dtype=torch.float32, device=self.device)
-        sc = torch.zeros((b,), dtype=torch.int32, device=self.device)
-        flags = torch.zeros((b,), dtype=torch.int32, device=self.device)
+        if out is not None:
+            sv, sw, sc, flags = out
+        else:
+            sv = torch.zeros((b, SEED_STRIDE), dtype=torch.int32, device=self.device)
+            sw = torch.zeros((b, SEED_STRIDE), dtype=torch.float32, device=self.device)
+            sc = torch.zeros((b,), dtype=torch.int32, device=self.device)
+            flags = torch.zeros((b,), dtype=torch.int32, device=self.device)
+        if sv.shape != (b, SEED_STRIDE) or sw.shape != (b, SEED_STRIDE) or sc.shape != (b,) or flags.shape != (b,):
+            raise ValueError("seeds out=: seed_vtx / seed_w must be [B, 32], seed_cnt / flags [B]")
         check(self.lib.hrag_stage_seeds(self.h, kept_idx.data_ptr(), kept_score.data_ptr(),
                                         kept_count.data_ptr(), kf, link_top_k, b, sv.data_ptr(),
                                         sw.data_ptr(), sc.data_ptr(), flags.data_ptr(), _stream()))

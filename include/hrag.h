@@ -401,6 +401,24 @@ hrag_status hrag_score_facts(hrag_engine *e, const uint16_t *q_fact_dev, int32_t
 #define HRAG_PPR_ERR_FLOOR_F16 2e-6f
 #define HRAG_PPR_ERR_FLOOR_F32 5e-7f
 #define HRAG_PPR_TOL_MIN 1e-7f
+/* The reset vector ("personalization", HippoRAG.py:1574-1638) that every state path of hrag_retrieve /
+ * hrag_retrieve_scored, the row shards and the hybrid mode hand to the PPR solve:
+ *   seed order   phrases by descending fp64 mean weight, ties in first-occurrence order (the reference's order is
+ *                that of a Python set: undefined); a phrase whose mean is NaN ranks above every number, NaN ties in
+ *                first-occurrence order -- the top-k's NaN rule.  The link_top_k first are kept.
+ *   seed_w       fp32(mean), sanitised: NaN, negative and zero become +0 (HippoRAG.py:1735 zeroes NaN / negative
+ *                entries of the whole reset vector).  Flag bit 2 keeps its meaning: a kept phrase whose mean is exactly
+ *                +-0 BEFORE sanitising (NaN and negative means are non-zero to the reference's count_nonzero).
+ *   prior        minmax(score) * passage_node_weight with the row min / max over the numbers of the row (NaN skipped,
+ *                hrag_row_minmax), then sanitised the same way on every path: an entry that is NaN or negative is 0.
+ *                +-inf scores agree with the reference exactly ((inf - mn) / inf is NaN, every finite entry 0: the
+ *                whole prior is 0).  The one difference: the reference's np.min propagates a NaN, so there one NaN
+ *                passage zeroes the whole prior; here only that passage's entry is 0.  Everything derived from the
+ *                prior -- the fp8 path's mass and scale bound, the fp16 scale -- is derived from the sanitised entries.
+ *                "seeds" scope: the masked row keeps the NaN (the scoped DPR fallback ranks it first, as unscoped);
+ *                the prior kernels that read it sanitise it.  An allowed set whose scores hold +-inf has no defined
+ *                scoped prior (every allowed entry normalises to NaN or 0) and is not covered by this rule.
+ * tests/test_gpu_reset_vector.py holds each part to its numpy restatement (tests/helpers.py seeds_np / prior_np). */
 hrag_status hrag_retrieve(hrag_engine *e, const uint16_t *q_pass_dev, int32_t batch,
                           const int32_t *kept_idx_dev, const float *kept_score_dev,
                           const int32_t *kept_count_dev, int32_t kf, int32_t link_top_k,
@@ -670,14 +688,15 @@ hrag_status hrag_row_minmax(const float *scores_dev, int32_t batch, int64_t n, i
                             float *min_out_dev, float *max_out_dev, hrag_stream stream);
 
 /* seeds == HippoRAG.py:1574-1623 + :1505-1542 on fact ids (needs the engine's fact_desc).
- * flags_dev int32 [B] is read-modify-written (bits 0 and 2). */
+ * flags_dev int32 [B] is read-modify-written (bits 0 and 2).  The reset-vector rule of hrag_retrieve (above) applies:
+ * seeds ranked with NaN means first, seed_w sanitised; slots [seed_cnt, HRAG_SEED_STRIDE) are not written. */
 hrag_status hrag_stage_seeds(hrag_engine *e, const int32_t *kept_idx_dev, const float *kept_score_dev,
                              const int32_t *kept_count_dev, int32_t kf, int32_t link_top_k,
                              int32_t batch, int32_t *seed_vtx_dev, float *seed_w_dev,
                              int32_t *seed_cnt_dev, int32_t *flags_dev, hrag_stream stream);
 
-/* passage prior == HippoRAG.py:1626-1635: tele[slab][p][c] = minmax(S[q][p]) * passage_node_weight
- * for ALL Np passages (scores_dev fp32 [B, ld] raw cosine scores in passage order, min/max per
+/* passage prior == HippoRAG.py:1626-1635: tele[slab][p][c] = minmax(S[q][p]) * passage_node_weight, sanitised
+ * (the reset-vector rule above hrag_retrieve), for ALL Np passages (scores_dev fp32 [B, ld] raw cosine scores in passage order, min/max per
  * row); rows of queries whose flags bit0 is set (DPR fallback) are zero.
  * tele_out_dev: [n_slabs][Np][bc]. */
 hrag_status hrag_stage_teleport(hrag_engine *e, const float *scores_dev, int64_t ld,

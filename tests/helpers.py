@@ -192,3 +192,78 @@ def split_f32_np(x):
         hi = x.astype(np.float16)
         lo = (x - hi.astype(np.float32)).astype(np.float16)
     return hi, lo
+
+
+# ----------------------------------------------------------------------------- the reset vector restated
+def seeds_np(kept_idx, kept_score, kept_count, link_top_k, subj, obj, num_chunks):
+    """hrag_stage_seeds restated in numpy (include/hrag.h; HippoRAG.py:1574-1623, :1505-1542):
+      - the entries of a query are (fact r, subject) then (fact r, object) for r < clamp(kept_count, 0, kf); a fact id
+        or vertex outside its table is skipped;
+      - w = fp32 score / fp32 num_chunks[v] where num_chunks[v] > 0, the score itself otherwise;
+      - per phrase an fp64 sum and count in entry order, mean = sum / count;
+      - stable descending selection by the fp64 mean, every NaN mean above every number, ties (NaN included) in
+        first-occurrence order; the first min(link_top_k, m) when 0 < link_top_k < m, else all m phrases;
+      - seed_w = fp32(mean) sanitised: NaN, negative or zero -> +0;
+      - flags bit 0: kept_count <= 0 (DPR fallback); bit 2: a kept phrase's mean is exactly +-0 before sanitising.
+    -> (seed_vtx int32 [B, 32] (-1 beyond seed_cnt), seed_w float32 [B, 32] (0 beyond), seed_cnt int32 [B],
+        flags int32 [B], means: list of the kept fp64 means per query)."""
+    kept_idx = np.asarray(kept_idx, np.int64)
+    kept_score = np.asarray(kept_score, np.float32)
+    kept_count = np.asarray(kept_count, np.int64)
+    subj, obj, num_chunks = (np.asarray(a, np.int64) for a in (subj, obj, num_chunks))
+    b, kf = kept_idx.shape
+    n_facts, n_v = subj.shape[0], num_chunks.shape[0]
+    vtx = np.full((b, 32), -1, np.int32)
+    wts = np.zeros((b, 32), np.float32)
+    cnt = np.zeros(b, np.int32)
+    flags = np.zeros(b, np.int32)
+    means = []
+    for q in range(b):
+        c = int(min(max(kept_count[q], 0), kf))
+        total, occ, order = {}, {}, []
+        for r in range(c):
+            f = int(kept_idx[q, r])
+            s = kept_score[q, r]
+            for side in (subj, obj):
+                if not 0 <= f < n_facts:
+                    continue
+                v = int(side[f])
+                if not 0 <= v < n_v:
+                    continue
+                nc = int(num_chunks[v])
+                with np.errstate(all="ignore"):
+                    w = np.float32(s / np.float32(nc)) if nc > 0 else s
+                if v not in total:
+                    total[v], occ[v] = 0.0, 0
+                    order.append(v)
+                total[v] += float(w)
+                occ[v] += 1
+        mean = {v: total[v] / occ[v] for v in order}
+        ranked = sorted(order, key=lambda v: (0, 0.0) if np.isnan(mean[v]) else (1, -mean[v]))
+        m = len(ranked)
+        keep = link_top_k if 0 < link_top_k < m else m
+        kept = ranked[:keep]
+        for j, v in enumerate(kept):
+            w32 = np.float32(mean[v])
+            vtx[q, j] = v
+            wts[q, j] = w32 if w32 > 0 else np.float32(0)
+        cnt[q] = keep
+        flags[q] = (1 if c == 0 else 0) | (4 if any(mean[v] == 0.0 for v in kept) else 0)
+        means.append([mean[v] for v in kept])
+    return vtx, wts, cnt, flags, means
+
+
+def prior_np(scores, weight, mn=None, mx=None):
+    """The passage prior every phase-B path forms, restated in fp32 (include/hrag.h): minmax(s) * weight with the row
+    min / max over the numbers of the row (NaN skipped, expected_topk's rule) unless given, a zero range giving 1,
+    then sanitised -- NaN, negative or zero -> +0.  -> float32 [B, n]."""
+    s = np.asarray(scores, np.float32)
+    if mn is None:
+        _, _, _, mn, mx = expected_topk(s, 1)
+    mn = np.asarray(mn, np.float32)[:, None]
+    mx = np.asarray(mx, np.float32)[:, None]
+    with np.errstate(all="ignore"):
+        rng_ = mx - mn
+        nrm = np.where(rng_ == 0, np.float32(1), (s - mn) / rng_).astype(np.float32)
+        v = (nrm * np.float32(weight)).astype(np.float32)
+    return np.where(v > 0, v, np.float32(0)).astype(np.float32)
