@@ -512,6 +512,22 @@ hrag_status launch_row_topk_large(const float *scores, int32_t batch, int64_t n,
                                   float *mx_out, hipStream_t s, void *ws, size_t ws_bytes,
                                   const TopkMask *mask = nullptr);
 
+// group.hip : grouped retrieval (include/hrag.h, hrag_group_rows).  Per (query, group) of the CSR group_ptr int64
+// [n_groups + 1] / members int32 [n]: gbest = the allowed member with the largest ranking key (-1: none), gscore = its
+// score (HRAG_GROUP_MAX) or the fp64 sum of the allowed members' scores in member order, rounded once (HRAG_GROUP_SUM);
+// gmask (may be NULL) [batch][gmask_ld] uint32: bit g set when group g has an allowed member -- the mask the ranking of
+// the group rows runs under.  mask: the doc filter over the passages (NULL: every passage)
+hrag_status launch_group_reduce(const float *scores, int32_t batch, int64_t n, int64_t ld, const int64_t *group_ptr,
+                                const int32_t *members, int64_t n_groups, int32_t agg, const TopkMask *mask,
+                                float *gscore, int32_t *gbest, int64_t out_ld, uint32_t *gmask, int64_t gmask_ld,
+                                hipStream_t s);
+// dst[q][i] = minmax_norm(src[q][i], mn[q], mx[q]): the dense scores as the dense ranking returns them, as rows
+hrag_status launch_minmax_rows(const float *src, int32_t batch, int64_t n, int64_t ld, const float *mn, const float *mx,
+                               float *dst, int64_t dst_ld, hipStream_t s);
+// out[q][j] = gbest[q][group_idx[q][j]] for the [batch, k] ranked group ids (-1 stays -1)
+hrag_status launch_group_best(const int32_t *group_idx, const int32_t *gbest, int64_t gld, int64_t n_groups, int32_t k,
+                              int32_t batch, int32_t *out, hipStream_t s);
+
 // knn.hip : fp32 rows -> the 3 * dim bf16 layout of HRAG_F32_SPLIT engines ([hi | lo | hi]; queries [hi | hi | lo])
 hrag_status launch_split3(const float *x, int64_t rows, int32_t dim, int32_t as_query, uint16_t *out, hipStream_t s,
                           int32_t normalize = 0);

@@ -41,7 +41,7 @@ static void workspace_ptrs(hrag_engine *e, std::vector<void **> &out) {
                      (void **)&e->d_ctl, (void **)&e->d_iters_used, (void **)&e->d_resid, (void **)&e->d_mass_tab,
                      (void **)&e->d_est_ws, (void **)&e->d_qsplit, (void **)&e->d_dyn, (void **)&e->d_mmax_ws,
                      (void **)&e->d_mmax_word, (void **)&e->sell.lcount, (void **)&e->fsell.lcount,
-                     (void **)&e->d_fact_mask};
+                     (void **)&e->d_fact_mask, (void **)&e->d_gscore, (void **)&e->d_gbest, (void **)&e->d_gmask};
     out.assign(std::begin(ptrs), std::end(ptrs));
 }
 
@@ -58,7 +58,7 @@ void free_engine(hrag_engine *e) {
                         e->d_seg_end, e->d_seg_slot, e->d_mrow_row, e->d_mrow_first, e->d_mrow_cnt,
                         e->d_passage_vertex, e->d_row_to_tele, e->d_pemb, e->d_femb, e->d_subj, e->d_obj,
                         e->d_num_chunks, e->d_deg, e->d_pinvdeg, e->d_row_ptele, e->d_iso, e->d_piso, e->d_colmask_static,
-                        e->d_fsrc_ptr, e->d_fsrc_pos};
+                        e->d_fsrc_ptr, e->d_fsrc_pos, e->d_grp_ptr, e->d_grp_members};
         for (void *p : ptrs)
             if (p) (void)hipFree(p);
         free_store(e->sell);
@@ -567,6 +567,47 @@ hrag_status ppr_sv_run(hrag_engine *e, const int32_t *row_slot, const float *tel
 // The per-call half of an engine handle, sized once for max_batch: scores, PPR states of every width, seeds, flags,
 // counters.  hrag_engine_create builds it after the index; hrag_workspace_create builds ONLY this for a handle that
 // borrows the index of another engine.  Needs e->want_sell / want_f16 / has_facts / f8_ready and the SELL-8 metadata.
+// what a grouped call adds to its ungrouped form (include/hrag.h, grouped retrieval)
+struct GroupOut {
+    int32_t agg;
+    int32_t *group_idx;
+    float *group_score;
+    int32_t *best_doc;
+};
+
+// argument checks of a grouped call, before anything is enqueued
+static hrag_status check_grouped(const hrag_engine *e, const GroupOut *g) {
+    if (!e->d_grp_ptr || !e->d_gscore) {
+        set_error("no passage groups on this engine: call hrag_engine_set_passage_groups first (on the root engine, before "
+                  "its workspaces are created)");
+        return HRAG_EINVAL;
+    }
+    HRAG_REQUIRE(g->agg == HRAG_GROUP_MAX || g->agg == HRAG_GROUP_SUM, "agg=%d: HRAG_GROUP_MAX (0) or HRAG_GROUP_SUM (1)",
+                 g->agg);
+    HRAG_REQUIRE(g->group_idx && g->group_score && g->best_doc, "NULL group output");
+    return HRAG_OK;
+}
+
+// rows [batch][ld_p] of final passage scores -> group rows -> their ranking under the group bitset -> representatives
+static hrag_status rank_groups(hrag_engine *e, const float *rows, int32_t batch, int32_t k, const TopkMask *mask,
+                               const GroupOut *g, hipStream_t s) {
+    HRAG_TRY(launch_group_reduce(rows, batch, e->n_passages, e->ld_p, e->d_grp_ptr, e->d_grp_members, e->n_groups, g->agg,
+                                 mask, e->d_gscore, e->d_gbest, e->ld_g, e->d_gmask, e->group_words, s));
+    const TopkMask gm{e->d_gmask, e->group_words, 0};
+    HRAG_TRY(rank_rows(e, e->d_gscore, batch, e->n_groups, k, 0, kNormNone, g->group_idx, g->group_score, s, &gm, e->ld_g));
+    return launch_group_best(g->group_idx, e->d_gbest, e->ld_g, e->n_groups, k, batch, g->best_doc, s);
+}
+
+// the group rows of a grouped call (per handle; the caller has pointed tl_alloc_bytes at the workspace half)
+static hrag_status alloc_group_rows(hrag_engine *e) {
+    e->ld_g = round_up(e->n_groups, 4);
+    e->group_words = ceil_div(e->n_groups, 32);
+    HRAG_TRY(dev_alloc(&e->d_gscore, (int64_t)e->max_batch * e->ld_g));
+    HRAG_TRY(dev_alloc(&e->d_gbest, (int64_t)e->max_batch * e->ld_g));
+    HRAG_TRY(dev_alloc(&e->d_gmask, (int64_t)e->max_batch * e->group_words));
+    return HRAG_OK;
+}
+
 static hrag_status alloc_workspace(hrag_engine *e) {
     const bool unsharded = e->n_rows == e->V;
     tl_alloc_bytes = &e->workspace_bytes;
@@ -652,6 +693,7 @@ static hrag_status alloc_workspace(hrag_engine *e) {
         HRAG_TRY(dev_alloc(&e->d_mx_f, B));
     }
     if (e->d_fsrc_ptr) HRAG_TRY(dev_alloc(&e->d_fact_mask, (int64_t)B * e->fact_words));   // scoped phase A
+    if (e->d_grp_ptr) HRAG_TRY(alloc_group_rows(e));                                       // grouped retrieval
     HRAG_TRY(dev_alloc(&e->d_mn_p, B));
     HRAG_TRY(dev_alloc(&e->d_mx_p, B));
     HRAG_TRY(dev_alloc(&e->d_seed_vtx, (int64_t)B * kMaxSeeds));
@@ -1350,20 +1392,23 @@ static hrag_status retrieve_impl(hrag_engine *e, const uint16_t *q_pass, const f
                                  float passage_node_weight, int32_t ppr_iters, int32_t ppr_max_iters, float ppr_tol,
                                  int32_t k, int32_t *doc_idx_out, float *doc_score_out, int32_t *flags_out,
                                  float *residual_out, int32_t *iters_out, hrag_stream stream,
-                                 const uint32_t *filter, int64_t filter_ld_words, bool scoped = false) {
+                                 const uint32_t *filter, int64_t filter_ld_words, bool scoped = false,
+                                 const GroupOut *grp = nullptr) {
     HRAG_TRY(check_batch(e, batch));
     TopkMask fm;
     const TopkMask *mask = nullptr;
     HRAG_TRY(doc_filter(e, filter, filter_ld_words, fm, &mask));
     HRAG_REQUIRE(!scoped || mask, "NULL filter (the scoped call needs the allowed passages)");
+    if (grp) HRAG_TRY(check_grouped(e, grp));
     HRAG_REQUIRE(ppr_tol >= 0.f && ppr_tol == ppr_tol, "ppr_tol must be >= 0");
     HRAG_REQUIRE(ppr_tol == 0.f || ppr_tol >= HRAG_PPR_TOL_MIN,
                  "ppr_tol=%g is below HRAG_PPR_TOL_MIN=%g: fp32 arithmetic leaves an error floor of %g however small the "
                  "measured residual reads (include/hrag.h: error <= max(%g * residual, floor))", (double)ppr_tol,
                  (double)HRAG_PPR_TOL_MIN, (double)HRAG_PPR_ERR_FLOOR_F32, (double)HRAG_PPR_ERR_K);
     HRAG_REQUIRE(ppr_tol == 0.f || ppr_max_iters >= ppr_iters, "ppr_max_iters=%d < ppr_iters=%d", ppr_max_iters, ppr_iters);
-    HRAG_REQUIRE((q_pass || pass_scores) && kept_idx && kept_score && kept_count && doc_idx_out && doc_score_out,
-                 "NULL argument");
+    HRAG_REQUIRE((q_pass || pass_scores) && kept_idx && kept_score && kept_count, "NULL argument");
+    // a grouped call may leave the ungrouped ranking out (both pointers NULL)
+    HRAG_REQUIRE(grp ? (doc_idx_out != nullptr) == (doc_score_out != nullptr) : doc_idx_out && doc_score_out, "NULL argument");
     HRAG_REQUIRE(e->n_rows == e->V && e->p_rows == e->n_passages,
                  "hrag_retrieve needs an unsharded engine; sharded engines use the hrag_stage_* operators");
     HRAG_REQUIRE(pass_scores || e->d_pemb, "the engine was created without passage embeddings: use hrag_retrieve_scored");
@@ -1539,7 +1584,9 @@ static hrag_status retrieve_impl(hrag_engine *e, const uint16_t *q_pass, const f
                                      lay, s));
     }
     HRAG_TRY(launch_flag_zero_mass(e->d_sums, batch, e->d_flags, 2, s));
-    HRAG_TRY(rank_rows(e, e->d_doc, batch, e->n_passages, k, 0, kNormNone, doc_idx_out, doc_score_out, s, mask));
+    if (doc_idx_out)
+        HRAG_TRY(rank_rows(e, e->d_doc, batch, e->n_passages, k, 0, kNormNone, doc_idx_out, doc_score_out, s, mask));
+    if (grp) HRAG_TRY(rank_groups(e, e->d_doc, batch, k, mask, grp, s));
     const bool measured = f8 || est != nullptr;
     if (!f8 && est)
         HRAG_TRY(launch_ppr8_finalize(est, e->d_flags, batch, damping / (1.0f - damping), ppr_tol, sweeps_run, e->d_ctl,
@@ -1662,12 +1709,15 @@ hrag_status hrag_dense_retrieve(hrag_engine *e, const uint16_t *q_pass, int32_t 
 
 static hrag_status dense_impl(hrag_engine *e, const uint16_t *q_pass, int32_t batch, int32_t k, int32_t *doc_idx_out,
                               float *doc_score_out, hrag_stream stream, const uint32_t *filter_dev,
-                              int64_t filter_ld_words, bool scoped) {
+                              int64_t filter_ld_words, bool scoped, const GroupOut *grp = nullptr) {
     HRAG_TRY(check_batch(e, batch));
     TopkMask fm;
     const TopkMask *mask = nullptr;
     HRAG_TRY(doc_filter(e, filter_dev, filter_ld_words, fm, &mask));
-    HRAG_REQUIRE(q_pass && doc_idx_out && doc_score_out, "NULL argument");
+    HRAG_REQUIRE(!scoped || mask, "NULL filter (the scoped call needs the allowed passages)");
+    if (grp) HRAG_TRY(check_grouped(e, grp));
+    HRAG_REQUIRE(q_pass != nullptr, "NULL argument");
+    HRAG_REQUIRE(grp ? (doc_idx_out != nullptr) == (doc_score_out != nullptr) : doc_idx_out && doc_score_out, "NULL argument");
     HRAG_REQUIRE(e->p_rows == e->n_passages && e->d_pemb, "hrag_dense_retrieve needs the whole passage matrix");
     HRAG_REQUIRE(k >= 1 && k <= e->max_topk, "k=%d outside [1, max_topk=%d]", k, e->max_topk);
     hipStream_t s = (hipStream_t)stream;
@@ -1678,7 +1728,15 @@ static hrag_status dense_impl(hrag_engine *e, const uint16_t *q_pass, int32_t ba
     HRAG_TRY(launch_sim_gemm(e->d_pemb, e->p_rows, e->kdim, q_pass, batch, e->d_spass, e->ld_p, s, 0, e->emb_dtype));
     // "seeds" scope: normalised over the allowed passages first; the ranking's own min-max is then identity
     if (scoped) HRAG_TRY(launch_masked_prior(e->d_spass, batch, e->n_passages, e->ld_p, *mask, s));
-    return rank_rows(e, e->d_spass, batch, e->n_passages, k, 0, kNormMinMax, doc_idx_out, doc_score_out, s, mask);
+    if (doc_idx_out)
+        HRAG_TRY(rank_rows(e, e->d_spass, batch, e->n_passages, k, 0, kNormMinMax, doc_idx_out, doc_score_out, s, mask));
+    if (grp) {
+        // the groups are formed over the scores the dense ranking returns: the rows normalised as its top-k does
+        HRAG_TRY(launch_row_minmax(e->d_spass, batch, e->n_passages, e->ld_p, e->d_mn_p, e->d_mx_p, s));
+        HRAG_TRY(launch_minmax_rows(e->d_spass, batch, e->n_passages, e->ld_p, e->d_mn_p, e->d_mx_p, e->d_doc, e->ld_p, s));
+        HRAG_TRY(rank_groups(e, e->d_doc, batch, k, mask, grp, s));
+    }
+    return HRAG_OK;
 }
 
 hrag_status hrag_dense_retrieve_filtered(hrag_engine *e, const uint16_t *q_pass, int32_t batch, int32_t k,
@@ -1693,6 +1751,116 @@ hrag_status hrag_dense_retrieve_scoped(hrag_engine *e, const uint16_t *q_pass, i
     HRAG_REQUIRE(e != nullptr && filter_dev != nullptr, "NULL argument / NULL filter (the scoped call needs the allowed passages)");
     HRAG_TRY(refuse_row_shard(e, "hrag_dense_retrieve_scoped", false));
     return dense_impl(e, q_pass, batch, k, doc_idx_out, doc_score_out, stream, filter_dev, filter_ld_words, true);
+}
+
+// ---- grouped retrieval (include/hrag.h): the passage -> group table and the grouped forms of the three calls
+hrag_status hrag_engine_set_passage_groups(hrag_engine *e, const int32_t *group_of, int64_t n_groups) {
+    HRAG_REQUIRE(e != nullptr, "engine is NULL");
+    HRAG_REQUIRE(!e->borrowed, "passage groups belong to the shared index: set them on the root engine, not on a workspace");
+    HRAG_REQUIRE(e->p_rows == e->n_passages && e->n_rows == e->V,
+                 "hrag_engine_set_passage_groups on a row-shard engine: a group's members span the shards (grouped "
+                 "retrieval is served by the unsharded engine only)");
+    if (e->n_workspaces.v.load() != 0) {
+        set_error("engine has %d live workspace(s): their handles hold copies of the index pointers -- destroy them, set the "
+                  "passage groups, create them again", e->n_workspaces.v.load());
+        return HRAG_EBUSY;
+    }
+    const int64_t n_p = e->n_passages;
+    HRAG_REQUIRE(n_p >= 1, "engine has no passages");
+    std::vector<int64_t> ptr;
+    std::vector<int32_t> members;
+    if (group_of) {
+        HRAG_REQUIRE(n_groups >= 1 && n_groups <= n_p, "n_groups=%lld outside [1, n_passages=%lld]", (long long)n_groups,
+                     (long long)n_p);
+        ptr.assign((size_t)n_groups + 1, 0);
+        for (int64_t p = 0; p < n_p; ++p) {
+            HRAG_REQUIRE(group_of[p] >= 0 && group_of[p] < n_groups, "group_of[%lld]=%d outside [0, n_groups=%lld)",
+                         (long long)p, group_of[p], (long long)n_groups);
+            ++ptr[(size_t)group_of[p] + 1];
+        }
+        for (int64_t g = 0; g < n_groups; ++g) ptr[(size_t)g + 1] += ptr[(size_t)g];
+        members.resize((size_t)n_p);
+        std::vector<int64_t> fill(ptr.begin(), ptr.end() - 1);
+        for (int64_t p = 0; p < n_p; ++p) members[(size_t)fill[(size_t)group_of[p]]++] = (int32_t)p;   // ascending per group
+    }
+    {
+        // the entry flag: not while another thread is inside a call on this handle
+        int expected = 0;
+        if (!e->in_call.v.compare_exchange_strong(expected, 1)) {
+            set_error("engine busy: another thread is inside a call on this engine");
+            return HRAG_EBUSY;
+        }
+    }
+    struct Leave { hrag_engine *e; ~Leave() { e->in_call.v.store(0); } } leave{e};
+    HRAG_HIP_TRY(hipSetDevice(e->device));
+    HRAG_HIP_TRY(hipDeviceSynchronize());   // a call in flight may still read the table being replaced
+    for (void *p : {(void *)e->d_grp_ptr, (void *)e->d_grp_members, (void *)e->d_gscore, (void *)e->d_gbest, (void *)e->d_gmask})
+        if (p) (void)hipFree(p);
+    e->index_bytes -= e->d_grp_ptr ? (e->n_groups + 1) * (int64_t)sizeof(int64_t) + n_p * (int64_t)sizeof(int32_t) : 0;
+    e->workspace_bytes -= e->d_gscore ? (int64_t)e->max_batch * (e->ld_g * 8 + e->group_words * 4) : 0;
+    e->d_grp_ptr = nullptr; e->d_grp_members = nullptr; e->d_gscore = nullptr; e->d_gbest = nullptr; e->d_gmask = nullptr;
+    e->n_groups = e->ld_g = e->group_words = 0;
+    if (!group_of) return HRAG_OK;
+    e->n_groups = n_groups;
+    {
+        tl_alloc_bytes = &e->index_bytes;
+        struct Unbook { ~Unbook() { tl_alloc_bytes = nullptr; } } unbook;
+        HRAG_TRY(dev_upload(&e->d_grp_ptr, ptr.data(), n_groups + 1));
+        HRAG_TRY(dev_upload(&e->d_grp_members, members.data(), n_p));
+    }
+    {
+        tl_alloc_bytes = &e->workspace_bytes;
+        struct Unbook { ~Unbook() { tl_alloc_bytes = nullptr; } } unbook;
+        HRAG_TRY(alloc_group_rows(e));
+    }
+    return HRAG_OK;
+}
+
+hrag_status hrag_retrieve_grouped(hrag_engine *e, const uint16_t *q_pass, int32_t batch, const int32_t *kept_idx,
+                                  const float *kept_score, const int32_t *kept_count, int32_t kf, int32_t link_top_k,
+                                  float damping, float passage_node_weight, int32_t ppr_iters, int32_t ppr_max_iters,
+                                  float ppr_tol, int32_t k, int32_t *doc_idx_out, float *doc_score_out, int32_t *flags_out,
+                                  float *residual_out, int32_t *iters_out, hrag_stream stream, const uint32_t *filter_dev,
+                                  int64_t filter_ld_words, int32_t scoped, int32_t agg, int32_t *group_idx_out,
+                                  float *group_score_out, int32_t *best_doc_idx_out) {
+    HRAG_REQUIRE(e != nullptr && q_pass != nullptr, "NULL argument");
+    const GroupOut g{agg, group_idx_out, group_score_out, best_doc_idx_out};
+    return retrieve_impl(e, q_pass, nullptr, 0, batch, kept_idx, kept_score, kept_count, kf, link_top_k, damping,
+                         passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol, k, doc_idx_out, doc_score_out,
+                         flags_out, residual_out, iters_out, stream, filter_dev, filter_ld_words, scoped != 0, &g);
+}
+
+hrag_status hrag_retrieve_scored_grouped(hrag_engine *e, const float *pass_scores, int64_t pass_ld, int32_t batch,
+                                         const int32_t *kept_idx, const float *kept_score, const int32_t *kept_count,
+                                         int32_t kf, int32_t link_top_k, float damping, float passage_node_weight,
+                                         int32_t ppr_iters, int32_t ppr_max_iters, float ppr_tol, int32_t k,
+                                         int32_t *doc_idx_out, float *doc_score_out, int32_t *flags_out,
+                                         float *residual_out, int32_t *iters_out, hrag_stream stream,
+                                         const uint32_t *filter_dev, int64_t filter_ld_words, int32_t scoped, int32_t agg,
+                                         int32_t *group_idx_out, float *group_score_out, int32_t *best_doc_idx_out) {
+    HRAG_REQUIRE(e != nullptr && pass_scores != nullptr, "NULL argument");
+    const GroupOut g{agg, group_idx_out, group_score_out, best_doc_idx_out};
+    return retrieve_impl(e, nullptr, pass_scores, pass_ld, batch, kept_idx, kept_score, kept_count, kf, link_top_k,
+                         damping, passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol, k, doc_idx_out, doc_score_out,
+                         flags_out, residual_out, iters_out, stream, filter_dev, filter_ld_words, scoped != 0, &g);
+}
+
+hrag_status hrag_dense_retrieve_grouped(hrag_engine *e, const uint16_t *q_pass, int32_t batch, int32_t k,
+                                        int32_t *doc_idx_out, float *doc_score_out, hrag_stream stream,
+                                        const uint32_t *filter_dev, int64_t filter_ld_words, int32_t scoped, int32_t agg,
+                                        int32_t *group_idx_out, float *group_score_out, int32_t *best_doc_idx_out) {
+    HRAG_REQUIRE(e != nullptr, "engine is NULL");
+    const GroupOut g{agg, group_idx_out, group_score_out, best_doc_idx_out};
+    return dense_impl(e, q_pass, batch, k, doc_idx_out, doc_score_out, stream, filter_dev, filter_ld_words, scoped != 0, &g);
+}
+
+hrag_status hrag_group_rows(const float *scores, int32_t batch, int64_t n, int64_t ld, const int64_t *group_ptr,
+                            const int32_t *members, int64_t n_groups, int32_t agg, const uint32_t *filter_dev,
+                            int64_t filter_ld_words, int64_t filter_bit_offset, float *gscore_out, int32_t *gbest_out,
+                            int64_t out_ld, hrag_stream stream) {
+    const TopkMask m{filter_dev, filter_ld_words, filter_bit_offset};
+    return launch_group_reduce(scores, batch, n, ld, group_ptr, members, n_groups, agg, filter_dev ? &m : nullptr,
+                               gscore_out, gbest_out, out_ld, nullptr, 0, (hipStream_t)stream);
 }
 
 hrag_status hrag_ppr(hrag_engine *e, const float *reset, int32_t batch, float damping, int32_t iters,

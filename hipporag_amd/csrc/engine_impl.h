@@ -178,6 +178,15 @@ struct hrag_engine {
     int32_t *d_fsrc_pos = nullptr;
     int64_t fsrc_nnz = 0, fact_words = 0;
     uint32_t *d_fact_mask = nullptr;
+    // grouped retrieval (hrag_engine_set_passage_groups): passage groups as a CSR (index half, borrowed by workspaces) and
+    // the current call's group rows (per handle): scores / representatives [max_batch][ld_g], the bitset of the groups
+    // that have an allowed member [max_batch][group_words] -- the mask their ranking runs under
+    int64_t *d_grp_ptr = nullptr;
+    int32_t *d_grp_members = nullptr;
+    int64_t n_groups = 0, ld_g = 0, group_words = 0;
+    float *d_gscore = nullptr;
+    int32_t *d_gbest = nullptr;
+    uint32_t *d_gmask = nullptr;
     // two-stage fp16 PPR (ppr16.hip): SELL-8 matrix + fp16 state, unsharded engines with max_batch > 8
     bool f16_ready = false;   // fp16 state buffers present (max_batch > 8)
     int32_t f16_max_batch = 0;  // ... sized for this many queries (64 when the fp8 path serves the larger batches)
@@ -317,11 +326,12 @@ struct EngineCall {
 // mask: the caller's doc filter (hrag_retrieve_filtered), or nullptr for every passage
 inline hrag_status rank_rows(hrag_engine *e, const float *rows, int32_t batch, int64_t n, int32_t k, int32_t idx_offset,
                              TopkNorm norm, int32_t *idx_out, float *val_out, hipStream_t s,
-                             const TopkMask *mask = nullptr) {
+                             const TopkMask *mask = nullptr, int64_t ld = 0) {
+    if (ld == 0) ld = e->ld_p;   // (the group rows of a grouped call have their own stride, n <= n_passages entries)
     if (k <= kTopkMax)
-        return launch_row_topk(rows, batch, n, e->ld_p, k, idx_offset, norm, idx_out, val_out, nullptr, nullptr, s,
+        return launch_row_topk(rows, batch, n, ld, k, idx_offset, norm, idx_out, val_out, nullptr, nullptr, s,
                                e->d_topk_ws, kTopkWsBytes, mask);
-    return launch_row_topk_large(rows, batch, n, e->ld_p, k, idx_offset, norm, idx_out, val_out, nullptr, nullptr, s,
+    return launch_row_topk_large(rows, batch, n, ld, k, idx_offset, norm, idx_out, val_out, nullptr, nullptr, s,
                                  e->d_topk_large, (size_t)e->topk_large_bytes, mask);
 }
 

@@ -432,7 +432,7 @@ class ShardedRetriever:
 
     def retrieve(self, q_pass, kept_idx, kept_score, kept_count, *, link_top_k=5, damping=0.5,
                  passage_node_weight=0.05, ppr_iters=20, k=200, ppr_tol=0.0, ppr_max_iters=0,
-                 check_saturation=True, doc_filter=None, filter_scope: str = "ranking"):
+                 check_saturation=True, doc_filter=None, filter_scope: str = "ranking", group_agg=None):
         """Returns (doc ids, doc scores, flags) -- and with ppr_tol > 0 additionally (residual, sweeps used): the
         convergence contract of hrag_retrieve on the shards.  Every shard measures the relative update of ITS
         passages; the measures are all-reduced (MAX) before every decision, so all shards run the same steps.
@@ -444,6 +444,8 @@ class ShardedRetriever:
         allowed passages of its slice, the merge puts a shard's -1 slots after every real entry.
         filter_scope="seeds": the passage prior and the DPR fallback normalised over the allowed passages of every shard
         (= HippoRAGEngine.retrieve(filter_scope="seeds"); the kept facts from score_facts(scope_filter=))."""
+        from .engine import refuse_group_agg
+        refuse_group_agg("ShardedRetriever", {"group_agg": group_agg})
         scoped = serve_seeds_scope(getattr(self, "st", None), filter_scope)
         if scoped:
             from .engine import check_filter_scope
@@ -629,9 +631,11 @@ class NativeShardedRetriever:
 
     def retrieve(self, q_pass, kept_idx, kept_score, kept_count, *, link_top_k=5, damping=0.5, passage_node_weight=0.05,
                  ppr_iters=20, k=200, ppr_tol=0.0, ppr_max_iters=0, check_saturation=True, doc_filter=None,
-                 filter_scope: str = "ranking"):
+                 filter_scope: str = "ranking", group_agg=None):
         """Same contract as ShardedRetriever.retrieve: (doc ids, doc scores, flags[, residual, sweeps used]);
         doc_filter: hrag_shard_retrieve_filtered with the global filter (filter_scope="seeds": hrag_shard_retrieve_scoped)."""
+        from .engine import refuse_group_agg
+        refuse_group_agg("NativeShardedRetriever", {"group_agg": group_agg})
         scoped = serve_seeds_scope(getattr(self, "st", None), filter_scope)
         if scoped:
             from .engine import check_filter_scope
@@ -718,6 +722,9 @@ class HybridRetriever:
         kw["doc_filter"] (optional): the global batch's filter; a per-query one is cut to this rank's rows.
         kw["filter_scope"]="seeds": hrag_retrieve_scored_scoped on this rank's rows (the prior masked over the allowed
         passages of the all-to-all'd score rows); needs the fact sources on the embedding shard, like score_facts."""
+        from .engine import refuse_group_agg
+        refuse_group_agg("HybridRetriever", kw)
+        kw.pop("group_agg", None)
         scope = kw.pop("filter_scope", "ranking")
         if serve_seeds_scope(getattr(self, "sim", None), scope):
             kw["filter_scope"] = scope

@@ -55,6 +55,32 @@ def pack_mask(mask) -> np.ndarray:
 
 
 FILTER_SCOPES = ("ranking", "seeds")
+GROUP_AGGS = {"max": 0, "sum": 1}      # HRAG_GROUP_MAX / HRAG_GROUP_SUM
+
+
+def check_group_agg(group_agg) -> Optional[int]:
+    """None (ungrouped) or the HRAG_GROUP_* code of "max" / "sum"."""
+    if group_agg is None:
+        return None
+    if group_agg not in GROUP_AGGS:
+        raise ValueError(f"group_agg={group_agg!r}: None, 'max' or 'sum' expected")
+    return GROUP_AGGS[group_agg]
+
+
+def group_table_csr(group_of, n_groups: int):
+    """The CSR the engine builds from a passage -> group table: (group_ptr int64 [n_groups + 1], members int32 [n],
+    the members of a group in ascending passage position)."""
+    g = np.asarray(group_of, np.int64)
+    ptr = np.zeros(n_groups + 1, np.int64)
+    ptr[1:] = np.cumsum(np.bincount(g, minlength=n_groups))
+    return ptr, np.argsort(g, kind="stable").astype(np.int32)
+
+
+def refuse_group_agg(who: str, kw: dict) -> None:
+    """The multi-GPU retrievers and the captured pipeline do not serve grouped retrieval."""
+    if kw.get("group_agg") is not None:
+        raise NotImplementedError(f"{who} does not serve group_agg: a group's members span the row shards and a sum across "
+                                  "shards is not bit-reproducible without a defined order -- use HippoRAGEngine.retrieve")
 
 
 def check_filter_scope(filter_scope: str, doc_filter) -> bool:
@@ -143,6 +169,16 @@ class RetrieveOutput:
                                  # of the passage scores (include/hrag.h, hrag_retrieve); -1 where not measured
     iters_used: "object" = None  # torch int32 [B]: PPR sweeps that ran
     all_scores: "object" = None  # torch fp32 [B, Np] (retrieve_converged(want_all_scores=True)): every passage's score
+    group_idx: "object" = None   # grouped call (group_agg=): torch int32 [B, k] group ids, best first; doc_idx then holds
+                                 # each ranked group's representative passage and doc_score the group score
+
+    @property
+    def group_score(self):       # the grouped call's names for the two tensors above
+        return self.doc_score
+
+    @property
+    def best_doc_idx(self):
+        return self.doc_idx
 
 
 logger = logging.getLogger(__name__)
@@ -235,6 +271,8 @@ class PendingRetrieve:
             # fp32 state: the scores that converge last are orders of magnitude below the largest one
             o2 = on_wider_state(lambda: run(rt, need, need), OPT_NO_FP8 | OPT_NO_F16)
             out.doc_idx[rt], out.doc_score[rt] = o2.doc_idx, o2.doc_score
+            if out.group_idx is not None:
+                out.group_idx[rt] = o2.group_idx
             out.flags[rt], out.residual[rt], out.iters_used[rt] = o2.flags, o2.residual, o2.iters_used
             if self.want_all_scores:
                 out.all_scores[rt] = o2.all_scores
@@ -503,6 +541,25 @@ class HippoRAGEngine:
                                                      rp.shape[0] - 1, pp.shape[0]))
         self.has_fact_sources = True
 
+    def set_passage_groups(self, group_of):
+        """The passage -> group table of grouped retrieval (hrag_engine_set_passage_groups): group_of[p] in [0, G) for every
+        passage position p, G = max + 1 (None clears it).  On the root engine, with no live workspaces."""
+        if getattr(self, "_parent", None) is not None:
+            raise ValueError("passage groups belong to the shared index: set them on the root engine")
+        if group_of is None:
+            check(self._lib.hrag_engine_set_passage_groups(self._handle, None, 0))
+            self.n_groups = 0
+            return
+        g = np.asarray(group_of)
+        if g.ndim != 1 or g.shape[0] != self.n_passages or g.dtype.kind not in "iu":
+            raise ValueError(f"group_of: an integer array of {self.n_passages} entries (one per passage) expected")
+        if g.size and (int(g.min()) < 0 or int(g.max()) >= self.n_passages):
+            raise ValueError("group ids must lie in [0, n_passages)")
+        g = np.ascontiguousarray(g, dtype=np.int32)
+        n_groups = int(g.max()) + 1
+        check(self._lib.hrag_engine_set_passage_groups(self._handle, g.ctypes.data, n_groups))
+        self.n_groups = n_groups
+
     def score_facts(self, q_fact, k: int = 5, scope_filter=None):
         """Phase A: (fact ids int32 [B,k], min-max normalised scores fp32 [B,k]).
         scope_filter: a doc filter (doc_filter_words) -- the top k among the facts of those passages, normalised over
@@ -524,16 +581,20 @@ class HippoRAGEngine:
     def retrieve(self, q_pass, kept_idx, kept_score, kept_count, *, link_top_k: int = 5,
                  damping: float = 0.5, passage_node_weight: float = 0.05, ppr_iters: int = 20,
                  k: int = 200, ppr_tol: float = 0.0, ppr_max_iters: int = 0,
-                 want_residual: bool = True, doc_filter=None, filter_scope: str = "ranking") -> RetrieveOutput:
+                 want_residual: bool = True, doc_filter=None, filter_scope: str = "ranking",
+                 group_agg: Optional[str] = None) -> RetrieveOutput:
         """Phase B: seeds + passage prior + PPR + ranking (DPR ranking where kept_count == 0).
         ppr_tol / ppr_max_iters: the convergence contract of include/hrag.h (0 = exactly ppr_iters sweeps);
         the output carries the per-query residual and the sweeps that ran.
         doc_filter: only these passages may be ranked (doc_filter_words; hrag_retrieve_filtered): each row is the first
         min(k, allowed) allowed entries of the unfiltered ranking, then -1 / 0.  Scoring is unchanged.
         filter_scope="seeds": the passage prior and the DPR fallback are normalised over the allowed passages as well
-        (hrag_retrieve_scoped; the kept facts should come from score_facts(scope_filter=) with the same filter)."""
+        (hrag_retrieve_scoped; the kept facts should come from score_facts(scope_filter=) with the same filter).
+        group_agg="max" | "sum" (after set_passage_groups; hrag_retrieve_grouped): the k best GROUPS -- group_idx, their
+        scores (group_score = doc_score) and each group's best passage (best_doc_idx = doc_idx); composes with both."""
         torch = _torch()
         scoped = check_filter_scope(filter_scope, doc_filter)
+        agg = check_group_agg(group_agg)
         q = self._q(q_pass)
         b = q.shape[0]
         kept_idx = kept_idx.to(self.device, torch.int32).contiguous()
@@ -551,6 +612,9 @@ class HippoRAGEngine:
                 link_top_k, damping, passage_node_weight, ppr_iters, max(ppr_max_iters, ppr_iters), ppr_tol, k,
                 idx.data_ptr(), sc.data_ptr(), flags.data_ptr(), resid.data_ptr() if resid is not None else None,
                 used.data_ptr() if used is not None else None, _stream())
+        if agg is not None:
+            return self._grouped(self._lib.hrag_retrieve_grouped, args, 14, doc_filter, scoped, agg, b, k,
+                                 RetrieveOutput(idx, sc, flags, resid, used))
         if doc_filter is None:
             check(self._lib.hrag_retrieve(*args))
         else:
@@ -559,13 +623,25 @@ class HippoRAGEngine:
             check(fn(*args, fw.data_ptr(), fld))
         return RetrieveOutput(idx, sc, flags, resid, used)
 
+    def _grouped(self, fn, args, doc_at, doc_filter, scoped, agg, b, k, out):
+        """A grouped call: `args` of the ungrouped form with the two ungrouped outputs (at doc_at) left out."""
+        torch = _torch()
+        fw, fld = (None, 0) if doc_filter is None else doc_filter_words(doc_filter, self.n_passages, b, self.device)
+        gi = self._empty((b, k), torch.int32)
+        args = args[:doc_at] + (None, None) + args[doc_at + 2:]
+        check(fn(*args, fw.data_ptr() if fw is not None else None, fld, 1 if scoped else 0, agg, gi.data_ptr(),
+                 out.doc_score.data_ptr(), out.doc_idx.data_ptr()))
+        out.group_idx = gi
+        return out
+
     def retrieve_scored(self, pass_scores, kept_idx, kept_score, kept_count, *, link_top_k: int = 5,
                         damping: float = 0.5, passage_node_weight: float = 0.05, ppr_iters: int = 20, k: int = 200,
                         ppr_tol: float = 0.0, ppr_max_iters: int = 0, doc_filter=None,
-                        filter_scope: str = "ranking") -> RetrieveOutput:
+                        filter_scope: str = "ranking", group_agg: Optional[str] = None) -> RetrieveOutput:
         """retrieve() with the raw passage scores fp32 [B, >= Np] supplied by the caller (hrag_retrieve_scored)."""
         torch = _torch()
         scoped = check_filter_scope(filter_scope, doc_filter)
+        agg = check_group_agg(group_agg)
         sc_in = pass_scores.to(self.device, torch.float32)
         if sc_in.stride(-1) != 1:
             sc_in = sc_in.contiguous()
@@ -580,6 +656,9 @@ class HippoRAGEngine:
                 kept_count.data_ptr(), kf, link_top_k, damping, passage_node_weight, ppr_iters,
                 max(ppr_max_iters, ppr_iters), ppr_tol, k, idx.data_ptr(), sc.data_ptr(), flags.data_ptr(), resid.data_ptr(),
                 used.data_ptr(), _stream())
+        if agg is not None:
+            return self._grouped(self._lib.hrag_retrieve_scored_grouped, args, 15, doc_filter, scoped, agg, b, k,
+                                 RetrieveOutput(idx, sc, flags, resid, used))
         if doc_filter is None:
             check(self._lib.hrag_retrieve_scored(*args))
         else:
@@ -637,14 +716,22 @@ class HippoRAGEngine:
         check(self._lib.hrag_last_doc_scores(self._handle, batch, out.data_ptr(), self.passage_rows, _stream()))
         return out
 
-    def dense_retrieve(self, q_pass, k: int = 200, doc_filter=None, filter_scope: str = "ranking"):
-        """DPR top-k; filter_scope="seeds": normalised over the allowed passages (hrag_dense_retrieve_scoped)."""
+    def dense_retrieve(self, q_pass, k: int = 200, doc_filter=None, filter_scope: str = "ranking",
+                       group_agg: Optional[str] = None):
+        """DPR top-k; filter_scope="seeds": normalised over the allowed passages (hrag_dense_retrieve_scoped).
+        group_agg="max" | "sum": (group ids, group scores, best passage of each group) over the normalised scores
+        (hrag_dense_retrieve_grouped)."""
         torch = _torch()
         scoped = check_filter_scope(filter_scope, doc_filter)
+        agg = check_group_agg(group_agg)
         q = self._q(q_pass)
         b = q.shape[0]
         idx = self._empty((b, k), torch.int32)
         sc = self._empty((b, k), torch.float32)
+        if agg is not None:
+            out = self._grouped(self._lib.hrag_dense_retrieve_grouped, (self._handle, q.data_ptr(), b, k, None, None, _stream()),
+                                4, doc_filter, scoped, agg, b, k, RetrieveOutput(idx, sc, None))
+            return out.group_idx, out.doc_score, out.doc_idx
         if doc_filter is None:
             check(self._lib.hrag_dense_retrieve(self._handle, q.data_ptr(), b, k, idx.data_ptr(),
                                                 sc.data_ptr(), _stream()))
@@ -898,6 +985,7 @@ class CapturedPipeline:
 
     def __init__(self, engine: "HippoRAGEngine", batch: int, *, k_f: int = 5, k: int = 200, **retrieve_kw):
         torch = _torch()
+        refuse_group_agg("CapturedPipeline", retrieve_kw)
         self.engine, self.batch = engine, int(batch)
         dev, dt = engine.device, engine.emb_dtype
         self._qf = torch.zeros((batch, engine.dim), dtype=dt, device=dev)

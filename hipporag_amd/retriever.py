@@ -186,6 +186,10 @@ class RetrievalConfig:
     doc_filter_scope: str = "ranking"    # what a doc filter limits (include/hrag.h): "ranking" -- only the ranked list (a
                                          # post-filter); "seeds" -- also the facts phase A may pick and the passage prior,
                                          # normalised over the allowed passages (one tenant's documents in a shared index)
+    group_by: Optional[str] = None       # grouped retrieval (include/hrag.h): a chunk-metadata key ("source_id" included);
+                                         # retrieve() / retrieve_dpr() then rank the GROUPS of passages that share its value,
+                                         # one best passage per group; None: passages, as the reference
+    group_agg: str = "max"               # a group's score: "max" (its best passage's) or "sum" (of its passages' scores)
 
 
 def identity_rerank_filter(query, candidate_items, candidate_indices, len_after_rerank=None):
@@ -215,6 +219,7 @@ class BatchRows(list):
     batch's arrays themselves (doc_idx int32 [b, k], doc_score fp32 [b, k]) for consumers that work on whole batches."""
     doc_idx = None
     doc_score = None
+    group_idx = None     # grouped retrieval: int32 [b, k] group ids (doc_idx: each group's best passage, doc_score: its score)
 
 
 def unpack_mask(words, n: int) -> np.ndarray:
@@ -237,6 +242,37 @@ def rank_allowed(full, allowed, want: int):
         idx[i, :len(order)] = order
         sc[i, :len(order)] = full[i][order]
     return idx, sc
+
+
+def group_rank_rows(full, group_of, allowed, want: int, agg: str = "max"):
+    """The host form of the grouped ranking (include/hrag.h, grouped retrieval): per row of `full` fp32 [B, n] the first
+    `want` groups -> (group ids, group scores, representative passages), -1 / 0 / -1 beyond the groups that have an allowed
+    member.  allowed: None, bool [n] or [B, n]."""
+    full = np.asarray(full, np.float32)
+    b, n = full.shape
+    g = np.asarray(group_of, np.int64)
+    n_groups = int(g.max()) + 1 if g.size else 0
+    allowed = np.ones((b, n), bool) if allowed is None else np.broadcast_to(np.asarray(allowed, bool), full.shape)
+    gi = np.full((b, want), -1, np.int32)
+    gs = np.zeros((b, want), np.float32)
+    rep = np.full((b, want), -1, np.int32)
+    for i in range(b):
+        order = np.argsort(full[i], kind="stable")[::-1]            # the ranking rule: best first, ties -> larger index
+        order = order[allowed[i][order]]
+        best = np.full(n_groups, -1, np.int64)
+        best[g[order[::-1]]] = order[::-1]                           # the last write per group is its best member
+        score = np.zeros(n_groups, np.float32)
+        has = best >= 0
+        if agg == "sum":
+            a = allowed[i]
+            with np.errstate(invalid="ignore", over="ignore"):
+                score = np.bincount(g[a], weights=full[i][a].astype(np.float64), minlength=n_groups).astype(np.float32)
+        else:
+            score[has] = full[i][best[has]]
+        rank = np.argsort(score, kind="stable")[::-1]
+        rank = rank[has[rank]][:want]
+        gi[i, :len(rank)], gs[i, :len(rank)], rep[i, :len(rank)] = rank, score[rank], best[rank]
+    return gi, gs, rep
 
 
 def masked_minmax_rows(raw, allowed):
@@ -272,7 +308,7 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
                           linking_top_k: int, damping: float, passage_node_weight: float, ppr_iters: int,
                           num_to_retrieve: int, n_passages: int, timers=None, ppr_tol: float = 0.0,
                           ppr_max_iters: int = 0, ppr_base_iters_narrow: Optional[int] = None, doc_filter=None,
-                          filter_scope: str = "ranking"):
+                          filter_scope: str = "ranking", group_agg: Optional[str] = None, group_of=None):
     """The body of retrieve() (HippoRAG.py:459-480), shared by the mirror class below and by
     reference_adapter.attach(): phase A on the device, the recognition-memory filter on the host (rerank_facts
     :1659-1707), phase B on the device, in batches of eng.max_batch queries.  Yields (offset of the batch, [(doc ids,
@@ -294,11 +330,17 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
     doc_filter: packed uint32 words (engine.pack_mask) [W] for every query or [len(queries), W]: only those passages
     are ranked (a post-filter: the scores do not change); passed to the engine only when given.
     filter_scope="seeds": phase A takes its facts from the allowed passages and phase B normalises the passage prior over
-    them (include/hrag.h, scoped doc filter); needs doc_filter and an engine with fact sources."""
+    them (include/hrag.h, scoped doc filter); needs doc_filter and an engine with fact sources.
+    group_agg ("max" / "sum") with group_of (int array over the passages, already set on the engine): the rows rank
+    GROUPS -- doc ids are each group's best passage, doc scores the group scores, rows.group_idx the group ids."""
     import torch
     from .engine import host_copy_async, host_wait
     k_f = int(linking_top_k)
     want = max(1, min(int(num_to_retrieve), n_passages))
+    if group_agg is not None:
+        if group_of is None:
+            raise ValueError("group_agg needs group_of (the passage -> group table)")
+        want = max(1, min(want, int(np.max(group_of)) + 1))
     k_docs = min(want, eng.max_topk)
     # more documents than the device top-k holds (HippoRAG.py:501-507 slices any prefix of the full ranking): the
     # scores of all passages come back and are ranked here with the library's rule (score desc, larger index first)
@@ -375,10 +417,14 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
             kw["doc_filter"] = scope_rows(doc_filter, bt.lo, b)
             if scoped:
                 kw["filter_scope"] = "seeds"
+        if group_agg is not None:
+            kw["group_agg"] = group_agg
         if two_halves:
             bt.pending = eng.retrieve_converged_start(*args, **kw)
             o = bt.pending.out
             bt.copies = (host_copy_async(o.doc_idx), host_copy_async(o.doc_score))
+            if group_agg is not None:
+                bt.copies += (host_copy_async(o.group_idx),)
         else:                                       # an engine with the one-call form only (test doubles)
             bt.pending, bt.out = None, eng.retrieve_converged(*args, **kw)
         tick("ppr_time", t0)
@@ -397,7 +443,17 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
             out = bt.out
             d_idx, d_sc = out.doc_idx.cpu().numpy(), out.doc_score.cpu().numpy()
             flags = out.flags.cpu().numpy()
-        if beyond:
+        g_idx = None
+        if group_agg is not None and not beyond:
+            g_idx = (host_wait(bt.copies[2]).copy() if bt.pending is not None and not bt.pending.repeated
+                     else out.group_idx.cpu().numpy())
+        if beyond and group_agg is not None:
+            full = out.all_scores.cpu().numpy()
+            rows_w = None if doc_filter is None else (doc_filter if doc_filter.ndim == 1
+                                                      else doc_filter[bt.lo: bt.lo + len(bt.qs)])
+            g_idx, d_sc, d_idx = group_rank_rows(full, group_of, None if rows_w is None else
+                                                 unpack_mask(rows_w, full.shape[1]), want, group_agg)
+        elif beyond:
             full = out.all_scores.cpu().numpy()
             if doc_filter is not None:
                 rows_w = doc_filter if doc_filter.ndim == 1 else doc_filter[bt.lo: bt.lo + len(bt.qs)]
@@ -407,7 +463,7 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
                 d_sc = np.take_along_axis(full, d_idx.astype(np.int64), axis=1)
         tick("ppr_time", t0)
         rows = BatchRows()
-        rows.doc_idx, rows.doc_score = d_idx, d_sc
+        rows.doc_idx, rows.doc_score, rows.group_idx = d_idx, d_sc, g_idx
         for i in range(len(bt.qs)):
             if flags[i] & 4:      # :1541
                 raise AssertionError("count_nonzero(all_phrase_weights) != len(linking_score_map)")
@@ -433,6 +489,9 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
             yield finish(prev)
         prev = cur
     yield finish(prev)
+
+
+_NO_GROUP = object()     # a passage without the group_by key: a group of its own
 
 
 class HippoRAG:
@@ -593,6 +652,7 @@ class HippoRAG:
         """The engine-facing arrays from the current graph / stores (what prepare_retrieval_objects reads,
         HippoRAG.py:1287-1389)."""
         self._filter_cache = {}          # the passage list changed: every cached doc filter bitset is stale
+        self._group_cache = None         # ... and so is the passage -> group table of grouped retrieval
         g = self._graph
         self.node_name_to_vertex_idx = dict(g.index)
         csr = g.to_csr()
@@ -893,6 +953,87 @@ class HippoRAG:
                     else np.zeros((0, w), np.uint32))
         return self._filter_words(doc_filter)
 
+    # ------------------------------------------------------------------ grouped retrieval
+    def group_table(self, group_by):
+        """The passage -> group table of grouped retrieval: (group_of int32 [n_passages], values, sizes).  group_by: a
+        chunk-metadata key ("source_id" included, matched as the doc filter matches it) -- passages with equal values
+        share a group, a passage without the key is a group of its own (value None) -- or an int array over
+        passage_node_keys (equal entries share a group; the entry is the value).  Group ids are assigned in
+        first-occurrence order of passage position.  Cached until the passage list changes."""
+        n = len(self.passage_node_keys)
+        if isinstance(group_by, str):
+            cached = self.__dict__.get("_group_cache")
+            if cached is not None and cached[0] == group_by:
+                return cached[1]
+            meta = self.chunk_metadata
+            raw = [meta.get(k, {}).get(group_by, _NO_GROUP) if group_by in meta.get(k, {}) else _NO_GROUP
+                   for k in self.passage_node_keys]
+        elif isinstance(group_by, np.ndarray) or isinstance(group_by, (list, tuple)):
+            arr = np.asarray(group_by)
+            if arr.dtype.kind not in "iu":
+                raise TypeError(f"group_by array dtype {arr.dtype}: an integer array over the passages is expected")
+            if arr.shape != (n,):
+                raise ValueError(f"group_by array of shape {arr.shape}: ({n},) expected (one entry per passage)")
+            raw = arr.tolist()
+        else:
+            raise TypeError(f"group_by of type {type(group_by).__name__}: a metadata key or an int array over the passages")
+        ids, values, group_of = {}, [], np.empty(n, np.int32)
+        for p, v in enumerate(raw):
+            try:
+                key = ("v", v) if v is not _NO_GROUP else ("p", p)
+                hash(key)
+            except TypeError:                               # an unhashable metadata value: by its repr
+                key = ("r", repr(v))
+            if key not in ids:
+                ids[key] = len(values)
+                values.append(None if v is _NO_GROUP else v)
+            group_of[p] = ids[key]
+        table = (group_of, values, np.bincount(group_of, minlength=len(values)))
+        if isinstance(group_by, str):
+            self._group_cache = (group_by, table)
+        return table
+
+    def _grouping(self, group_by, group_agg):
+        """(group_agg or None, table or None) of a call: the arguments, else RetrievalConfig.group_by / group_agg."""
+        from .engine import check_group_agg
+        cfg = self.global_config
+        group_by = cfg.group_by if group_by is None else group_by
+        if group_by is None:
+            if group_agg is not None:
+                raise ValueError("group_agg needs group_by (a metadata key or an int array over the passages)")
+            return None, None
+        agg = cfg.group_agg if group_agg is None else group_agg
+        check_group_agg(agg)
+        if agg is None:
+            raise ValueError("group_agg must be 'max' or 'sum'")
+        return agg, self.group_table(group_by)
+
+    def _engine_groups(self, table):
+        """The engine ranks by `table` from here on (set once per table: it is part of the device index)."""
+        eng = self.engine
+        if getattr(eng, "_group_table_id", None) is not table[0]:
+            if not hasattr(eng, "set_passage_groups"):
+                raise NotImplementedError(f"{type(eng).__name__} does not serve grouped retrieval")
+            eng.set_passage_groups(table[0])
+            eng._group_table_id = table[0]
+
+    def _group_solutions(self, queries, rows, table, num_to_retrieve):
+        """QuerySolutions of a grouped batch: per entry the representative passage, the group score and the passage's
+        metadata plus {"group": value, "group_size": n}."""
+        texts, keys = self._result_tables()
+        _, values, sizes = table
+        meta = self.chunk_metadata
+        out = []
+        for i, q in enumerate(queries):
+            gi = np.asarray(rows.group_idx[i][:num_to_retrieve], np.int64)
+            keep = gi >= 0
+            gi, ids = gi[keep], np.asarray(rows.doc_idx[i][:num_to_retrieve], np.int64)[keep]
+            md = [{**meta.get(k, {}), "group": values[g], "group_size": int(sizes[g])} for k, g in zip(keys[ids], gi)]
+            out.append(QuerySolution(question=q, docs=texts[ids].tolist(),
+                                     doc_scores=np.asarray(rows.doc_score[i][:len(ids)]), doc_metadata=md,
+                                     graph_seeds=(rows[i][2] if len(rows) > i else None) or []))
+        return out
+
     def _scope(self, filter_scope, doc_filter) -> str:
         """The doc filter's scope of a call: the argument, else RetrievalConfig.doc_filter_scope; "ranking" without a
         filter."""
@@ -912,8 +1053,12 @@ class HippoRAG:
 
     # ------------------------------------------------------------------ retrieve :413-499
     def retrieve(self, queries: List[str], num_to_retrieve: Optional[int] = None,
-                 gold_docs: Optional[List[List[str]]] = None, doc_filter=None, filter_scope: Optional[str] = None):
-        """doc_filter: limit the ranked documents to a subset of the corpus (a post-filter: scores do not change) --
+                 gold_docs: Optional[List[List[str]]] = None, doc_filter=None, filter_scope: Optional[str] = None,
+                 group_by=None, group_agg: Optional[str] = None):
+        """group_by / group_agg (defaults RetrievalConfig.group_by / group_agg): rank GROUPS of passages -- source
+        documents -- instead of passages (group_table): num_to_retrieve counts groups, every entry is a group's best
+        passage with the group's score and {"group", "group_size"} in its metadata.
+        doc_filter: limit the ranked documents to a subset of the corpus (a post-filter: scores do not change) --
         a metadata dict {key: value} or {key: [values]} (values of a key: any of them; keys: all of them; matched
         against the chunk metadata, source_id included), a bool numpy array over passage_node_keys, or a list with one
         of those per query.  Each query gets the first num_to_retrieve allowed documents of its unfiltered ranking.
@@ -927,9 +1072,10 @@ class HippoRAG:
         self._ensure_ready()
         scope = self._scope(filter_scope, doc_filter)
         words = self._doc_filter_words(doc_filter, len(queries))
+        agg, table = self._grouping(group_by, group_agg)
         self.get_query_embeddings(queries)
         results: List[QuerySolution] = []
-        self._retrieve_into(results, queries, num_to_retrieve, words, scope)
+        self._retrieve_into(results, queries, num_to_retrieve, words, scope, agg, table)
         self.all_retrieval_time += time.time() - t_start
         logger.info("Total Retrieval Time %.2fs", self.all_retrieval_time)
         logger.info("Total Recognition Memory Time %.2fs", self.rerank_time)
@@ -938,9 +1084,13 @@ class HippoRAG:
             return results, self._recall(gold_docs, [r.docs for r in results])
         return results
 
-    def _retrieve_into(self, results, queries, num_to_retrieve, doc_filter=None, filter_scope: str = "ranking"):
+    def _retrieve_into(self, results, queries, num_to_retrieve, doc_filter=None, filter_scope: str = "ranking",
+                       group_agg=None, table=None):
         cfg = self.global_config
         extra = {} if doc_filter is None else {"doc_filter": doc_filter, "filter_scope": filter_scope}
+        if group_agg is not None:
+            self._engine_groups(table)
+            extra.update(group_agg=group_agg, group_of=table[0])
         # batch by batch: the lists of document strings of one batch are built while the device works on the next
         for lo, rows in iter_batched_retrieve(self.engine, queries, self._q_tensor, self.facts if self.fact_node_keys else [],
                                               self.rerank_filter, linking_top_k=cfg.linking_top_k, damping=cfg.damping,
@@ -950,12 +1100,16 @@ class HippoRAG:
                                               num_to_retrieve=num_to_retrieve, n_passages=len(self.passage_node_keys),
                                               timers=self, **extra):
             with gc_paused():       # around the materialisation only: the filter (an LLM call in production) runs outside
+                if group_agg is not None:
+                    results.extend(self._group_solutions(queries[lo: lo + len(rows)], rows, table, num_to_retrieve))
+                    continue
                 results.extend(self._build_query_solutions(queries[lo: lo + len(rows)], rows, num_to_retrieve))
 
     # ------------------------------------------------------------------ retrieve_ircot :509-558
     def retrieve_ircot(self, queries: List[str], max_qa_steps: int, num_to_retrieve: Optional[int] = None,
                        gold_docs: Optional[List[List[str]]] = None, reason_fn: Optional[Callable] = None,
-                       doc_filter=None, filter_scope: Optional[str] = None):
+                       doc_filter=None, filter_scope: Optional[str] = None, group_by=None,
+                       group_agg: Optional[str] = None):
         """Iterative retrieval: alternate retrieval and one reasoning step per query, merging the document
         scores by max (:526-543).  reason_fn(query, ranked_docs, thoughts) -> str stands for
         utils/qa_utils.reason_step (the IRCoT prompt + reader LLM are outside this package).  The reference
@@ -969,7 +1123,7 @@ class HippoRAG:
         if num_to_retrieve is None:
             num_to_retrieve = self.global_config.retrieval_top_k
         first = self.retrieve(list(queries), num_to_retrieve=num_to_retrieve, doc_filter=doc_filter,
-                              filter_scope=filter_scope)
+                              filter_scope=filter_scope, group_by=group_by, group_agg=group_agg)
         merged = [dict(zip(r.docs, r.doc_scores.tolist())) for r in first]
         meta = [dict(zip(r.docs, r.doc_metadata or [])) for r in first]
         thoughts: List[List[str]] = [[] for _ in queries]
@@ -990,7 +1144,7 @@ class HippoRAG:
                 break
             for i, r in zip(step_i, self.retrieve(step_q, num_to_retrieve=num_to_retrieve,
                                                   doc_filter=self._filter_rows(doc_filter, step_i),
-                                                  filter_scope=filter_scope)):
+                                                  filter_scope=filter_scope, group_by=group_by, group_agg=group_agg)):
                 for doc, score in zip(r.docs, r.doc_scores.tolist()):
                     merged[i][doc] = max(merged[i].get(doc, float("-inf")), score)
                 meta[i].update(dict(zip(r.docs, r.doc_metadata or [])))
@@ -1050,19 +1204,24 @@ class HippoRAG:
 
     # ------------------------------------------------------------------ retrieve_dpr :665-732
     def retrieve_dpr(self, queries: List[str], num_to_retrieve: Optional[int] = None,
-                     gold_docs: Optional[List[List[str]]] = None, doc_filter=None, filter_scope: Optional[str] = None):
+                     gold_docs: Optional[List[List[str]]] = None, doc_filter=None, filter_scope: Optional[str] = None,
+                     group_by=None, group_agg: Optional[str] = None):
         """Dense retrieval; doc_filter / filter_scope as in retrieve() ("seeds": the scores are normalised over the
-        allowed passages)."""
+        allowed passages); group_by / group_agg as in retrieve(), over the normalised dense scores."""
         cfg = self.global_config
         if num_to_retrieve is None:
             num_to_retrieve = cfg.retrieval_top_k
         self._ensure_ready()
         scope = self._scope(filter_scope, doc_filter)
         words = self._doc_filter_words(doc_filter, len(queries))
+        agg, table = self._grouping(group_by, group_agg)
         import torch
         self.get_query_embeddings(queries)
         eng = self.engine
         want = max(1, min(num_to_retrieve, len(self.passage_node_keys)))
+        if agg is not None:
+            self._engine_groups(table)
+            want = min(want, len(table[1]))
         k_docs = min(want, eng.max_topk)
         # more documents than the device top-k holds (:704-714 slices any prefix of the full ranking): the raw scores of all
         # passages come back and are normalised and ranked here with the library's rule (score desc, larger index first)
@@ -1080,6 +1239,9 @@ class HippoRAG:
             extra = {} if words is None else {
                 "doc_filter": torch.from_numpy(np.ascontiguousarray(rows_of(lo, len(qs))).view(np.int32)),
                 "filter_scope": scope}
+            if agg is not None:
+                gi, sc, idx = eng.dense_retrieve(self._q_tensor(qs, "passage"), k=k_docs, group_agg=agg, **extra)
+                return qs, host_copy_async(idx), host_copy_async(sc), host_copy_async(gi)
             idx, sc = eng.dense_retrieve(self._q_tensor(qs, "passage"), k=k_docs, **extra)
             return qs, host_copy_async(idx), host_copy_async(sc)
 
@@ -1087,21 +1249,31 @@ class HippoRAG:
         starts = list(range(0, len(queries), eng.max_batch))
         pending = enqueue(starts[0]) if starts else None
         for n in range(len(starts)):
-            qs, idx_h, sc_h = pending
+            qs, idx_h, sc_h, *gi_h = pending
             pending = enqueue(starts[n + 1]) if n + 1 < len(starts) else None
+            gi = None
             if beyond:
                 raw = host_wait(idx_h)[:, :len(self.passage_node_keys)]
                 if scope == "seeds":
                     full = masked_minmax_rows(raw, unpack_mask(rows_of(starts[n], len(qs)), raw.shape[1]))
                 else:
                     full = np.stack([min_max_normalize(r) for r in raw]).astype(np.float32)
-                if words is not None:
+                if agg is not None:
+                    gi, sc, idx = group_rank_rows(full, table[0], None if words is None else
+                                                  unpack_mask(rows_of(starts[n], len(qs)), full.shape[1]), want, agg)
+                elif words is not None:
                     idx, sc = rank_allowed(full, unpack_mask(rows_of(starts[n], len(qs)), full.shape[1]), want)
                 else:
                     idx = np.stack([np.argsort(r, kind="stable")[::-1][:want] for r in full]).astype(np.int32)
                     sc = np.take_along_axis(full, idx.astype(np.int64), axis=1)
             else:
                 idx, sc = host_wait(idx_h).copy(), host_wait(sc_h).copy()
+                gi = host_wait(gi_h[0]).copy() if gi_h else None
+            if agg is not None:
+                rows = BatchRows([(idx[i], sc[i], None) for i in range(len(qs))])
+                rows.doc_idx, rows.doc_score, rows.group_idx = idx, sc, gi
+                results.extend(self._group_solutions(qs, rows, table, num_to_retrieve))
+                continue
             with gc_paused():
                 for i, q in enumerate(qs):
                     r = self._build_retrieval_result(q, idx[i], sc[i], num_to_retrieve)

@@ -554,6 +554,80 @@ hrag_status hrag_dense_retrieve_scoped(hrag_engine *e, const uint16_t *q_pass_de
                                        int32_t *doc_idx_out_dev, float *doc_score_out_dev, hrag_stream stream,
                                        const uint32_t *filter_dev, int64_t filter_ld_words);
 
+/* ---- grouped retrieval: rank source documents, one best passage per source ----
+ * An index is an index of chunks (passages); a caller who indexed sources -- papers, files -- as several passages each
+ * asks for sources.  Every passage position p (the index doc_idx_out uses) belongs to one group g[p] in [0, n_groups),
+ * 1 <= n_groups <= n_passages.  For one query with final passage scores s[p] (exactly what hrag_last_doc_scores returns)
+ * and an optional doc filter:
+ *   - only ALLOWED passages take part (no filter: all of them); a group with no allowed member does not appear;
+ *   - REPRESENTATIVE of a group: its best allowed member under the ranking rule at the top of this header (score
+ *     descending, ties -> larger passage position, every NaN above +inf);
+ *   - GROUP SCORE: HRAG_GROUP_MAX -- the representative's score; HRAG_GROUP_SUM -- the sum of the allowed members' scores,
+ *     accumulated in fp64 in ascending passage position and rounded once to fp32: numpy's
+ *     np.bincount(g[allowed], weights=s[allowed].astype(np.float64), minlength=n_groups).astype(np.float32) bit for bit
+ *     (NaN propagates; for PPR scores this is the walker's mass in the source);
+ *   - groups are ranked by the same rule on (group score, group id): score descending, ties -> larger GROUP ID, NaN first.
+ *     The result is the first min(k, groups with an allowed member) groups; the slots beyond hold -1 / 0 / -1.
+ *   - queries on the DPR fallback (flags bit 0) follow the same rule on their normalised dense scores;
+ *     the dense call: on the min-max normalised scores it returns (over the allowed passages in the "seeds" scope).
+ * Consequence for HRAG_GROUP_MAX: when no two groups have bit-equal best scores, the grouped ranking is the ungrouped FULL
+ * ranking with every passage but the first of each group removed, ids and scores bit-identical to those entries.
+ * Nothing else changes: phase A, seeds, prior, PPR, the "seeds" scope, flags, residual and iteration outputs are those of
+ * the ungrouped call; with no groups set, or through the other entry points, every output is what it was.
+ * Cost: one read of the [B, n_passages] score rows (csrc/group.hip: no atomics -- one fixed-order chain of fp64 adds per
+ * (query, group), so results are bitwise reproducible), then the ranking over n_groups instead of n_passages entries. */
+#define HRAG_GROUP_MAX 0
+#define HRAG_GROUP_SUM 1
+
+/* The passage -> group table, host array group_of [n_passages] with 0 <= group_of[p] < n_groups (HRAG_EINVAL otherwise;
+ * a group id that no passage carries is legal and never appears).  Part of the shared INDEX: accepted on a root engine
+ * that has no live workspaces and is not inside a call (HRAG_EINVAL / HRAG_EBUSY otherwise), on neither a workspace handle
+ * nor a row-shard engine; workspaces created afterwards borrow the table and get their own group buffers.  Calling it
+ * again replaces the table; group_of == NULL clears it (n_groups is then ignored).  The per-call group buffers are
+ * allocated here for the root and at creation for every later workspace -- never inside a retrieve call. */
+hrag_status hrag_engine_set_passage_groups(hrag_engine *e, const int32_t *group_of, int64_t n_groups);
+
+/* hrag_retrieve_filtered / hrag_retrieve_scored_filtered / hrag_dense_retrieve_filtered, grouped.  filter_dev may be NULL
+ * (every passage); scoped != 0: the "seeds" scope of the scoped calls above (needs a filter).  agg: HRAG_GROUP_MAX /
+ * HRAG_GROUP_SUM.  Outputs [B, k], k <= max_topk: group ids, group scores, the representative passage position of each
+ * ranked group.  doc_idx_out_dev / doc_score_out_dev may be NULL; when given they receive the ungrouped ranking of the
+ * same call (k entries, as the _filtered form writes them).  Without a group table: HRAG_EINVAL. */
+hrag_status hrag_retrieve_grouped(hrag_engine *e, const uint16_t *q_pass_dev, int32_t batch,
+                                  const int32_t *kept_idx_dev, const float *kept_score_dev,
+                                  const int32_t *kept_count_dev, int32_t kf, int32_t link_top_k,
+                                  float damping, float passage_node_weight, int32_t ppr_iters,
+                                  int32_t ppr_max_iters, float ppr_tol, int32_t k,
+                                  int32_t *doc_idx_out_dev, float *doc_score_out_dev,
+                                  int32_t *flags_out_dev, float *residual_out_dev, int32_t *iters_out_dev,
+                                  hrag_stream stream, const uint32_t *filter_dev, int64_t filter_ld_words,
+                                  int32_t scoped, int32_t agg, int32_t *group_idx_out_dev, float *group_score_out_dev,
+                                  int32_t *best_doc_idx_out_dev);
+hrag_status hrag_retrieve_scored_grouped(hrag_engine *e, const float *pass_scores_dev, int64_t pass_ld, int32_t batch,
+                                         const int32_t *kept_idx_dev, const float *kept_score_dev,
+                                         const int32_t *kept_count_dev, int32_t kf, int32_t link_top_k, float damping,
+                                         float passage_node_weight, int32_t ppr_iters, int32_t ppr_max_iters,
+                                         float ppr_tol, int32_t k, int32_t *doc_idx_out_dev, float *doc_score_out_dev,
+                                         int32_t *flags_out_dev, float *residual_out_dev, int32_t *iters_out_dev,
+                                         hrag_stream stream, const uint32_t *filter_dev, int64_t filter_ld_words,
+                                         int32_t scoped, int32_t agg, int32_t *group_idx_out_dev,
+                                         float *group_score_out_dev, int32_t *best_doc_idx_out_dev);
+hrag_status hrag_dense_retrieve_grouped(hrag_engine *e, const uint16_t *q_pass_dev, int32_t batch, int32_t k,
+                                        int32_t *doc_idx_out_dev, float *doc_score_out_dev, hrag_stream stream,
+                                        const uint32_t *filter_dev, int64_t filter_ld_words, int32_t scoped, int32_t agg,
+                                        int32_t *group_idx_out_dev, float *group_score_out_dev,
+                                        int32_t *best_doc_idx_out_dev);
+
+/* The group reduction alone, engine-free: scores_dev fp32 [batch, ld] (n valid entries per row), the groups as a device
+ * CSR -- group_ptr_dev int64 [n_groups + 1] from 0 to n, members_dev int32 [n] passage positions, ascending inside a
+ * group (the order HRAG_GROUP_SUM adds in) -- and optionally the doc filter (format and filter_ld_words /
+ * filter_bit_offset rule of hrag_topk_rows_masked; NULL: every element).  Writes gscore_out_dev fp32 and gbest_out_dev
+ * int32, both [batch, out_ld], out_ld >= n_groups: the group score and the representative (-1 and score 0 for a group
+ * without an allowed member).  A member outside [0, n) counts as not allowed. */
+hrag_status hrag_group_rows(const float *scores_dev, int32_t batch, int64_t n, int64_t ld, const int64_t *group_ptr_dev,
+                            const int32_t *members_dev, int64_t n_groups, int32_t agg, const uint32_t *filter_dev,
+                            int64_t filter_ld_words, int64_t filter_bit_offset, float *gscore_out_dev,
+                            int32_t *gbest_out_dev, int64_t out_ld, hrag_stream stream);
+
 /* ---- lower-level seams (used by the per-method adapters and by the parity tests) ---- */
 
 /* np.dot(embeddings, q.T) (HippoRAG.py:1459 / :1496): raw cosine scores.
