@@ -136,6 +136,8 @@ SIGNATURES = {
                                                _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P, _P, _P]),
     "hrag_dense_retrieve_grouped": (C.c_int, [_P, _P, _I32, _I32, _P, _P, _P, _P, _I64, _I32, _I32, _P, _P, _P]),
     "hrag_group_rows": (C.c_int, [_P, _I32, _I64, _I64, _P, _P, _I64, _I32, _P, _I64, _I64, _P, _P, _I64, _P]),
+    "hrag_group_hits_rows": (C.c_int, [_P, _I32, _I64, _I64, _P, _P, _I64, _P, _I32, _I32, _P, _I64, _I64, _P, _P, _P]),
+    "hrag_last_group_hits": (C.c_int, [_P, _I32, _P, _I32, _I32, _P, _I64, _P, _P, _P]),
     "hrag_ppr_sweeps": (C.c_int, [_P, _I32, _I32, _F32, _I32, _P]),
     "hrag_ppr_layout": (C.c_int, [_P, _I32, C.POINTER(_I32), C.POINTER(_I32)]),
     "hrag_row_minmax": (C.c_int, [_P, _I32, _I64, _I64, _P, _P, _P]),

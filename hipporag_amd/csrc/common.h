@@ -528,6 +528,13 @@ hrag_status launch_minmax_rows(const float *src, int32_t batch, int64_t n, int64
 hrag_status launch_group_best(const int32_t *group_idx, const int32_t *gbest, int64_t gld, int64_t n_groups, int32_t k,
                               int32_t batch, int32_t *out, hipStream_t s);
 
+// the hits of ranked groups (include/hrag.h, hrag_group_hits_rows): for every entry of group_idx int32 [batch][k] (-1 or an
+// id outside [0, n_groups): an empty row) the first `hits` allowed members of that group by the ranking rule -> hit_idx
+// int32 / hit_score fp32 [batch][k][hits], -1 / 0 beyond the allowed members
+hrag_status launch_group_hits(const float *scores, int32_t batch, int64_t n, int64_t ld, const int64_t *group_ptr,
+                              const int32_t *members, int64_t n_groups, const int32_t *group_idx, int32_t k, int32_t hits,
+                              const TopkMask *mask, int32_t *hit_idx, float *hit_score, hipStream_t s);
+
 // knn.hip : fp32 rows -> the 3 * dim bf16 layout of HRAG_F32_SPLIT engines ([hi | lo | hi]; queries [hi | hi | lo])
 hrag_status launch_split3(const float *x, int64_t rows, int32_t dim, int32_t as_query, uint16_t *out, hipStream_t s,
                           int32_t normalize = 0);

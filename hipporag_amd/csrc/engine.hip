@@ -1073,6 +1073,7 @@ hrag_status hrag_workspace_create(hrag_engine *e, hrag_engine **out) {
     w->state_elems = w->state16_elems = w->state8_bytes = 0;
     w->index_bytes = 0; w->workspace_bytes = 0;
     w->last_ppr_state = 0;
+    w->rows_batch = 0;                                           // its own score rows: nothing written yet
     root->n_workspaces.v.fetch_add(1);
     const hrag_status st = alloc_workspace(w);
     if (st != HRAG_OK) { free_engine(w); return st; }
@@ -1419,6 +1420,7 @@ static hrag_status retrieve_impl(hrag_engine *e, const uint16_t *q_pass, const f
     HRAG_REQUIRE(e->n_passages >= 1, "engine has no passages");
     hipStream_t s = (hipStream_t)stream;
     HRAG_ENGINE_CALL(e, stream);
+    e->rows_batch = 0;   // the score rows are being rewritten (hrag_last_group_hits); set again when all is enqueued
     const bool sv = use_sv(e, batch);
     const bool f8 = !sv && batch > 64 && e->d_pool8[0] && ppr8_usable(e, batch, ppr_iters, damping);
     const int f8_iters = ppr_iters;
@@ -1612,6 +1614,7 @@ static hrag_status retrieve_impl(hrag_engine *e, const uint16_t *q_pass, const f
     e->last.n_slabs = lay.n_slabs;
     e->last.slab_width = f8 ? 128 : lay.bc;
     e->last_ppr_state = f8 ? HRAG_PPR_STATE_FP8 : f16 ? HRAG_PPR_STATE_F16 : sv ? HRAG_PPR_STATE_SMALL : HRAG_PPR_STATE_F32;
+    e->rows_batch = batch;
     e->counters.retrieve.fetch_add(1);
     e->counters.queries.fetch_add(batch);
     return HRAG_OK;
@@ -1732,9 +1735,11 @@ static hrag_status dense_impl(hrag_engine *e, const uint16_t *q_pass, int32_t ba
         HRAG_TRY(rank_rows(e, e->d_spass, batch, e->n_passages, k, 0, kNormMinMax, doc_idx_out, doc_score_out, s, mask));
     if (grp) {
         // the groups are formed over the scores the dense ranking returns: the rows normalised as its top-k does
+        e->rows_batch = 0;
         HRAG_TRY(launch_row_minmax(e->d_spass, batch, e->n_passages, e->ld_p, e->d_mn_p, e->d_mx_p, s));
         HRAG_TRY(launch_minmax_rows(e->d_spass, batch, e->n_passages, e->ld_p, e->d_mn_p, e->d_mx_p, e->d_doc, e->ld_p, s));
         HRAG_TRY(rank_groups(e, e->d_doc, batch, k, mask, grp, s));
+        e->rows_batch = batch;
     }
     return HRAG_OK;
 }
@@ -1861,6 +1866,44 @@ hrag_status hrag_group_rows(const float *scores, int32_t batch, int64_t n, int64
     const TopkMask m{filter_dev, filter_ld_words, filter_bit_offset};
     return launch_group_reduce(scores, batch, n, ld, group_ptr, members, n_groups, agg, filter_dev ? &m : nullptr,
                                gscore_out, gbest_out, out_ld, nullptr, 0, (hipStream_t)stream);
+}
+
+hrag_status hrag_group_hits_rows(const float *scores, int32_t batch, int64_t n, int64_t ld, const int64_t *group_ptr,
+                                 const int32_t *members, int64_t n_groups, const int32_t *group_idx, int32_t k, int32_t hits,
+                                 const uint32_t *filter_dev, int64_t filter_ld_words, int64_t filter_bit_offset,
+                                 int32_t *hit_idx_out, float *hit_score_out, hrag_stream stream) {
+    const TopkMask m{filter_dev, filter_ld_words, filter_bit_offset};
+    return launch_group_hits(scores, batch, n, ld, group_ptr, members, n_groups, group_idx, k, hits,
+                             filter_dev ? &m : nullptr, hit_idx_out, hit_score_out, (hipStream_t)stream);
+}
+
+hrag_status hrag_last_group_hits(hrag_engine *e, int32_t batch, const int32_t *group_idx, int32_t k, int32_t hits,
+                                 const uint32_t *filter_dev, int64_t filter_ld_words, int32_t *hit_idx_out,
+                                 float *hit_score_out, hrag_stream stream) {
+    HRAG_TRY(check_batch(e, batch));
+    HRAG_REQUIRE(e->p_rows == e->n_passages && e->n_rows == e->V,
+                 "hrag_last_group_hits on a row-shard engine: a group's members span the shards (grouped retrieval is "
+                 "served by the unsharded engine only)");
+    if (!e->d_grp_ptr) {
+        set_error("no passage groups on this engine: call hrag_engine_set_passage_groups first (on the root engine, before "
+                  "its workspaces are created)");
+        return HRAG_EINVAL;
+    }
+    TopkMask fm;
+    const TopkMask *mask = nullptr;
+    HRAG_TRY(doc_filter(e, filter_dev, filter_ld_words, fm, &mask));
+    HRAG_REQUIRE(group_idx && hit_idx_out && hit_score_out, "NULL argument");
+    HRAG_REQUIRE(k >= 1, "k=%d: at least 1", k);
+    HRAG_REQUIRE(hits >= 1 && hits <= HRAG_GROUP_HITS_MAX, "hits=%d outside [1, HRAG_GROUP_HITS_MAX=%d]", hits,
+                 HRAG_GROUP_HITS_MAX);
+    HRAG_ENGINE_CALL(e, stream);   // (rows_batch is read inside the call: another thread's retrieve cannot be rewriting it)
+    HRAG_REQUIRE(e->d_doc && e->rows_batch >= 1,
+                 "no score rows on this handle: hrag_last_group_hits follows a retrieve, a scored or a grouped dense call "
+                 "(the ungrouped dense calls do not write the rows)");
+    HRAG_REQUIRE(batch <= e->rows_batch, "batch=%d exceeds the %d queries of the call that wrote the score rows", batch,
+                 e->rows_batch);
+    return launch_group_hits(e->d_doc, batch, e->n_passages, e->ld_p, e->d_grp_ptr, e->d_grp_members, e->n_groups, group_idx,
+                             k, hits, mask, hit_idx_out, hit_score_out, (hipStream_t)stream);
 }
 
 hrag_status hrag_ppr(hrag_engine *e, const float *reset, int32_t batch, float damping, int32_t iters,

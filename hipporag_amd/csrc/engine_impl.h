@@ -187,6 +187,9 @@ struct hrag_engine {
     float *d_gscore = nullptr;
     int32_t *d_gbest = nullptr;
     uint32_t *d_gmask = nullptr;
+    // hrag_last_group_hits: the batch of the call that last wrote the score rows d_doc of this handle (a retrieve, a scored
+    // or a GROUPED dense call; the ungrouped dense calls rank d_spass and leave d_doc alone); 0: none yet
+    int32_t rows_batch = 0;
     // two-stage fp16 PPR (ppr16.hip): SELL-8 matrix + fp16 state, unsharded engines with max_batch > 8
     bool f16_ready = false;   // fp16 state buffers present (max_batch > 8)
     int32_t f16_max_batch = 0;  // ... sized for this many queries (64 when the fp8 path serves the larger batches)

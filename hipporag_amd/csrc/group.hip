@@ -19,6 +19,16 @@
 // met the group walks it together, 64 members per step -- coalesced where the members are consecutive, the key maximum per
 // lane then across lanes; for SUM every lane adds the 64 scores of the step in member order (v_readlane broadcasts), so
 // the chain is the sequential one: the loads are parallel, the adds are not, by definition.
+//
+// group_hits_kernel<MASKED> (hrag_group_hits_rows / hrag_last_group_hits): the m best allowed members of each RANKED group.
+// One wavefront owns one (query, ranked slot): it walks the group's members 64 per step like the long-group path above,
+// every lane forming the ranking key of its member (0: not allowed), and keeps the best keys seen so far SORTED ACROSS ITS
+// LANES -- lane i holds the i-th best.  A step whose keys all lie below the held m-th key is skipped after one ballot;
+// otherwise the step's keys are bitonic-sorted across the lanes, the elementwise maximum of the held list against the
+// reversed new list is a bitonic sequence holding the best 64 of both, and the 6-stage bitonic merge sorts it again.  Keys
+// are unique (the position is their low half), so the result does not depend on any order of execution; no atomics, no
+// scratch, no LDS.  Lanes < m write the position and the score decoded from the key -- the canonical quiet NaN, -0 as +0,
+// as every ranking returns scores.
 #include <algorithm>
 
 #include "common.h"
@@ -126,6 +136,72 @@ __global__ __launch_bounds__(kGroupThreads) void group_reduce_kernel(
     }
 }
 
+// compare-exchange with the lane `o` away: the lane that `keep_max` names keeps the larger key, its partner the smaller
+__device__ __forceinline__ uint64_t cmp_xchg(uint64_t v, int o, bool keep_max) {
+    const uint64_t other = shfl_xor_u64(v, o);
+    return (other > v) == keep_max ? other : v;
+}
+
+constexpr int kHitsThreads = 256;   // four wavefronts, one (query, ranked slot) each
+
+template <bool MASKED>
+__global__ __launch_bounds__(kHitsThreads) void group_hits_kernel(
+    const float *__restrict__ scores, int64_t n, int64_t ld, const int64_t *__restrict__ group_ptr,
+    const int32_t *__restrict__ members, int64_t n_groups, const uint32_t *__restrict__ mask, int64_t mask_ld,
+    int64_t mask_bit0, const int32_t *__restrict__ group_idx, int32_t k, int32_t hits, int32_t *__restrict__ hit_idx,
+    float *__restrict__ hit_score) {
+    const int q = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const int64_t slot = (int64_t)blockIdx.x * (kHitsThreads / 64) + (threadIdx.x >> 6);
+    if (slot >= k) return;                                   // wavefront-uniform
+    const float *row = scores + (size_t)q * ld;
+    const uint32_t *mrow = MASKED ? mask + (size_t)q * mask_ld : nullptr;
+    auto allowed = [&](int32_t m) -> bool {
+        if ((uint64_t)(uint32_t)m >= (uint64_t)n) return false;   // a member outside the row is never read
+        if constexpr (MASKED) {
+            const int64_t b = mask_bit0 + m;
+            return (mrow[b >> 5] >> (b & 31)) & 1u;
+        }
+        return true;
+    };
+    const int64_t g = group_idx[(size_t)q * k + slot];
+    int64_t beg = 0, end = 0;
+    if (g >= 0 && g < n_groups) {                            // a padded slot (-1) or an id outside the table: an empty row
+        beg = group_ptr[g];
+        end = group_ptr[g + 1];
+        beg = beg < 0 ? 0 : beg > n ? n : beg;               // the member array has n entries
+        end = end < beg ? beg : end > n ? n : end;
+    }
+    uint64_t held = 0;                                       // lane i: the i-th best key so far (0: none)
+    for (int64_t j0 = beg; j0 < end; j0 += 64) {
+        const int64_t j = j0 + lane;
+        uint64_t key = 0;
+        if (j < end) {
+            const int32_t m = members[j];
+            if (allowed(m)) key = rank_key(row[m], (uint32_t)m);
+        }
+        if (!__ballot(key > shfl_u64(held, hits - 1))) continue;   // nothing here enters the best `hits`
+        // bitonic sort, descending over the lanes: blocks of kk lanes alternate descending / ascending until kk = 64
+#pragma unroll
+        for (int kk = 2; kk <= 64; kk <<= 1)
+#pragma unroll
+            for (int o = kk >> 1; o > 0; o >>= 1) key = cmp_xchg(key, o, ((lane & o) == 0) == ((lane & kk) == 0));
+        if (j0 != beg) {
+            // held (descending) against the new keys reversed (ascending): the maxima are the best 64 of both, bitonic
+            const uint64_t rev = shfl_u64(key, 63 - lane);
+            key = rev > held ? rev : held;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) key = cmp_xchg(key, o, (lane & o) == 0);
+        }
+        held = key;
+    }
+    if (lane < hits) {
+        const size_t at = ((size_t)q * k + slot) * hits + lane;
+        hit_idx[at] = held ? (int32_t)(uint32_t)held : -1;
+        hit_score[at] = held ? ordered_to_f32((uint32_t)(held >> 32)) : 0.f;
+    }
+}
+
 // out[q][i] = (s - mn[q]) / (mx[q] - mn[q]), a zero range giving 1: the normalisation the dense ranking applies to the
 // scores it returns (topk.hip minmax_norm), as a row so that groups can be formed over it
 __global__ void minmax_rows_kernel(const float *__restrict__ src, int64_t n, int64_t ld, const float *__restrict__ mn,
@@ -179,6 +255,35 @@ hrag_status launch_group_reduce(const float *scores, int32_t batch, int64_t n, i
         if (mask) HRAG_GROUP_LAUNCH(HRAG_GROUP_MAX, true); else HRAG_GROUP_LAUNCH(HRAG_GROUP_MAX, false);
     }
 #undef HRAG_GROUP_LAUNCH
+    HRAG_LAUNCH_CHECK();
+    return HRAG_OK;
+}
+
+hrag_status launch_group_hits(const float *scores, int32_t batch, int64_t n, int64_t ld, const int64_t *group_ptr,
+                              const int32_t *members, int64_t n_groups, const int32_t *group_idx, int32_t k, int32_t hits,
+                              const TopkMask *mask, int32_t *hit_idx, float *hit_score, hipStream_t s) {
+    HRAG_REQUIRE(scores && group_ptr && members && group_idx && hit_idx && hit_score, "NULL argument");
+    HRAG_REQUIRE(batch >= 1 && batch <= 65535, "batch=%d outside [1, 65535]", batch);
+    HRAG_REQUIRE(n >= 1 && n < ((int64_t)1 << 31) && ld >= n, "n=%lld / ld=%lld: 1 <= n < 2^31, ld >= n", (long long)n,
+                 (long long)ld);
+    HRAG_REQUIRE(n_groups >= 1 && n_groups <= n, "n_groups=%lld outside [1, n=%lld]", (long long)n_groups, (long long)n);
+    HRAG_REQUIRE(k >= 1, "k=%d: at least 1", k);
+    HRAG_REQUIRE(hits >= 1 && hits <= HRAG_GROUP_HITS_MAX, "hits=%d outside [1, HRAG_GROUP_HITS_MAX=%d]", hits,
+                 HRAG_GROUP_HITS_MAX);
+    if (mask) {
+        HRAG_REQUIRE(mask->words != nullptr && mask->bit_offset >= 0, "bad filter");
+        HRAG_REQUIRE(mask->ld_words == 0 || mask->ld_words >= (mask->bit_offset + n + 31) / 32,
+                     "filter_ld_words=%lld: 0 (one row for the batch) or >= ceil((bit offset + n) / 32) = %lld",
+                     (long long)mask->ld_words, (long long)((mask->bit_offset + n + 31) / 32));
+    }
+    const dim3 grid((unsigned)ceil_div(k, kHitsThreads / 64), (unsigned)batch);
+    if (mask)
+        hipLaunchKernelGGL((group_hits_kernel<true>), grid, dim3(kHitsThreads), 0, s, scores, n, ld, group_ptr, members,
+                           n_groups, mask->words, mask->ld_words, mask->bit_offset, group_idx, k, hits, hit_idx, hit_score);
+    else
+        hipLaunchKernelGGL((group_hits_kernel<false>), grid, dim3(kHitsThreads), 0, s, scores, n, ld, group_ptr, members,
+                           n_groups, (const uint32_t *)nullptr, (int64_t)0, (int64_t)0, group_idx, k, hits, hit_idx,
+                           hit_score);
     HRAG_LAUNCH_CHECK();
     return HRAG_OK;
 }

@@ -432,7 +432,8 @@ class ShardedRetriever:
 
     def retrieve(self, q_pass, kept_idx, kept_score, kept_count, *, link_top_k=5, damping=0.5,
                  passage_node_weight=0.05, ppr_iters=20, k=200, ppr_tol=0.0, ppr_max_iters=0,
-                 check_saturation=True, doc_filter=None, filter_scope: str = "ranking", group_agg=None):
+                 check_saturation=True, doc_filter=None, filter_scope: str = "ranking", group_agg=None,
+                 group_hits=None):
         """Returns (doc ids, doc scores, flags) -- and with ppr_tol > 0 additionally (residual, sweeps used): the
         convergence contract of hrag_retrieve on the shards.  Every shard measures the relative update of ITS
         passages; the measures are all-reduced (MAX) before every decision, so all shards run the same steps.
@@ -445,7 +446,7 @@ class ShardedRetriever:
         filter_scope="seeds": the passage prior and the DPR fallback normalised over the allowed passages of every shard
         (= HippoRAGEngine.retrieve(filter_scope="seeds"); the kept facts from score_facts(scope_filter=))."""
         from .engine import refuse_group_agg
-        refuse_group_agg("ShardedRetriever", {"group_agg": group_agg})
+        refuse_group_agg("ShardedRetriever", {"group_agg": group_agg, "group_hits": group_hits})
         scoped = serve_seeds_scope(getattr(self, "st", None), filter_scope)
         if scoped:
             from .engine import check_filter_scope
@@ -631,11 +632,11 @@ class NativeShardedRetriever:
 
     def retrieve(self, q_pass, kept_idx, kept_score, kept_count, *, link_top_k=5, damping=0.5, passage_node_weight=0.05,
                  ppr_iters=20, k=200, ppr_tol=0.0, ppr_max_iters=0, check_saturation=True, doc_filter=None,
-                 filter_scope: str = "ranking", group_agg=None):
+                 filter_scope: str = "ranking", group_agg=None, group_hits=None):
         """Same contract as ShardedRetriever.retrieve: (doc ids, doc scores, flags[, residual, sweeps used]);
         doc_filter: hrag_shard_retrieve_filtered with the global filter (filter_scope="seeds": hrag_shard_retrieve_scoped)."""
         from .engine import refuse_group_agg
-        refuse_group_agg("NativeShardedRetriever", {"group_agg": group_agg})
+        refuse_group_agg("NativeShardedRetriever", {"group_agg": group_agg, "group_hits": group_hits})
         scoped = serve_seeds_scope(getattr(self, "st", None), filter_scope)
         if scoped:
             from .engine import check_filter_scope
@@ -725,6 +726,7 @@ class HybridRetriever:
         from .engine import refuse_group_agg
         refuse_group_agg("HybridRetriever", kw)
         kw.pop("group_agg", None)
+        kw.pop("group_hits", None)
         scope = kw.pop("filter_scope", "ranking")
         if serve_seeds_scope(getattr(self, "sim", None), scope):
             kw["filter_scope"] = scope

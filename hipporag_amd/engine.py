@@ -56,6 +56,7 @@ def pack_mask(mask) -> np.ndarray:
 
 FILTER_SCOPES = ("ranking", "seeds")
 GROUP_AGGS = {"max": 0, "sum": 1}      # HRAG_GROUP_MAX / HRAG_GROUP_SUM
+GROUP_HITS_MAX = 64                    # HRAG_GROUP_HITS_MAX
 
 
 def check_group_agg(group_agg) -> Optional[int]:
@@ -65,6 +66,20 @@ def check_group_agg(group_agg) -> Optional[int]:
     if group_agg not in GROUP_AGGS:
         raise ValueError(f"group_agg={group_agg!r}: None, 'max' or 'sum' expected")
     return GROUP_AGGS[group_agg]
+
+
+def check_group_hits(group_hits, group_agg) -> Optional[int]:
+    """None (the representative only) or m, the passages wanted per ranked group (include/hrag.h, group hits): an int in
+    [1, GROUP_HITS_MAX], valid only on a grouped call."""
+    if group_hits is None:
+        return None
+    if group_agg is None:
+        raise ValueError("group_hits needs group_agg: it asks for the best passages of each ranked GROUP")
+    if isinstance(group_hits, bool) or not isinstance(group_hits, (int, np.integer)):
+        raise ValueError(f"group_hits={group_hits!r}: None or an int in [1, {GROUP_HITS_MAX}] expected")
+    if not 1 <= int(group_hits) <= GROUP_HITS_MAX:
+        raise ValueError(f"group_hits={group_hits}: outside [1, {GROUP_HITS_MAX}]")
+    return int(group_hits)
 
 
 def group_table_csr(group_of, n_groups: int):
@@ -81,6 +96,9 @@ def refuse_group_agg(who: str, kw: dict) -> None:
     if kw.get("group_agg") is not None:
         raise NotImplementedError(f"{who} does not serve group_agg: a group's members span the row shards and a sum across "
                                   "shards is not bit-reproducible without a defined order -- use HippoRAGEngine.retrieve")
+    if kw.get("group_hits") is not None:
+        raise NotImplementedError(f"{who} does not serve group_hits (the best passages of each ranked group): use "
+                                  "HippoRAGEngine.retrieve")
 
 
 def check_filter_scope(filter_scope: str, doc_filter) -> bool:
@@ -171,6 +189,10 @@ class RetrieveOutput:
     all_scores: "object" = None  # torch fp32 [B, Np] (retrieve_converged(want_all_scores=True)): every passage's score
     group_idx: "object" = None   # grouped call (group_agg=): torch int32 [B, k] group ids, best first; doc_idx then holds
                                  # each ranked group's representative passage and doc_score the group score
+
+    hit_idx: "object" = None     # group_hits=m: torch int32 [B, k, m], the m best allowed passages of each ranked group, best
+                                 # first (entry 0 is the representative), -1 beyond the group's allowed members
+    hit_score: "object" = None   # torch fp32 [B, k, m]: each hit's own passage score (0 where hit_idx is -1)
 
     @property
     def group_score(self):       # the grouped call's names for the two tensors above
@@ -273,6 +295,8 @@ class PendingRetrieve:
             out.doc_idx[rt], out.doc_score[rt] = o2.doc_idx, o2.doc_score
             if out.group_idx is not None:
                 out.group_idx[rt] = o2.group_idx
+            if out.hit_idx is not None:
+                out.hit_idx[rt], out.hit_score[rt] = o2.hit_idx, o2.hit_score
             out.flags[rt], out.residual[rt], out.iters_used[rt] = o2.flags, o2.residual, o2.iters_used
             if self.want_all_scores:
                 out.all_scores[rt] = o2.all_scores
@@ -582,7 +606,7 @@ class HippoRAGEngine:
                  damping: float = 0.5, passage_node_weight: float = 0.05, ppr_iters: int = 20,
                  k: int = 200, ppr_tol: float = 0.0, ppr_max_iters: int = 0,
                  want_residual: bool = True, doc_filter=None, filter_scope: str = "ranking",
-                 group_agg: Optional[str] = None) -> RetrieveOutput:
+                 group_agg: Optional[str] = None, group_hits: Optional[int] = None) -> RetrieveOutput:
         """Phase B: seeds + passage prior + PPR + ranking (DPR ranking where kept_count == 0).
         ppr_tol / ppr_max_iters: the convergence contract of include/hrag.h (0 = exactly ppr_iters sweeps);
         the output carries the per-query residual and the sweeps that ran.
@@ -591,10 +615,13 @@ class HippoRAGEngine:
         filter_scope="seeds": the passage prior and the DPR fallback are normalised over the allowed passages as well
         (hrag_retrieve_scoped; the kept facts should come from score_facts(scope_filter=) with the same filter).
         group_agg="max" | "sum" (after set_passage_groups; hrag_retrieve_grouped): the k best GROUPS -- group_idx, their
-        scores (group_score = doc_score) and each group's best passage (best_doc_idx = doc_idx); composes with both."""
+        scores (group_score = doc_score) and each group's best passage (best_doc_idx = doc_idx); composes with both.
+        group_hits=m (with group_agg; hrag_last_group_hits right behind the grouped call): hit_idx / hit_score [B, k, m],
+        the m best allowed passages of each ranked group with their own scores; every other output is unchanged."""
         torch = _torch()
         scoped = check_filter_scope(filter_scope, doc_filter)
         agg = check_group_agg(group_agg)
+        hits = check_group_hits(group_hits, group_agg)
         q = self._q(q_pass)
         b = q.shape[0]
         kept_idx = kept_idx.to(self.device, torch.int32).contiguous()
@@ -614,7 +641,7 @@ class HippoRAGEngine:
                 used.data_ptr() if used is not None else None, _stream())
         if agg is not None:
             return self._grouped(self._lib.hrag_retrieve_grouped, args, 14, doc_filter, scoped, agg, b, k,
-                                 RetrieveOutput(idx, sc, flags, resid, used))
+                                 RetrieveOutput(idx, sc, flags, resid, used), hits)
         if doc_filter is None:
             check(self._lib.hrag_retrieve(*args))
         else:
@@ -623,8 +650,9 @@ class HippoRAGEngine:
             check(fn(*args, fw.data_ptr(), fld))
         return RetrieveOutput(idx, sc, flags, resid, used)
 
-    def _grouped(self, fn, args, doc_at, doc_filter, scoped, agg, b, k, out):
-        """A grouped call: `args` of the ungrouped form with the two ungrouped outputs (at doc_at) left out."""
+    def _grouped(self, fn, args, doc_at, doc_filter, scoped, agg, b, k, out, hits=None):
+        """A grouped call: `args` of the ungrouped form with the two ungrouped outputs (at doc_at) left out.  hits: the
+        follow-up hrag_last_group_hits over the rows this call leaves, with its group ids and its filter."""
         torch = _torch()
         fw, fld = (None, 0) if doc_filter is None else doc_filter_words(doc_filter, self.n_passages, b, self.device)
         gi = self._empty((b, k), torch.int32)
@@ -632,16 +660,34 @@ class HippoRAGEngine:
         check(fn(*args, fw.data_ptr() if fw is not None else None, fld, 1 if scoped else 0, agg, gi.data_ptr(),
                  out.doc_score.data_ptr(), out.doc_idx.data_ptr()))
         out.group_idx = gi
+        if hits is not None:
+            out.hit_idx, out.hit_score = self.last_group_hits(gi, hits, fw, fld)
         return out
+
+    def last_group_hits(self, group_idx, hits: int, filter_words=None, filter_ld: int = 0):
+        """(hit_idx int32, hit_score fp32) [B, k, hits] for group ids int32 [B, k] over the score rows the last retrieve /
+        retrieve_scored / grouped dense_retrieve on this handle left (hrag_last_group_hits).  filter_words / filter_ld: what
+        doc_filter_words made of that call's doc filter (None: every passage)."""
+        torch = _torch()
+        gi = group_idx.to(self.device, torch.int32).contiguous()
+        b, k = gi.shape
+        hi = self._empty((b, k, hits), torch.int32)
+        hs = self._empty((b, k, hits), torch.float32)
+        check(self._lib.hrag_last_group_hits(self._handle, b, gi.data_ptr(), k, hits,
+                                             filter_words.data_ptr() if filter_words is not None else None, filter_ld,
+                                             hi.data_ptr(), hs.data_ptr(), _stream()))
+        return hi, hs
 
     def retrieve_scored(self, pass_scores, kept_idx, kept_score, kept_count, *, link_top_k: int = 5,
                         damping: float = 0.5, passage_node_weight: float = 0.05, ppr_iters: int = 20, k: int = 200,
                         ppr_tol: float = 0.0, ppr_max_iters: int = 0, doc_filter=None,
-                        filter_scope: str = "ranking", group_agg: Optional[str] = None) -> RetrieveOutput:
+                        filter_scope: str = "ranking", group_agg: Optional[str] = None,
+                        group_hits: Optional[int] = None) -> RetrieveOutput:
         """retrieve() with the raw passage scores fp32 [B, >= Np] supplied by the caller (hrag_retrieve_scored)."""
         torch = _torch()
         scoped = check_filter_scope(filter_scope, doc_filter)
         agg = check_group_agg(group_agg)
+        hits = check_group_hits(group_hits, group_agg)
         sc_in = pass_scores.to(self.device, torch.float32)
         if sc_in.stride(-1) != 1:
             sc_in = sc_in.contiguous()
@@ -658,7 +704,7 @@ class HippoRAGEngine:
                 used.data_ptr(), _stream())
         if agg is not None:
             return self._grouped(self._lib.hrag_retrieve_scored_grouped, args, 15, doc_filter, scoped, agg, b, k,
-                                 RetrieveOutput(idx, sc, flags, resid, used))
+                                 RetrieveOutput(idx, sc, flags, resid, used), hits)
         if doc_filter is None:
             check(self._lib.hrag_retrieve_scored(*args))
         else:
@@ -717,20 +763,23 @@ class HippoRAGEngine:
         return out
 
     def dense_retrieve(self, q_pass, k: int = 200, doc_filter=None, filter_scope: str = "ranking",
-                       group_agg: Optional[str] = None):
+                       group_agg: Optional[str] = None, group_hits: Optional[int] = None):
         """DPR top-k; filter_scope="seeds": normalised over the allowed passages (hrag_dense_retrieve_scoped).
         group_agg="max" | "sum": (group ids, group scores, best passage of each group) over the normalised scores
-        (hrag_dense_retrieve_grouped)."""
+        (hrag_dense_retrieve_grouped); group_hits=m adds two entries, (hit_idx, hit_score) [B, k, m] over those scores."""
         torch = _torch()
         scoped = check_filter_scope(filter_scope, doc_filter)
         agg = check_group_agg(group_agg)
+        hits = check_group_hits(group_hits, group_agg)
         q = self._q(q_pass)
         b = q.shape[0]
         idx = self._empty((b, k), torch.int32)
         sc = self._empty((b, k), torch.float32)
         if agg is not None:
             out = self._grouped(self._lib.hrag_dense_retrieve_grouped, (self._handle, q.data_ptr(), b, k, None, None, _stream()),
-                                4, doc_filter, scoped, agg, b, k, RetrieveOutput(idx, sc, None))
+                                4, doc_filter, scoped, agg, b, k, RetrieveOutput(idx, sc, None), hits)
+            if hits is not None:
+                return out.group_idx, out.doc_score, out.doc_idx, out.hit_idx, out.hit_score
             return out.group_idx, out.doc_score, out.doc_idx
         if doc_filter is None:
             check(self._lib.hrag_dense_retrieve(self._handle, q.data_ptr(), b, k, idx.data_ptr(),

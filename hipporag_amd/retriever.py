@@ -190,6 +190,8 @@ class RetrievalConfig:
                                          # retrieve() / retrieve_dpr() then rank the GROUPS of passages that share its value,
                                          # one best passage per group; None: passages, as the reference
     group_agg: str = "max"               # a group's score: "max" (its best passage's) or "sum" (of its passages' scores)
+    group_hits: Optional[int] = None     # with group_by: the best m passages of each ranked group (1 .. 64) in the entry's
+                                         # metadata ("group_hits"); None: the representative only
 
 
 def identity_rerank_filter(query, candidate_items, candidate_indices, len_after_rerank=None):
@@ -220,6 +222,8 @@ class BatchRows(list):
     doc_idx = None
     doc_score = None
     group_idx = None     # grouped retrieval: int32 [b, k] group ids (doc_idx: each group's best passage, doc_score: its score)
+    hit_idx = None       # group_hits=m: int32 [b, k, m] the best m allowed passages of each ranked group (-1 beyond them)
+    hit_score = None     # fp32 [b, k, m] their own scores
 
 
 def unpack_mask(words, n: int) -> np.ndarray:
@@ -244,10 +248,38 @@ def rank_allowed(full, allowed, want: int):
     return idx, sc
 
 
-def group_rank_rows(full, group_of, allowed, want: int, agg: str = "max"):
+def group_hits_rows(full, group_of, allowed, group_idx, hits: int):
+    """The host form of the group hits (include/hrag.h, group hits): per row of `full` fp32 [B, n] and per entry of
+    group_idx int [B, k] (-1 or an id outside the table: an empty row) the first `hits` allowed members of that group by
+    the ranking rule -> (hit_idx int32, hit_score fp32) [B, k, hits], -1 / 0 beyond the group's allowed members; scores as
+    every ranking returns them (the quiet NaN, -0 as +0).  allowed: None, bool [n] or [B, n]."""
+    full = np.asarray(full, np.float32)
+    b, n = full.shape
+    g = np.asarray(group_of, np.int64)
+    gi = np.asarray(group_idx, np.int64)
+    n_groups = int(g.max()) + 1 if g.size else 0
+    allowed = np.ones((b, n), bool) if allowed is None else np.broadcast_to(np.asarray(allowed, bool), full.shape)
+    hi = np.full(gi.shape + (hits,), -1, np.int32)
+    hs = np.zeros(gi.shape + (hits,), np.float32)
+    for i in range(b):
+        order = np.argsort(full[i], kind="stable")[::-1]            # the ranking rule: best first, ties -> larger index
+        order = order[allowed[i][order]]
+        by_group = np.argsort(g[order], kind="stable")              # stable: the ranking's order inside every group
+        members = order[by_group]
+        start = np.searchsorted(g[order][by_group], np.arange(n_groups + 1))
+        for j, gg in enumerate(gi[i]):
+            if 0 <= gg < n_groups:
+                top = members[start[gg]: min(start[gg + 1], start[gg] + hits)]
+                hi[i, j, :len(top)] = top
+                hs[i, j, :len(top)] = full[i][top]
+    hs[np.isnan(hs)] = np.float32(np.nan)
+    return hi, hs + np.float32(0)
+
+
+def group_rank_rows(full, group_of, allowed, want: int, agg: str = "max", hits: Optional[int] = None):
     """The host form of the grouped ranking (include/hrag.h, grouped retrieval): per row of `full` fp32 [B, n] the first
     `want` groups -> (group ids, group scores, representative passages), -1 / 0 / -1 beyond the groups that have an allowed
-    member.  allowed: None, bool [n] or [B, n]."""
+    member.  allowed: None, bool [n] or [B, n].  hits=m: two more entries, group_hits_rows of the ranked groups."""
     full = np.asarray(full, np.float32)
     b, n = full.shape
     g = np.asarray(group_of, np.int64)
@@ -272,6 +304,8 @@ def group_rank_rows(full, group_of, allowed, want: int, agg: str = "max"):
         rank = np.argsort(score, kind="stable")[::-1]
         rank = rank[has[rank]][:want]
         gi[i, :len(rank)], gs[i, :len(rank)], rep[i, :len(rank)] = rank, score[rank], best[rank]
+    if hits is not None:
+        return (gi, gs, rep) + group_hits_rows(full, group_of, allowed, gi, hits)
     return gi, gs, rep
 
 
@@ -308,7 +342,8 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
                           linking_top_k: int, damping: float, passage_node_weight: float, ppr_iters: int,
                           num_to_retrieve: int, n_passages: int, timers=None, ppr_tol: float = 0.0,
                           ppr_max_iters: int = 0, ppr_base_iters_narrow: Optional[int] = None, doc_filter=None,
-                          filter_scope: str = "ranking", group_agg: Optional[str] = None, group_of=None):
+                          filter_scope: str = "ranking", group_agg: Optional[str] = None, group_of=None,
+                          group_hits: Optional[int] = None):
     """The body of retrieve() (HippoRAG.py:459-480), shared by the mirror class below and by
     reference_adapter.attach(): phase A on the device, the recognition-memory filter on the host (rerank_facts
     :1659-1707), phase B on the device, in batches of eng.max_batch queries.  Yields (offset of the batch, [(doc ids,
@@ -332,11 +367,15 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
     filter_scope="seeds": phase A takes its facts from the allowed passages and phase B normalises the passage prior over
     them (include/hrag.h, scoped doc filter); needs doc_filter and an engine with fact sources.
     group_agg ("max" / "sum") with group_of (int array over the passages, already set on the engine): the rows rank
-    GROUPS -- doc ids are each group's best passage, doc scores the group scores, rows.group_idx the group ids."""
+    GROUPS -- doc ids are each group's best passage, doc scores the group scores, rows.group_idx the group ids.
+    group_hits=m (with group_agg): rows.hit_idx / rows.hit_score [b, k, m], the best m allowed passages of every ranked
+    group; the engine serves them right behind each batch's grouped call, the host form beyond max_topk."""
     import torch
     from .engine import host_copy_async, host_wait
     k_f = int(linking_top_k)
     want = max(1, min(int(num_to_retrieve), n_passages))
+    from .engine import check_group_hits
+    group_hits = check_group_hits(group_hits, group_agg)
     if group_agg is not None:
         if group_of is None:
             raise ValueError("group_agg needs group_of (the passage -> group table)")
@@ -419,12 +458,16 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
                 kw["filter_scope"] = "seeds"
         if group_agg is not None:
             kw["group_agg"] = group_agg
+        if group_hits is not None and not beyond:
+            kw["group_hits"] = group_hits
         if two_halves:
             bt.pending = eng.retrieve_converged_start(*args, **kw)
             o = bt.pending.out
             bt.copies = (host_copy_async(o.doc_idx), host_copy_async(o.doc_score))
             if group_agg is not None:
                 bt.copies += (host_copy_async(o.group_idx),)
+            if "group_hits" in kw:
+                bt.copies += (host_copy_async(o.hit_idx), host_copy_async(o.hit_score))
         else:                                       # an engine with the one-call form only (test doubles)
             bt.pending, bt.out = None, eng.retrieve_converged(*args, **kw)
         tick("ppr_time", t0)
@@ -443,16 +486,21 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
             out = bt.out
             d_idx, d_sc = out.doc_idx.cpu().numpy(), out.doc_score.cpu().numpy()
             flags = out.flags.cpu().numpy()
-        g_idx = None
+        g_idx = h_idx = h_sc = None
         if group_agg is not None and not beyond:
-            g_idx = (host_wait(bt.copies[2]).copy() if bt.pending is not None and not bt.pending.repeated
-                     else out.group_idx.cpu().numpy())
+            copied = bt.pending is not None and not bt.pending.repeated
+            g_idx = host_wait(bt.copies[2]).copy() if copied else out.group_idx.cpu().numpy()
+            if group_hits is not None:
+                h_idx, h_sc = ((host_wait(bt.copies[3]).copy(), host_wait(bt.copies[4]).copy()) if copied
+                               else (out.hit_idx.cpu().numpy(), out.hit_score.cpu().numpy()))
         if beyond and group_agg is not None:
             full = out.all_scores.cpu().numpy()
             rows_w = None if doc_filter is None else (doc_filter if doc_filter.ndim == 1
                                                       else doc_filter[bt.lo: bt.lo + len(bt.qs)])
-            g_idx, d_sc, d_idx = group_rank_rows(full, group_of, None if rows_w is None else
-                                                 unpack_mask(rows_w, full.shape[1]), want, group_agg)
+            g_idx, d_sc, d_idx, *h = group_rank_rows(full, group_of, None if rows_w is None else
+                                                     unpack_mask(rows_w, full.shape[1]), want, group_agg, group_hits)
+            if h:
+                h_idx, h_sc = h
         elif beyond:
             full = out.all_scores.cpu().numpy()
             if doc_filter is not None:
@@ -464,6 +512,7 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
         tick("ppr_time", t0)
         rows = BatchRows()
         rows.doc_idx, rows.doc_score, rows.group_idx = d_idx, d_sc, g_idx
+        rows.hit_idx, rows.hit_score = h_idx, h_sc
         for i in range(len(bt.qs)):
             if flags[i] & 4:      # :1541
                 raise AssertionError("count_nonzero(all_phrase_weights) != len(linking_score_map)")
@@ -1008,6 +1057,15 @@ class HippoRAG:
             raise ValueError("group_agg must be 'max' or 'sum'")
         return agg, self.group_table(group_by)
 
+    def _hits(self, group_hits, agg):
+        """The group hits of a call: the argument, else RetrievalConfig.group_hits; only a grouped call has them."""
+        from .engine import check_group_hits
+        if agg is None:
+            if group_hits is not None:
+                raise ValueError("group_hits needs group_by (it asks for the best passages of each ranked group)")
+            return None
+        return check_group_hits(self.global_config.group_hits if group_hits is None else group_hits, agg)
+
     def _engine_groups(self, table):
         """The engine ranks by `table` from here on (set once per table: it is part of the device index)."""
         eng = self.engine
@@ -1019,7 +1077,8 @@ class HippoRAG:
 
     def _group_solutions(self, queries, rows, table, num_to_retrieve):
         """QuerySolutions of a grouped batch: per entry the representative passage, the group score and the passage's
-        metadata plus {"group": value, "group_size": n}."""
+        metadata plus {"group": value, "group_size": n}; with group hits also "group_hits": [{"doc", "score", "position"}],
+        the group's best passages, best first (entry 0 is the representative)."""
         texts, keys = self._result_tables()
         _, values, sizes = table
         meta = self.chunk_metadata
@@ -1029,6 +1088,12 @@ class HippoRAG:
             keep = gi >= 0
             gi, ids = gi[keep], np.asarray(rows.doc_idx[i][:num_to_retrieve], np.int64)[keep]
             md = [{**meta.get(k, {}), "group": values[g], "group_size": int(sizes[g])} for k, g in zip(keys[ids], gi)]
+            if rows.hit_idx is not None:
+                h_idx = np.asarray(rows.hit_idx[i][:num_to_retrieve], np.int64)[keep]
+                h_sc = np.asarray(rows.hit_score[i][:num_to_retrieve])[keep]
+                for d, pos, sc in zip(md, h_idx, h_sc):
+                    d["group_hits"] = [{"doc": texts[p], "score": float(v), "position": int(p)}
+                                       for p, v in zip(pos, sc) if p >= 0]
             out.append(QuerySolution(question=q, docs=texts[ids].tolist(),
                                      doc_scores=np.asarray(rows.doc_score[i][:len(ids)]), doc_metadata=md,
                                      graph_seeds=(rows[i][2] if len(rows) > i else None) or []))
@@ -1054,10 +1119,12 @@ class HippoRAG:
     # ------------------------------------------------------------------ retrieve :413-499
     def retrieve(self, queries: List[str], num_to_retrieve: Optional[int] = None,
                  gold_docs: Optional[List[List[str]]] = None, doc_filter=None, filter_scope: Optional[str] = None,
-                 group_by=None, group_agg: Optional[str] = None):
+                 group_by=None, group_agg: Optional[str] = None, group_hits: Optional[int] = None):
         """group_by / group_agg (defaults RetrievalConfig.group_by / group_agg): rank GROUPS of passages -- source
         documents -- instead of passages (group_table): num_to_retrieve counts groups, every entry is a group's best
         passage with the group's score and {"group", "group_size"} in its metadata.
+        group_hits=m (default RetrievalConfig.group_hits; with group_by): every entry's metadata also carries "group_hits",
+        the group's best m allowed passages as [{"doc", "score", "position"}], best first; docs / doc_scores are unchanged.
         doc_filter: limit the ranked documents to a subset of the corpus (a post-filter: scores do not change) --
         a metadata dict {key: value} or {key: [values]} (values of a key: any of them; keys: all of them; matched
         against the chunk metadata, source_id included), a bool numpy array over passage_node_keys, or a list with one
@@ -1073,9 +1140,10 @@ class HippoRAG:
         scope = self._scope(filter_scope, doc_filter)
         words = self._doc_filter_words(doc_filter, len(queries))
         agg, table = self._grouping(group_by, group_agg)
+        hits = self._hits(group_hits, agg)
         self.get_query_embeddings(queries)
         results: List[QuerySolution] = []
-        self._retrieve_into(results, queries, num_to_retrieve, words, scope, agg, table)
+        self._retrieve_into(results, queries, num_to_retrieve, words, scope, agg, table, hits)
         self.all_retrieval_time += time.time() - t_start
         logger.info("Total Retrieval Time %.2fs", self.all_retrieval_time)
         logger.info("Total Recognition Memory Time %.2fs", self.rerank_time)
@@ -1085,12 +1153,14 @@ class HippoRAG:
         return results
 
     def _retrieve_into(self, results, queries, num_to_retrieve, doc_filter=None, filter_scope: str = "ranking",
-                       group_agg=None, table=None):
+                       group_agg=None, table=None, group_hits=None):
         cfg = self.global_config
         extra = {} if doc_filter is None else {"doc_filter": doc_filter, "filter_scope": filter_scope}
         if group_agg is not None:
             self._engine_groups(table)
             extra.update(group_agg=group_agg, group_of=table[0])
+            if group_hits is not None:
+                extra["group_hits"] = group_hits
         # batch by batch: the lists of document strings of one batch are built while the device works on the next
         for lo, rows in iter_batched_retrieve(self.engine, queries, self._q_tensor, self.facts if self.fact_node_keys else [],
                                               self.rerank_filter, linking_top_k=cfg.linking_top_k, damping=cfg.damping,
@@ -1205,9 +1275,9 @@ class HippoRAG:
     # ------------------------------------------------------------------ retrieve_dpr :665-732
     def retrieve_dpr(self, queries: List[str], num_to_retrieve: Optional[int] = None,
                      gold_docs: Optional[List[List[str]]] = None, doc_filter=None, filter_scope: Optional[str] = None,
-                     group_by=None, group_agg: Optional[str] = None):
+                     group_by=None, group_agg: Optional[str] = None, group_hits: Optional[int] = None):
         """Dense retrieval; doc_filter / filter_scope as in retrieve() ("seeds": the scores are normalised over the
-        allowed passages); group_by / group_agg as in retrieve(), over the normalised dense scores."""
+        allowed passages); group_by / group_agg / group_hits as in retrieve(), over the normalised dense scores."""
         cfg = self.global_config
         if num_to_retrieve is None:
             num_to_retrieve = cfg.retrieval_top_k
@@ -1215,6 +1285,7 @@ class HippoRAG:
         scope = self._scope(filter_scope, doc_filter)
         words = self._doc_filter_words(doc_filter, len(queries))
         agg, table = self._grouping(group_by, group_agg)
+        hits = self._hits(group_hits, agg)
         import torch
         self.get_query_embeddings(queries)
         eng = self.engine
@@ -1240,8 +1311,10 @@ class HippoRAG:
                 "doc_filter": torch.from_numpy(np.ascontiguousarray(rows_of(lo, len(qs))).view(np.int32)),
                 "filter_scope": scope}
             if agg is not None:
-                gi, sc, idx = eng.dense_retrieve(self._q_tensor(qs, "passage"), k=k_docs, group_agg=agg, **extra)
-                return qs, host_copy_async(idx), host_copy_async(sc), host_copy_async(gi)
+                if hits is not None:
+                    extra["group_hits"] = hits
+                gi, sc, idx, *h = eng.dense_retrieve(self._q_tensor(qs, "passage"), k=k_docs, group_agg=agg, **extra)
+                return (qs, host_copy_async(idx), host_copy_async(sc), host_copy_async(gi)) + tuple(map(host_copy_async, h))
             idx, sc = eng.dense_retrieve(self._q_tensor(qs, "passage"), k=k_docs, **extra)
             return qs, host_copy_async(idx), host_copy_async(sc)
 
@@ -1251,7 +1324,7 @@ class HippoRAG:
         for n in range(len(starts)):
             qs, idx_h, sc_h, *gi_h = pending
             pending = enqueue(starts[n + 1]) if n + 1 < len(starts) else None
-            gi = None
+            gi = h_idx = h_sc = None
             if beyond:
                 raw = host_wait(idx_h)[:, :len(self.passage_node_keys)]
                 if scope == "seeds":
@@ -1259,8 +1332,11 @@ class HippoRAG:
                 else:
                     full = np.stack([min_max_normalize(r) for r in raw]).astype(np.float32)
                 if agg is not None:
-                    gi, sc, idx = group_rank_rows(full, table[0], None if words is None else
-                                                  unpack_mask(rows_of(starts[n], len(qs)), full.shape[1]), want, agg)
+                    gi, sc, idx, *h = group_rank_rows(full, table[0], None if words is None else
+                                                      unpack_mask(rows_of(starts[n], len(qs)), full.shape[1]), want, agg,
+                                                      hits)
+                    if h:
+                        h_idx, h_sc = h
                 elif words is not None:
                     idx, sc = rank_allowed(full, unpack_mask(rows_of(starts[n], len(qs)), full.shape[1]), want)
                 else:
@@ -1269,9 +1345,12 @@ class HippoRAG:
             else:
                 idx, sc = host_wait(idx_h).copy(), host_wait(sc_h).copy()
                 gi = host_wait(gi_h[0]).copy() if gi_h else None
+                if len(gi_h) == 3:
+                    h_idx, h_sc = host_wait(gi_h[1]).copy(), host_wait(gi_h[2]).copy()
             if agg is not None:
                 rows = BatchRows([(idx[i], sc[i], None) for i in range(len(qs))])
                 rows.doc_idx, rows.doc_score, rows.group_idx = idx, sc, gi
+                rows.hit_idx, rows.hit_score = h_idx, h_sc
                 results.extend(self._group_solutions(qs, rows, table, num_to_retrieve))
                 continue
             with gc_paused():

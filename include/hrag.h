@@ -628,6 +628,46 @@ hrag_status hrag_group_rows(const float *scores_dev, int32_t batch, int64_t n, i
                             int64_t filter_ld_words, int64_t filter_bit_offset, float *gscore_out_dev,
                             int32_t *gbest_out_dev, int64_t out_ld, hrag_stream stream);
 
+/* ---- grouped retrieval, group hits: the m best passages of each ranked source ----
+ * A grouped call returns ONE passage per ranked group, the representative; a reader is fed the best few chunks of each of
+ * the best sources.  For one query take its final passage scores s[p] (what hrag_last_doc_scores returns; after
+ * hrag_dense_retrieve_grouped the min-max normalised scores that call ranked), the optional doc filter, and a ranked group
+ * slot j holding group id g.  Then hits[j][0 .. m) are the first min(m, allowed members of g) entries of the ranking rule
+ * at the top of this header restricted to the allowed members of g: score descending, ties -> larger passage position,
+ * every NaN above +inf, -0 ties +0.  The slots beyond hold -1 / 0; a padded group slot (g == -1) gives an all -1 / 0 row.
+ * Scores come back as every ranking returns them: the canonical quiet NaN, -0 as +0.  Consequences:
+ *   1. hits[j][0] == best_doc_idx[j] for both aggregators.  HRAG_GROUP_MAX: its score equals the group score bit for
+ *      bit; HRAG_GROUP_SUM: the hits carry each member's own score, not the sum.
+ *   2. The hits of group g are the ungrouped filtered ranking (hrag_retrieve_filtered, "ranking" scope) of the same
+ *      query under the filter (allowed AND member of g), ids and scores bit-identical -- without a second PPR.
+ *   3. m == 1 returns what the grouped call already did.
+ * 1 <= m <= HRAG_GROUP_HITS_MAX (one wavefront holds the list); anything else is HRAG_EINVAL before anything is enqueued.
+ * Cost: one wavefront per (query, ranked slot) reads that group's members and their scores once (csrc/group.hip); no
+ * atomics, no allocation, no synchronisation, no read-back -- capture-safe like the calls it follows. */
+#define HRAG_GROUP_HITS_MAX 64
+
+/* The selection alone, engine-free, beside hrag_group_rows with the same argument rules and checks: scores_dev, the group
+ * CSR and the filter as there; group_idx_dev int32 [batch, k], each entry a group id or -1 (an id outside [0, n_groups)
+ * counts as -1; ids may repeat).  Writes hit_idx_out_dev int32 and hit_score_out_dev fp32, both [batch, k, hits]. */
+hrag_status hrag_group_hits_rows(const float *scores_dev, int32_t batch, int64_t n, int64_t ld,
+                                 const int64_t *group_ptr_dev, const int32_t *members_dev, int64_t n_groups,
+                                 const int32_t *group_idx_dev, int32_t k, int32_t hits, const uint32_t *filter_dev,
+                                 int64_t filter_ld_words, int64_t filter_bit_offset, int32_t *hit_idx_out_dev,
+                                 float *hit_score_out_dev, hrag_stream stream);
+
+/* The hits of ranked groups over the score rows the handle's LAST retrieve, scored or grouped dense call left -- the rows
+ * hrag_last_doc_scores reads; after hrag_dense_retrieve_grouped the normalised rows -- with the engine's group table.  A
+ * follow-up call: issue it right after the grouped call (same handle, the usual stream and one-call-per-handle rules;
+ * a workspace handle has its own rows), with the group ids that call returned and the filter it was given (NULL: every
+ * passage).  The ids need not come from a grouped call: any [batch, k] ids in [-1, n_groups) are legal, k >= 1 is not
+ * bound by max_topk.  The handle records the batch of the call that last wrote its rows; an ungrouped hrag_dense_retrieve*
+ * call does not write them (it ranks the raw similarity rows), so the record then still names the call before it.
+ * HRAG_EINVAL: no group table, a row-shard engine, no rows written yet on this handle, batch above the recorded one,
+ * hits outside [1, HRAG_GROUP_HITS_MAX], k < 1; the outputs are then untouched. */
+hrag_status hrag_last_group_hits(hrag_engine *e, int32_t batch, const int32_t *group_idx_dev, int32_t k, int32_t hits,
+                                 const uint32_t *filter_dev, int64_t filter_ld_words, int32_t *hit_idx_out_dev,
+                                 float *hit_score_out_dev, hrag_stream stream);
+
 /* ---- lower-level seams (used by the per-method adapters and by the parity tests) ---- */
 
 /* np.dot(embeddings, q.T) (HippoRAG.py:1459 / :1496): raw cosine scores.
