@@ -783,10 +783,14 @@ hrag_status hrag_ppr_sweeps(hrag_engine *e, int32_t batch, int32_t n, float damp
                             hrag_stream stream);
 
 /* ------------------------------------------------------------------------------------------
- * Stage-level operators.  hrag_retrieve() is exactly the composition of these on engine-owned
- * buffers; they are exported so that a host can interleave its own exchange steps (the
- * multi-GPU row-shard mode of hipporag_amd/dist.py all-gathers x between hrag_stage_ppr_step
- * calls) -- every buffer is caller-owned device memory.
+ * Stage-level operators.  hrag_retrieve() on the fp32 state (HRAG_OPT_F32_STATE, or any sweep count /
+ * damping the narrower states do not take) is exactly the composition of these on engine-owned
+ * buffers -- bit for bit: tests/test_gpu_stage_ops.py composes them by hand and on row windows that
+ * share one state, tests/test_gpu_csr_sweep.py holds each of them to fp64 at every slab width.  They are
+ * the seams for per-method adapters and those tests: fp32 state, every buffer caller-owned device memory,
+ * a host may interleave its own steps between any two of them.  (The multi-GPU row-shard mode of
+ * hipporag_amd/dist.py exchanged x between hrag_stage_ppr_step calls once; it runs on the hrag_shard_*
+ * calls below, on the staged e4m3 state, and shares only hrag_stage_seeds with this list.)
  *
  * PPR state layout ("slab layout"): x is [n_slabs][V][bc] fp32; query q lives in slab q / bc,
  * column q % bc; hrag_ppr_layout() returns (bc, n_slabs) for a batch on this engine.
