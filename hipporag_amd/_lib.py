@@ -19,7 +19,7 @@ PPR_ERR_K, PPR_ERR_FLOOR_FP8, PPR_ERR_FLOOR_F16, PPR_ERR_FLOOR_F32, PPR_TOL_MIN 
 # hrag_opts.flags (include/hrag.h HRAG_OPT_*)
 OPT_NATURAL_ROW_ORDER, OPT_NT_CSR, OPT_NT_STORE, OPT_F32_STATE, OPT_TEMPORAL16, OPT_NO_FP8 = 1, 2, 4, 8, 16, 32
 OPT_ROWS_BY_MINCOL, OPT_ROWS_BFS, OPT_SLABS_PER_WG_1, OPT_NO_F16, OPT_XCD_BLOCKED = 64, 128, 256, 1024, 2048
-OPT_ACCEL = 4096
+OPT_ACCEL, OPT_STORE_R1 = 4096, 8192
 
 
 class HragError(RuntimeError):
@@ -68,7 +68,7 @@ class Stats(C.Structure):
     """hrag_stats of include/hrag.h."""
     _fields_ = [("is_workspace", C.c_int32), ("live_workspaces", C.c_int32), ("index_bytes", C.c_int64),
                 ("workspace_bytes", C.c_int64), ("ppr_states", C.c_int32), ("fp8_unavailable", C.c_int32),
-                ("last_ppr_state", C.c_int32), ("reserved", C.c_int32), ("calls_score_facts", C.c_int64),
+                ("last_ppr_state", C.c_int32), ("ppr8_r1_long_rows", C.c_int32), ("calls_score_facts", C.c_int64),
                 ("calls_retrieve", C.c_int64), ("calls_dense_retrieve", C.c_int64), ("calls_ppr", C.c_int64),
                 ("calls_shard", C.c_int64), ("queries", C.c_int64)]
 

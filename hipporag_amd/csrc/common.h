@@ -202,7 +202,10 @@ hrag_status launch_ppr16_seed_rows(const int32_t *seed_vtx, const float *seed_w,
 
 // ppr8.hip : staged fp8 (e4m3) state + fp32 true residual, 128 queries per 128-byte line, SELL-8 over the
 // OWNED rows (row shard; single GPU: all rows) with the row-normalised values At = D^-1 A
-enum Ppr8Mode { kP8ModeC = 0, kP8ModeB = 1, kP8ModeF = 2, kP8ModeB0 = 3 };   // B0: first boundary, R_in = b v/d
+// B0: first boundary, R_in = b v/d.  B0N / B1 (the default plan, csrc/shard.hip ppr8_begin): the fp32 R_1 that B0 would
+// store and the next boundary would read once is not stored -- B0N writes everything B0 writes but R, and B1, the boundary
+// that consumes R_1, forms it again in registers from c_0 (x0) exactly as B0 does.  Long rows keep the stored R_1.
+enum Ppr8Mode { kP8ModeC = 0, kP8ModeB = 1, kP8ModeF = 2, kP8ModeB0 = 3, kP8ModeB0N = 4, kP8ModeB1 = 5 };
 constexpr int kP8MaxStages = 12;      // stage lengths 1,2,3,..,3,(1|2) => <= 11 stages for ppr_iters <= 30
 constexpr float kP8C0Scale = 128.f;   // c_0 = Q(v/d * 2^7),  max(v/d) in (1/2, 1]
 constexpr int32_t kFlagFp8Saturated = 8;   // flags bit 3 (HRAG_FLAG_FP8_SATURATED)
@@ -238,6 +241,8 @@ struct Ppr8Args {
     uint32_t row_stride;       // spg * 128: bytes between consecutive vertices of a group
     int64_t group_bytes;       // (V + 1) * row_stride
     const uint8_t *x;          // gather source
+    const uint8_t *x0 = nullptr;   // mode B1: c_0's buffer (the gather source of the first sweep) and 1 / cs_0
+    float inv_cs0 = 0.f;
     uint8_t *y;                // mode C: the new iterate; mode B: rt of the next stage (owned rows written)
     const uint8_t *rt;         // mode C / rio bit 0: the quantised right-hand side of the stage (being closed)
     float *R;                  // true residual, fp32 [n_slabs][n_rows][128] lane-interleaved (LOCAL rows)

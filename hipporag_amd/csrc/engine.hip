@@ -1093,6 +1093,7 @@ hrag_status hrag_engine_stats(hrag_engine *e, hrag_stats *out) {
                    (e->f8_ready ? HRAG_PPR_STATE_FP8 : 0);
     s.fp8_unavailable = e->fp8_unavailable;
     s.last_ppr_state = e->last_ppr_state;
+    s.ppr8_r1_long_rows = e->p8.r1_long_rows;
     s.calls_score_facts = e->counters.score_facts.load();
     s.calls_retrieve = e->counters.retrieve.load();
     s.calls_dense_retrieve = e->counters.dense.load();

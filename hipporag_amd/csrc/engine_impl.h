@@ -112,6 +112,7 @@ struct Ppr8Session {
     // group arrives, so the groups of a step must come in ascending order and a step must be complete before the next
     // begins -- ppr8_sweep enforces it (a stale scale would otherwise only show as a saturation flag)
     int32_t last_step = -1, last_group = -1;
+    int32_t r1_long_rows = 0;            // hrag_stats.ppr8_r1_long_rows: -1 stored R_1, n >= 0 recomputed (n long rows stored)
 };
 
 }  // namespace hrag

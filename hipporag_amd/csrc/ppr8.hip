@@ -168,14 +168,26 @@ struct Gather8M {
         if constexpr (K + 1 < 8) Gather8M<K + 1>::load(xv, wk, c, wbits, on, xs, stride, lane_off);
     }
 };
+// The products of slot K are skipped when none of the wavefront's 8 columns of that slot is in the bitmap (wave-uniform;
+// ~60 % of the slots at 6 % density): every gathered value is then zero, and for a FINITE weight acc + 0 * w = acc (acc is
+// never -0: it starts at +0).  A NaN / Inf weight on such a slot (engine creation rejects Inf through its row-sum check, a
+// NaN passes it) is no longer multiplied in by the FIRST sweep; the next sweep gathers every slot unmasked and turns the
+// row into NaN as before, one sweep later: a matrix with non-finite entries has NaN scores either way.
+// The conversions and FMAs over zeros, not the bytes, were what the masked loop spent its time on.
+template <int K>
+struct Fma8M {
+    __device__ __forceinline__ static void run(f32x2_t (&acc)[8], const float (&wk)[8], const v4i_t (&xv)[8], int on) {
+        if (__builtin_amdgcn_ballot_w64(bcast8<K>(on) != 0) != 0) fma16(acc, wk[K], xv[K]);
+        if constexpr (K + 1 < 8) Fma8M<K + 1>::run(acc, wk, xv, on);
+    }
+};
 __device__ __forceinline__ void gather_step_masked(f32x2_t (&acc)[8], int c, int wbits, int on, const char *xs,
                                                    unsigned stride, unsigned lane_off) {
     v4i_t xv[8];
     float wk[8];
     Gather8M<0>::load(xv, wk, c, wbits, on, xs, stride, lane_off);
     __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) fma16(acc, wk[k], xv[k]);
+    Fma8M<0>::run(acc, wk, xv, on);
 }
 
 // (col, val) pairs through a buffer descriptor (hipcc keeps raw buffer loads where they are written:
@@ -299,11 +311,18 @@ __device__ __forceinline__ size_t state_off(const Ppr8Args &a, int slab, int64_t
 // the values by ~2.5x per stage below where the e4m3 range resolves them (cfg 3: 1.8e-6 instead of 4.4e-7, and the
 // contract then needs 26 sweeps).  Every boundary reports max |R cs'| of the batch (mq, per wavefront -> a.mmax_ws);
 // ppr8_next_scale_kernel turns it into the scale of the stage after next.  Wave-uniform scalar loads.
+// (uniform(): the fallback as a VALUE.  Left as a plain load of the argument struct, hipcc merges the two loads into one
+// load through a selected ADDRESS, which pins that word of the kernel arguments to a scratch slot.)
+__device__ __forceinline__ float uniform(float v) {
+    return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
+}
 __device__ __forceinline__ float scale_inv(const Ppr8Args &a, int stage, float fallback) {
-    return a.dyn ? a.dyn[kP8DynInv + stage] : fallback;
+    const float fb = uniform(fallback);
+    return a.dyn ? a.dyn[kP8DynInv + stage] : fb;
 }
 __device__ __forceinline__ float scale_cs(const Ppr8Args &a, int stage, float fallback) {
-    return a.dyn ? a.dyn[stage] : fallback;
+    const float fb = uniform(fallback);
+    return a.dyn ? a.dyn[stage] : fb;
 }
 
 // Finish one output row (lrow: LOCAL row): lane gl of its group owns queries 16*gl .. 16*gl+15 of the slab.
@@ -318,9 +337,14 @@ __device__ __forceinline__ float scale_cs(const Ppr8Args &a, int stage, float fa
 // er (mode F with a.est): on return |R_p| / z_p of this lane's 16 queries when the row is an owned passage (the
 // relative size of the update the final sweep applies to the passage score), untouched otherwise.
 // mq (modes B / B0): raised to max |R_new cs'| of this lane's 16 queries (what the dynamic stage scales are measured on).
-template <int MODE, int RIO, bool EST>
+// LONG: the row is a long one that the last-arriving wavefront finishes from the partial sums.  Modes B0N / B1 keep the
+// stored fp32 R_1 for those rows (a few MB); every other row of B0N stores no R, and B1 takes R_in = R_1 from rpre, where
+// the wavefront formed it again (first_residual).  rpre is not read in any other mode.
+template <int MODE, int RIO, bool EST, bool LONG = false>
 __device__ __forceinline__ void finish_row(const Ppr8Args &a, int slab, int lrow, int gl,
-                                           const f32x2_t (&acc)[8], f32x2_t (&er)[8], float &mq) {
+                                           const f32x2_t (&acc)[8], f32x2_t (&er)[8], float &mq,
+                                           const f32x2_t (&rpre)[8]) {
+    constexpr bool kFirst = MODE == kP8ModeB0 || MODE == kP8ModeB0N;
     const int64_t grow = a.row_offset + lrow;
     const float inv_cs = scale_inv(a, a.dyn_stage, a.inv_cs), cs_next = scale_cs(a, a.dyn_stage + 1, a.cs_next);
     const size_t off = state_off(a, slab, grow, gl);
@@ -339,14 +363,17 @@ __device__ __forceinline__ void finish_row(const Ppr8Args &a, int slab, int lrow
         const bool is_passage = slot >= 0 && slot < a.p_rows;
         v4i_t cv = {0, 0, 0, 0};
         // B0: c_0 = Q(v/d) exists only on the rows with a teleport row (ppr8_init_kernel writes no others)
-        if (MODE != kP8ModeB0 || slot >= 0) cv = __builtin_nontemporal_load(reinterpret_cast<const v4i_t *>(a.x + off));
+        if (!kFirst || slot >= 0) cv = __builtin_nontemporal_load(reinterpret_cast<const v4i_t *>(a.x + off));
         decode16(cv, c);
         float *rrow = a.R + ((size_t)slab * a.n_rows + (size_t)lrow) * 128;
         uint16_t *hrow = a.rho + ((size_t)slab * a.n_rows + (size_t)lrow) * 128;
-        if constexpr (MODE == kP8ModeB0) {
+        if constexpr (kFirst) {
             load_zv(a.tele, a.tele_rows, a.row_slot, a.deg, a.n_slabs64, slab, lrow, grow, gl, rin);   // R_in = b v/d
 #pragma unroll
             for (int j = 0; j < 8; ++j) rin[j] *= a.beta;
+        } else if constexpr (MODE == kP8ModeB1 && !LONG) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) rin[j] = rpre[j];
         } else if constexpr ((RIO & 1) != 0) {
             f32x2_t r8[8];
             decode16(__builtin_nontemporal_load(reinterpret_cast<const v4i_t *>(a.rt + off)), r8);
@@ -362,7 +389,7 @@ __device__ __forceinline__ void finish_row(const Ppr8Args &a, int slab, int lrow
             const f32x2_t t = __builtin_elementwise_fma(acc[j], al, -c[j]);   // a (At c) - c, one rounding
             out[j] = __builtin_elementwise_fma(t, inv, rin[j]);              // inv is a power of two: exact
         }
-        if constexpr (MODE == kP8ModeB || MODE == kP8ModeB0) {
+        if constexpr (MODE != kP8ModeF) {
             f32x2_t q[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) q[j] = out[j] * cs_next;
@@ -381,7 +408,7 @@ __device__ __forceinline__ void finish_row(const Ppr8Args &a, int slab, int lrow
 #pragma unroll
                 for (int j = 0; j < 8; ++j) back[j] = q[j] - back[j];          // exact: |q - Q(q)| <= 2^-4 |q|
                 st16h(hrow, gl, back);
-            } else {
+            } else if constexpr (MODE != kP8ModeB0N || LONG) {
                 st16i(rrow, gl, out);
             }
             // the final combine needs every stage's c at the passage rows only: keep a compact copy
@@ -474,6 +501,47 @@ __device__ __forceinline__ int ld_mask(__amdgpu_buffer_rsrc_t rsrc, unsigned vof
     return __builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, 0, 0);
 }
 
+// Mode B1: R_1 of one row from the first sweep's gathered sum acc = At c_0, formed exactly as finish_row forms `out` in
+// mode B0 (the same loads, the same fp32 operations in the same order): R_1 = b v/d + (a At c_0 - c_0) / cs_0.
+__device__ __forceinline__ void first_residual(const Ppr8Args &a, int slab, int lrow, int gl, const f32x2_t (&acc)[8],
+                                               f32x2_t (&rin)[8]) {
+    const int64_t grow = a.row_offset + lrow;
+    const float inv_cs = scale_inv(a, 0, a.inv_cs0);
+    f32x2_t c[8];
+    v4i_t cv = {0, 0, 0, 0};
+    if (a.row_slot[lrow] >= 0)
+        cv = __builtin_nontemporal_load(reinterpret_cast<const v4i_t *>(a.x0 + state_off(a, slab, grow, gl)));
+    decode16(cv, c);
+    load_zv(a.tele, a.tele_rows, a.row_slot, a.deg, a.n_slabs64, slab, lrow, grow, gl, rin);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) rin[j] *= a.beta;
+    const f32x2_t al = {a.alpha, a.alpha}, inv = {inv_cs, inv_cs};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const f32x2_t t = __builtin_elementwise_fma(acc[j], al, -c[j]);
+        rin[j] = __builtin_elementwise_fma(t, inv, rin[j]);
+    }
+}
+
+// The first sweep's gather loop (modes B0 / B0N, and B1 before its own): c_0 is zero outside the passage / seed vertices:
+// test the column bitmap (one step ahead) and issue only the gathers of those columns
+__device__ __forceinline__ void masked_loop(const Ppr8Args &a, f32x2_t (&acc)[8], __amdgpu_buffer_rsrc_t prs, unsigned poff,
+                                            unsigned pbase, int n_steps, const char *xs, unsigned stride, unsigned lane_off) {
+    int2 p0 = ld_pair(prs, poff, pbase);
+    int2 p1 = ld_pair(prs, poff + 512u, pbase);
+    const __amdgpu_buffer_rsrc_t mrs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<uint32_t *>(a.colmask), 0, (int)a.colmask_bytes, 0x00020000);
+    int m0 = ld_mask(mrs, ((unsigned)p0.x >> 5) * 4u);
+    for (int s = 0; s < n_steps; ++s) {
+        const int2 p2 = ld_pair(prs, poff + (unsigned)(s + 2) * 512u, pbase);
+        const int m1 = ld_mask(mrs, ((unsigned)p1.x >> 5) * 4u);
+        gather_step_masked(acc, p0.x, p0.y, (m0 >> (p0.x & 31)) & 1, xs, stride, lane_off);
+        p0 = p1;
+        p1 = p2;
+        m0 = m1;
+    }
+}
+
 // 1-D grid, XCD-aware: workgroups are dealt to the 8 XCDs round-robin, so ids 8 apart run back to back
 // on the same XCD.  They are given the SAME chunk group for consecutive slabs: the second reader of
 // a (col, val) block then finds it in that XCD's L2 (measured: C sweep 0.822 -> 0.802 ms at cfg 3;
@@ -500,27 +568,24 @@ __global__ __launch_bounds__(256, 4) void ppr8_kernel(const Ppr8Args a) {
     const unsigned pbase = (unsigned)meta.x * 512u;   // scalar: first byte of this chunk's pairs
     const unsigned poff = (unsigned)lane * 8u;
     const unsigned lane_off = (unsigned)gl * 16u;
-    f32x2_t acc[8];
+    f32x2_t acc[8], rpre[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] = f32x2_t{0.f, 0.f};
-    // pair stream read two steps ahead, unconditionally (the array carries the padding)
-    int2 p0 = ld_pair(prs, poff, pbase);
-    int2 p1 = ld_pair(prs, poff + 512u, pbase);
-    if constexpr (MODE == kP8ModeB0) {
-        // c_0 is zero outside the passage / seed vertices: test the column bitmap (one step ahead) and issue
-        // only the gathers of those columns
-        const __amdgpu_buffer_rsrc_t mrs = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<uint32_t *>(a.colmask), 0, (int)a.colmask_bytes, 0x00020000);
-        int m0 = ld_mask(mrs, ((unsigned)p0.x >> 5) * 4u);
-        for (int s = 0; s < n_steps; ++s) {
-            const int2 p2 = ld_pair(prs, poff + (unsigned)(s + 2) * 512u, pbase);
-            const int m1 = ld_mask(mrs, ((unsigned)p1.x >> 5) * 4u);
-            gather_step_masked(acc, p0.x, p0.y, (m0 >> (p0.x & 31)) & 1, xs, stride, lane_off);
-            p0 = p1;
-            p1 = p2;
-            m0 = m1;
-        }
+    for (int j = 0; j < 8; ++j) acc[j] = rpre[j] = f32x2_t{0.f, 0.f};
+    if constexpr (MODE == kP8ModeB1) {
+        // the first sweep once more over this chunk, from c_0's buffer: R_1 of the wavefront's rows, in registers
+        const char *xs0 = reinterpret_cast<const char *>(a.x0) + (size_t)g * (size_t)a.group_bytes + (size_t)k * 128;
+        masked_loop(a, acc, prs, poff, pbase, n_steps, xs0, stride, lane_off);
+        const int row = a.m.vrow[chunk * 8 + grp];
+        if (row >= 0) first_residual(a, slab, row, gl, acc, rpre);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] = f32x2_t{0.f, 0.f};
+    }
+    if constexpr (MODE == kP8ModeB0 || MODE == kP8ModeB0N) {
+        masked_loop(a, acc, prs, poff, pbase, n_steps, xs, stride, lane_off);
     } else {
+        // pair stream read two steps ahead, unconditionally (the array carries the padding)
+        int2 p0 = ld_pair(prs, poff, pbase);
+        int2 p1 = ld_pair(prs, poff + 512u, pbase);
         for (int s = 0; s < n_steps; ++s) {
             const int2 p2 = ld_pair(prs, poff + (unsigned)(s + 2) * 512u, pbase);
             gather_step(acc, p0.x, p0.y, xs, stride, lane_off);
@@ -539,12 +604,12 @@ __global__ __launch_bounds__(256, 4) void ppr8_kernel(const Ppr8Args a) {
     for (int j = 0; j < 8; ++j) er[j] = f32x2_t{0.f, 0.f};
     float mq = 0.f;
     if (tgt >= 0) {
-        finish_row<MODE, RIO, EST>(a, slab, tgt, gl, acc, er, mq);
+        finish_row<MODE, RIO, EST>(a, slab, tgt, gl, acc, er, mq, rpre);
     } else if (seg) {
         st16i_sc1(qrs, (unsigned)(-(tgt + 1)) * 512u, gl, acc);
     }
     if constexpr (kEst) est_commit<true>(a, slab, chunk, gl, grp, er);   // every lane takes part in the reduction
-    if constexpr (MODE == kP8ModeB || MODE == kP8ModeB0) mmax_commit<true>(a, chunk * a.mmax_units + (slab - a.mmax_slab0), mq);
+    if constexpr (MODE != kP8ModeC && MODE != kP8ModeF) mmax_commit<true>(a, chunk * a.mmax_units + (slab - a.mmax_slab0), mq);
     // Long rows arrive as segments in different wavefronts; the segment that arrives LAST (agent-scope
     // counter) lends its whole wavefront to the row: the 8 lane groups stride over the row's partial sums, the 8
     // group totals are added with xor-shuffles -- a fixed summation order, whoever comes last -- and the row is
@@ -584,9 +649,9 @@ __global__ __launch_bounds__(256, 4) void ppr8_kernel(const Ppr8Args a) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) er[j] = f32x2_t{0.f, 0.f};
             float m2 = 0.f;
-            finish_row<MODE, RIO, EST>(a, slab, a.m.lrow_row[mm], gl, acc, er, m2);
+            finish_row<MODE, RIO, EST, true>(a, slab, a.m.lrow_row[mm], gl, acc, er, m2, acc);
             if constexpr (kEst) est_commit<false>(a, slab, chunk, gl, 0, er);
-            if constexpr (MODE == kP8ModeB || MODE == kP8ModeB0) mmax_commit<false>(a, 0, m2);
+            if constexpr (MODE != kP8ModeC && MODE != kP8ModeF) mmax_commit<false>(a, 0, m2);
         }
         if (lane == 0) __hip_atomic_store(cnts + mm, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -629,6 +694,42 @@ struct Gather8PM {   // mode B0: masked (see Gather8M)
     }
 };
 
+template <int K>
+struct Fma8PM {   // see Fma8M
+    __device__ __forceinline__ static void run(f32x2_t (&acc0)[8], f32x2_t (&acc1)[8], const float (&wk)[8],
+                                               const v4i_t (&x0)[8], const v4i_t (&x1)[8], int on) {
+        if (__builtin_amdgcn_ballot_w64(bcast8<K>(on) != 0) != 0) {
+            fma16(acc0, wk[K], x0[K]);
+            fma16(acc1, wk[K], x1[K]);
+        }
+        if constexpr (K + 1 < 8) Fma8PM<K + 1>::run(acc0, acc1, wk, x0, x1, on);
+    }
+};
+
+// masked_loop for a slab pair
+__device__ __forceinline__ void masked_loop_pair(const Ppr8Args &a, f32x2_t (&acc0)[8], f32x2_t (&acc1)[8],
+                                                 __amdgpu_buffer_rsrc_t prs, unsigned poff, unsigned pbase, int n_steps,
+                                                 const char *xs, unsigned stride, unsigned lane_off) {
+    int2 p0 = ld_pair(prs, poff, pbase);
+    int2 p1 = ld_pair(prs, poff + 512u, pbase);
+    const __amdgpu_buffer_rsrc_t mrs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<uint32_t *>(a.colmask), 0, (int)a.colmask_bytes, 0x00020000);
+    int m0 = ld_mask(mrs, ((unsigned)p0.x >> 5) * 4u);
+    for (int s = 0; s < n_steps; ++s) {
+        const int2 p2 = ld_pair(prs, poff + (unsigned)(s + 2) * 512u, pbase);
+        const int m1 = ld_mask(mrs, ((unsigned)p1.x >> 5) * 4u);
+        v4i_t x0[8], x1[8];
+        float wk[8];
+        const int on = (m0 >> (p0.x & 31)) & 1;
+        Gather8PM<0>::load(x0, x1, wk, p0.x, p0.y, on, xs, stride, lane_off);
+        __builtin_amdgcn_sched_barrier(0);
+        Fma8PM<0>::run(acc0, acc1, wk, x0, x1, on);
+        p0 = p1;
+        p1 = p2;
+        m0 = m1;
+    }
+}
+
 template <int MODE, int RIO, bool EST>
 __device__ __forceinline__ void ppr8_pair_body(const Ppr8Args &a) {
     if (a.gate && *a.gate != a.gate_want) return;   // a conditional step the device decided not to run
@@ -650,32 +751,27 @@ __device__ __forceinline__ void ppr8_pair_body(const Ppr8Args &a) {
     const unsigned pbase = (unsigned)meta.x * 512u;
     const unsigned poff = (unsigned)lane * 8u;
     const unsigned lane_off = (unsigned)gl * 16u;
-    f32x2_t acc0[8], acc1[8];
+    f32x2_t acc0[8], acc1[8], rpre0[8], rpre1[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) acc0[j] = acc1[j] = f32x2_t{0.f, 0.f};
-    int2 p0 = ld_pair(prs, poff, pbase);
-    int2 p1 = ld_pair(prs, poff + 512u, pbase);
-    if constexpr (MODE == kP8ModeB0) {
-        const __amdgpu_buffer_rsrc_t mrs = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<uint32_t *>(a.colmask), 0, (int)a.colmask_bytes, 0x00020000);
-        int m0 = ld_mask(mrs, ((unsigned)p0.x >> 5) * 4u);
-        for (int s = 0; s < n_steps; ++s) {
-            const int2 p2 = ld_pair(prs, poff + (unsigned)(s + 2) * 512u, pbase);
-            const int m1 = ld_mask(mrs, ((unsigned)p1.x >> 5) * 4u);
-            v4i_t x0[8], x1[8];
-            float wk[8];
-            Gather8PM<0>::load(x0, x1, wk, p0.x, p0.y, (m0 >> (p0.x & 31)) & 1, xs, stride, lane_off);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int kk = 0; kk < 8; ++kk) {
-                fma16(acc0, wk[kk], x0[kk]);
-                fma16(acc1, wk[kk], x1[kk]);
-            }
-            p0 = p1;
-            p1 = p2;
-            m0 = m1;
+    for (int j = 0; j < 8; ++j) acc0[j] = acc1[j] = rpre0[j] = rpre1[j] = f32x2_t{0.f, 0.f};
+    if constexpr (MODE == kP8ModeB1) {
+        // the first sweep once more over this chunk, from c_0's buffer: R_1 of the wavefront's rows, in registers (the two
+        // loops run one after the other: the accumulators are reused)
+        const char *xs0 = reinterpret_cast<const char *>(a.x0) + (size_t)g * (size_t)a.group_bytes + (size_t)k * 128;
+        masked_loop_pair(a, acc0, acc1, prs, poff, pbase, n_steps, xs0, stride, lane_off);
+        const int row = a.m.vrow[chunk * 8 + grp];
+        if (row >= 0) {
+            first_residual(a, slab, row, gl, acc0, rpre0);
+            first_residual(a, slab + 1, row, gl, acc1, rpre1);
         }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc0[j] = acc1[j] = f32x2_t{0.f, 0.f};
+    }
+    if constexpr (MODE == kP8ModeB0 || MODE == kP8ModeB0N) {
+        masked_loop_pair(a, acc0, acc1, prs, poff, pbase, n_steps, xs, stride, lane_off);
     } else {
+        int2 p0 = ld_pair(prs, poff, pbase);
+        int2 p1 = ld_pair(prs, poff + 512u, pbase);
         for (int s = 0; s < n_steps; ++s) {
             const int2 p2 = ld_pair(prs, poff + (unsigned)(s + 2) * 512u, pbase);
             v4i_t x0[8], x1[8];
@@ -705,13 +801,13 @@ __device__ __forceinline__ void ppr8_pair_body(const Ppr8Args &a) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) er[j] = f32x2_t{0.f, 0.f};
         if (tgt >= 0) {
-            finish_row<MODE, RIO, EST>(a, slab + half, tgt, gl, half ? acc1 : acc0, er, mq);
+            finish_row<MODE, RIO, EST>(a, slab + half, tgt, gl, half ? acc1 : acc0, er, mq, half ? rpre1 : rpre0);
         } else if (seg) {
             st16i_sc1(half ? q1 : q0, (unsigned)(-(tgt + 1)) * 512u, gl, half ? acc1 : acc0);
         }
         if constexpr (kEst) est_commit<true>(a, slab + half, chunk, gl, grp, er);
     }
-    if constexpr (MODE == kP8ModeB || MODE == kP8ModeB0) mmax_commit<true>(a, chunk * a.mmax_units + (slab - a.mmax_slab0), mq);
+    if constexpr (MODE != kP8ModeC && MODE != kP8ModeF) mmax_commit<true>(a, chunk * a.mmax_units + (slab - a.mmax_slab0), mq);
     // long rows: as in ppr8_kernel; one arrival (the first slab's counter) covers both slabs of the pair
     if (__builtin_amdgcn_ballot_w64(seg) == 0) return;   // wave-uniform
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -750,9 +846,9 @@ __device__ __forceinline__ void ppr8_pair_body(const Ppr8Args &a) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) er[j] = f32x2_t{0.f, 0.f};
                 float m2 = 0.f;
-                finish_row<MODE, RIO, EST>(a, slab + half, a.m.lrow_row[mm], gl, acc0, er, m2);
+                finish_row<MODE, RIO, EST, true>(a, slab + half, a.m.lrow_row[mm], gl, acc0, er, m2, acc0);
                 if constexpr (kEst) est_commit<false>(a, slab + half, chunk, gl, 0, er);
-                if constexpr (MODE == kP8ModeB || MODE == kP8ModeB0) mmax_commit<false>(a, 0, m2);
+                if constexpr (MODE != kP8ModeC && MODE != kP8ModeF) mmax_commit<false>(a, 0, m2);
             }
         }
         if (lane == 0) __hip_atomic_store(cnts + mm, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1145,6 +1241,11 @@ static hrag_status sweep_dispatch(const Ppr8Args &a, int mode, bool main_only, h
     switch (mode) {
         case kP8ModeC: return sweep_mode<kP8ModeC, 0>(a, main_only, s);
         case kP8ModeB0: return sweep_mode<kP8ModeB0, 0>(a, main_only, s);
+        case kP8ModeB0N: return sweep_mode<kP8ModeB0N, 0>(a, main_only, s);
+        case kP8ModeB1:   // R_in is recomputed: never the 3-byte form
+            if (rio == 0) return sweep_mode<kP8ModeB1, 0>(a, main_only, s);
+            if (rio == 2) return sweep_mode<kP8ModeB1, 2>(a, main_only, s);
+            break;
         case kP8ModeB:
             if (rio == 0) return sweep_mode<kP8ModeB, 0>(a, main_only, s);
             if (rio == 2) return sweep_mode<kP8ModeB, 2>(a, main_only, s);

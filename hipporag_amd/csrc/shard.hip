@@ -360,6 +360,25 @@ hrag_status ppr8_begin(hrag_engine *e, const float *mn, const float *mx, const f
     HRAG_REQUIRE(n <= (int)(sizeof(p.steps) / sizeof(p.steps[0])), "internal: %d steps", n);
     p.n_steps = n;
     p.n_stage = n_stage;
+    // ---- R_1 is written once (B0) and read once (the boundary that closes stage 2): 2 x 4 bytes per row and query that
+    // the result does not need while c_0 still exists -- that boundary forms R_1 again in registers from c_0 (modes B0N /
+    // B1, ppr8.hip; bit-identical).  Applies when every step between the two is an unconditional stage sweep that leaves
+    // c_0's buffer alone (a 2-sweep stage 2: the plain plans and the accelerated plan under a tolerance; a 3-sweep stage 2
+    // needs all three buffers) and the boundary takes the fp32 R in; anything else, and HRAG_OPT_STORE_R1, keeps the
+    // stored R_1.  No change of the buffer rotation was needed: stage 2's sweep already goes 1 -> 2.  Row shards take the
+    // same path: buffer 0 is exchanged once before step 0 and not written before stage 3.
+    p.r1_long_rows = -1;
+    if (!(e->opt_flags & HRAG_OPT_STORE_R1) && p.steps[0].mode == kP8ModeB0 && p.steps[0].gate < 0) {
+        const int x0 = p.steps[0].x;
+        int i = 1;
+        while (i < n && p.steps[i].mode == kP8ModeC && p.steps[i].y != x0 && p.steps[i].gate < 0) ++i;
+        if (i < n && p.steps[i].mode == kP8ModeB && (p.steps[i].rio & 1) == 0 && p.steps[i].y != x0 &&
+            p.steps[i].gate < 0 && p.steps[0].y != x0) {
+            p.steps[0].mode = kP8ModeB0N;
+            p.steps[i].mode = kP8ModeB1;
+            p.r1_long_rows = e->sell.n_lrow;
+        }
+    }
 
     // ---- reset vector on the owned rows: per-query scale, passage prior rows, seed rows, column bitmap
     HRAG_TRY(launch_ppr8_scale(zmax, mass, passage_weight, seed_vtx, seed_w, seed_cnt, e->d_deg, e->d_iso, e->V,
@@ -421,7 +440,7 @@ hrag_status ppr8_sweep(hrag_engine *e, int32_t i, int32_t group, int32_t *exchan
     }
     a.x = p.buf[st.x];
     a.inv_cs = st.inv_cs; a.cs_next = st.cs_next;
-    const bool boundary = st.mode == kP8ModeB || st.mode == kP8ModeB0;
+    const bool boundary = st.mode != kP8ModeC && st.mode != kP8ModeF;
     if (p.dyn && st.mode != kP8ModeC) {     // measured stage scales (HRAG_OPT_ACCEL; plain plans at small damping)
         a.dyn = e->d_dyn; a.dyn_stage = st.stage;
         if (boundary) {
@@ -433,11 +452,12 @@ hrag_status ppr8_sweep(hrag_engine *e, int32_t i, int32_t group, int32_t *exchan
         a.y = p.buf[st.y];
         a.rt = p.buf[st.rt];
         a.c_mul = st.c_mul; a.r_mul = st.r_mul;
-    } else if (st.mode == kP8ModeB || st.mode == kP8ModeB0) {
+    } else if (boundary) {
         a.y = p.buf[st.y];
         a.rt = st.rt >= 0 ? p.buf[st.rt] : nullptr;
         a.rio = st.rio;
         a.stage_out = stage_copy(e, st.stage);
+        if (st.mode == kP8ModeB1) { a.x0 = p.buf[p.steps[0].x]; a.inv_cs0 = p.steps[0].inv_cs; }
     } else {   // kP8ModeF: the passage rows only; stage st.stage is the last one
         a.rt = st.rt >= 0 ? p.buf[st.rt] : nullptr;
         a.rio = st.rio;
@@ -770,8 +790,8 @@ hrag_status hrag_engine_gather_embeddings(hrag_engine *e, int32_t which, const i
 hrag_status hrag_engine_set_flags(hrag_engine *e, int32_t flags, int32_t on) {
     HRAG_REQUIRE(e != nullptr, "engine is NULL");
     const int32_t runtime = HRAG_OPT_NO_FP8 | HRAG_OPT_NT_CSR | HRAG_OPT_NT_STORE | HRAG_OPT_TEMPORAL16 | HRAG_OPT_SLABS_PER_WG_1 |
-                            HRAG_OPT_NO_F16 | HRAG_OPT_XCD_BLOCKED | HRAG_OPT_ACCEL;
-    HRAG_REQUIRE((flags & ~runtime) == 0, "only HRAG_OPT_NO_FP8 / NO_F16 / ACCEL / NT_CSR / NT_STORE / TEMPORAL16 / SLABS_PER_WG_1 / XCD_BLOCKED can change after creation");
+                            HRAG_OPT_NO_F16 | HRAG_OPT_XCD_BLOCKED | HRAG_OPT_ACCEL | HRAG_OPT_STORE_R1;
+    HRAG_REQUIRE((flags & ~runtime) == 0, "only HRAG_OPT_NO_FP8 / NO_F16 / ACCEL / STORE_R1 / NT_CSR / NT_STORE / TEMPORAL16 / SLABS_PER_WG_1 / XCD_BLOCKED can change after creation");
     if (on) e->opt_flags |= flags; else e->opt_flags &= ~flags;
     return HRAG_OK;
 }

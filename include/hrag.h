@@ -221,6 +221,15 @@ typedef struct hrag_fact_desc {
                                       /* (hipporag_amd.graph.looks_undirected, evaluated when the flag is first asked for),   */
                                       /* and refuses otherwise                                                                 */
 
+#define HRAG_OPT_STORE_R1 8192        /* fp8-state PPR: keep the stored fp32 residual R_1 between the first sweep and the     */
+                                      /* boundary that closes stage 2 instead of forming it again in registers from c_0 at    */
+                                      /* that boundary (csrc/ppr8.hip modes B0N / B1, the default: 2 GB less traffic per      */
+                                      /* retrieve at BASELINE configs[2]).  Results are bit-identical either way: the flag is */
+                                      /* the A/B lever for the R_1 round trip and the reference of                            */
+                                      /* tests/test_gpu_first_residual.py.  It is NOT the path of the builds before the       */
+                                      /* recompute: their first sweep also lacked the skip of all-zero matrix slots, which    */
+                                      /* the stored form now shares.  Runtime-switchable.                                     */
+
 typedef struct hrag_opts {
     int32_t max_batch;    /* largest B any call will pass (workspace is sized once)              */
     int32_t max_topk;     /* largest k_p (retrieval_top_k), >= 1.  Above 2048 the final rankings */
@@ -321,7 +330,9 @@ typedef struct hrag_stats {
     int32_t ppr_states;         /* HRAG_PPR_STATE_* the handle can run                                             */
     int32_t fp8_unavailable;    /* HRAG_FP8_UNAVAILABLE_* (0: the e4m3 state exists)                               */
     int32_t last_ppr_state;     /* HRAG_PPR_STATE_* the last hrag_retrieve / _scored on this handle ran on (0: none) */
-    int32_t reserved;
+    int32_t ppr8_r1_long_rows;  /* last e4m3-state PPR session of this handle: -1 = the first residual R_1 was stored for  */
+                                /* every row (HRAG_OPT_STORE_R1 or a plan the recompute does not cover); n >= 0 = it was    */
+                                /* recomputed at its boundary and only the n long rows kept the stored one (0: no session) */
     int64_t calls_score_facts, calls_retrieve, calls_dense_retrieve, calls_ppr, calls_shard;
     int64_t queries;            /* queries served by hrag_retrieve / _scored / hrag_dense_retrieve                  */
 } hrag_stats;
