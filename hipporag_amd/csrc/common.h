@@ -540,6 +540,21 @@ hrag_status launch_group_hits(const float *scores, int32_t batch, int64_t n, int
                               const int32_t *members, int64_t n_groups, const int32_t *group_idx, int32_t k, int32_t hits,
                               const TopkMask *mask, int32_t *hit_idx, float *hit_score, hipStream_t s);
 
+// fuse.hip : fused retrieval (include/hrag.h, hrag_fuse_rows / hrag_rrf_rows).  rows fp32 [batch][ld] are B member rows,
+// member_ptr int32 [n_fused + 1] (device) cuts them into questions of consecutive rows; IN PLACE, rows [0, n_fused) receive
+// the fused rows (HRAG_FUSE_SUM with optional device weights [batch], HRAG_FUSE_MAX without), the columns n .. ld untouched
+hrag_status launch_fuse_rows(float *rows, int32_t batch, int64_t n, int64_t ld, const int32_t *member_ptr, int32_t n_fused,
+                             const float *weight, int32_t mode, hipStream_t s);
+// reciprocal rank fusion of ranked lists int32 [batch][depth] (-1: empty slot; the ids of one row unique): out [n_fused][ld]
+// is zeroed over n columns, then question q's members add (float)(w / (c + rank)) in member order (fp32 chain)
+hrag_status launch_rrf_rows(const int32_t *list_idx, int32_t batch, int32_t depth, const int32_t *member_ptr,
+                            int32_t n_fused, const float *weight, int32_t c, float *out, int64_t n, int64_t ld,
+                            hipStream_t s);
+// dst uint32 [batch][words]: row m = row (question of member m) of src [n_fused][src_ld] -- a per-question doc filter as
+// the per-member filter of the RRF member rankings
+hrag_status launch_expand_filter(const uint32_t *src, int64_t src_ld, int64_t words, const int32_t *member_ptr,
+                                 int32_t batch, int32_t n_fused, uint32_t *dst, hipStream_t s);
+
 // knn.hip : fp32 rows -> the 3 * dim bf16 layout of HRAG_F32_SPLIT engines ([hi | lo | hi]; queries [hi | hi | lo])
 hrag_status launch_split3(const float *x, int64_t rows, int32_t dim, int32_t as_query, uint16_t *out, hipStream_t s,
                           int32_t normalize = 0);

@@ -1907,6 +1907,125 @@ hrag_status hrag_last_group_hits(hrag_engine *e, int32_t batch, const int32_t *g
                              k, hits, mask, hit_idx_out, hit_score_out, (hipStream_t)stream);
 }
 
+// ---- fused retrieval (include/hrag.h): sum / max / RRF over the member rows of a question, then the usual ranking
+hrag_status hrag_fuse_rows(float *scores, int32_t batch, int64_t n, int64_t ld, const int32_t *member_ptr, int32_t n_fused,
+                           const float *weight, int32_t mode, hrag_stream stream) {
+    return launch_fuse_rows(scores, batch, n, ld, member_ptr, n_fused, weight, mode, (hipStream_t)stream);
+}
+
+hrag_status hrag_rrf_rows(const int32_t *list_idx, int32_t batch, int32_t depth, const int32_t *member_ptr, int32_t n_fused,
+                          const float *weight, int32_t c, float *out, int64_t n, int64_t ld, hrag_stream stream) {
+    return launch_rrf_rows(list_idx, batch, depth, member_ptr, n_fused, weight, c, out, n, ld, (hipStream_t)stream);
+}
+
+namespace {
+// the caller's workspace of hrag_last_fused: byte offsets of its parts, each a multiple of 256
+struct FuseWs {
+    int64_t member_ptr = 0, weight = 0, list_idx = 0, list_val = 0, filter = 0, total = 0;
+};
+bool fuse_ws_layout(int32_t batch, int64_t n_passages, int32_t mode, int32_t depth, bool per_question_filter, FuseWs *w) {
+    if (batch < 1 || n_passages < 1 || mode < HRAG_FUSE_SUM || mode > HRAG_FUSE_RRF) return false;
+    int64_t at = 0;
+    auto take = [&](int64_t bytes) { const int64_t o = at; at += round_up(bytes, 256); return o; };
+    w->member_ptr = take(((int64_t)batch + 1) * 4);
+    w->weight = take((int64_t)batch * 4);
+    if (mode == HRAG_FUSE_RRF) {
+        if (depth < 1) return false;
+        w->list_idx = take((int64_t)batch * depth * 4);
+        w->list_val = take((int64_t)batch * depth * 4);
+        if (per_question_filter) w->filter = take((int64_t)batch * ceil_div(n_passages, 32) * 4);
+    }
+    w->total = at;
+    return true;
+}
+}  // namespace
+
+int64_t hrag_fuse_workspace_bytes(int32_t batch, int64_t n_passages, int32_t mode, int32_t depth,
+                                  int32_t per_question_filter) {
+    FuseWs w;
+    return fuse_ws_layout(batch, n_passages, mode, depth, per_question_filter != 0, &w) ? w.total : -1;
+}
+
+hrag_status hrag_last_fused(hrag_engine *e, int32_t batch, const int32_t *member_ptr, int32_t n_fused, const float *weight,
+                            int32_t mode, int32_t rrf_c, int32_t rrf_depth, int32_t k, const uint32_t *filter_dev,
+                            int64_t filter_ld_words, int32_t group_agg, int32_t *doc_idx_out, float *doc_score_out,
+                            int32_t *group_idx_out, float *group_score_out, int32_t *best_doc_idx_out, void *workspace,
+                            size_t workspace_bytes, hrag_stream stream) {
+    HRAG_TRY(check_batch(e, batch));
+    HRAG_REQUIRE(e->p_rows == e->n_passages && e->n_rows == e->V,
+                 "hrag_last_fused on a row-shard engine: its score rows are slices of the passages (fused retrieval is "
+                 "served by the unsharded engine only)");
+    HRAG_REQUIRE(member_ptr != nullptr, "NULL argument");
+    HRAG_REQUIRE(n_fused >= 1 && n_fused <= batch, "n_fused=%d outside [1, batch=%d]", n_fused, batch);
+    HRAG_REQUIRE(member_ptr[0] == 0 && member_ptr[n_fused] == batch, "member_ptr must run from 0 to batch=%d (it runs from %d to %d)",
+                 batch, member_ptr[0], member_ptr[n_fused]);
+    for (int32_t q = 0; q < n_fused; ++q)
+        HRAG_REQUIRE(member_ptr[q + 1] > member_ptr[q], "member_ptr is not strictly increasing at question %d (%d, %d): every "
+                     "question has at least one member", q, member_ptr[q], member_ptr[q + 1]);
+    HRAG_REQUIRE(mode == HRAG_FUSE_SUM || mode == HRAG_FUSE_MAX || mode == HRAG_FUSE_RRF,
+                 "mode=%d: HRAG_FUSE_SUM (0), HRAG_FUSE_MAX (1) or HRAG_FUSE_RRF (2)", mode);
+    HRAG_REQUIRE(mode != HRAG_FUSE_MAX || weight == nullptr, "HRAG_FUSE_MAX takes no weights");
+    if (weight)
+        for (int32_t i = 0; i < batch; ++i)
+            HRAG_REQUIRE(std::isfinite(weight[i]) && weight[i] >= 0.f, "weight[%d]=%g: every weight must be finite and >= 0", i,
+                         (double)weight[i]);
+    if (mode == HRAG_FUSE_RRF) {
+        HRAG_REQUIRE(rrf_c >= 0, "rrf_c=%d: at least 0", rrf_c);
+        const int64_t dmax = std::min<int64_t>(e->max_topk, e->n_passages);
+        HRAG_REQUIRE(rrf_depth >= 1 && rrf_depth <= dmax, "rrf_depth=%d outside [1, min(max_topk, n_passages)=%lld]", rrf_depth,
+                     (long long)dmax);
+    }
+    TopkMask fm;
+    const TopkMask *mask = nullptr;
+    HRAG_TRY(doc_filter(e, filter_dev, filter_ld_words, fm, &mask));
+    HRAG_REQUIRE((doc_idx_out != nullptr) == (doc_score_out != nullptr), "doc_idx_out / doc_score_out: both or neither");
+    const GroupOut g{group_agg, group_idx_out, group_score_out, best_doc_idx_out};
+    const GroupOut *grp = group_agg >= 0 ? &g : nullptr;
+    if (grp) HRAG_TRY(check_grouped(e, grp));
+    if (doc_idx_out || grp) HRAG_REQUIRE(k >= 1 && k <= e->max_topk, "k=%d outside [1, max_topk=%d]", k, e->max_topk);
+    FuseWs ws;
+    const bool per_q = mask && mask->ld_words != 0;
+    HRAG_REQUIRE(fuse_ws_layout(batch, e->n_passages, mode, rrf_depth, per_q, &ws), "bad argument");
+    HRAG_REQUIRE(workspace && (int64_t)workspace_bytes >= ws.total, "workspace of %lld bytes, %lld needed (hrag_fuse_workspace_bytes)",
+                 (long long)workspace_bytes, (long long)ws.total);
+    HRAG_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "the workspace must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    HRAG_ENGINE_CALL(e, stream);   // (rows_batch is read inside the call: another thread's retrieve cannot be rewriting it)
+    HRAG_REQUIRE(e->d_doc && e->rows_batch >= 1,
+                 "no score rows on this handle: hrag_last_fused follows a retrieve, a scored or a grouped dense call (the "
+                 "ungrouped dense calls do not write the rows)");
+    HRAG_REQUIRE(batch <= e->rows_batch, "batch=%d exceeds the %d queries of the call that wrote the score rows", batch,
+                 e->rows_batch);
+    char *base = static_cast<char *>(workspace);
+    int32_t *d_ptr = reinterpret_cast<int32_t *>(base + ws.member_ptr);
+    float *d_w = weight ? reinterpret_cast<float *>(base + ws.weight) : nullptr;
+    e->rows_batch = 0;             // the rows are being rewritten; set again when the fusion is enqueued
+    HRAG_HIP_TRY(hipMemcpyAsync(d_ptr, member_ptr, ((size_t)n_fused + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (weight) HRAG_HIP_TRY(hipMemcpyAsync(d_w, weight, (size_t)batch * sizeof(float), hipMemcpyHostToDevice, s));
+    if (mode == HRAG_FUSE_RRF) {
+        int32_t *lists = reinterpret_cast<int32_t *>(base + ws.list_idx);
+        float *vals = reinterpret_cast<float *>(base + ws.list_val);
+        TopkMask mm;
+        const TopkMask *member_mask = mask;
+        if (per_q) {   // one filter row per question -> one per member row
+            uint32_t *rows = reinterpret_cast<uint32_t *>(base + ws.filter);
+            const int64_t words = ceil_div(e->n_passages, 32);
+            HRAG_TRY(launch_expand_filter(mask->words, mask->ld_words, words, d_ptr, batch, n_fused, rows, s));
+            mm = TopkMask{rows, words, 0};
+            member_mask = &mm;
+        }
+        HRAG_TRY(rank_rows(e, e->d_doc, batch, e->n_passages, rrf_depth, 0, kNormNone, lists, vals, s, member_mask));
+        HRAG_TRY(launch_rrf_rows(lists, batch, rrf_depth, d_ptr, n_fused, d_w, rrf_c, e->d_doc, e->n_passages, e->ld_p, s));
+    } else {
+        HRAG_TRY(launch_fuse_rows(e->d_doc, batch, e->n_passages, e->ld_p, d_ptr, n_fused, d_w, mode, s));
+    }
+    e->rows_batch = n_fused;
+    if (doc_idx_out)
+        HRAG_TRY(rank_rows(e, e->d_doc, n_fused, e->n_passages, k, 0, kNormNone, doc_idx_out, doc_score_out, s, mask));
+    if (grp) HRAG_TRY(rank_groups(e, e->d_doc, n_fused, k, mask, grp, s));
+    return HRAG_OK;
+}
+
 hrag_status hrag_ppr(hrag_engine *e, const float *reset, int32_t batch, float damping, int32_t iters,
                      float *x_out, int32_t *flags_out, hrag_stream stream) {
     HRAG_TRY(check_batch(e, batch));

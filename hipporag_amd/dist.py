@@ -433,7 +433,7 @@ class ShardedRetriever:
     def retrieve(self, q_pass, kept_idx, kept_score, kept_count, *, link_top_k=5, damping=0.5,
                  passage_node_weight=0.05, ppr_iters=20, k=200, ppr_tol=0.0, ppr_max_iters=0,
                  check_saturation=True, doc_filter=None, filter_scope: str = "ranking", group_agg=None,
-                 group_hits=None):
+                 group_hits=None, fuse=None):
         """Returns (doc ids, doc scores, flags) -- and with ppr_tol > 0 additionally (residual, sweeps used): the
         convergence contract of hrag_retrieve on the shards.  Every shard measures the relative update of ITS
         passages; the measures are all-reduced (MAX) before every decision, so all shards run the same steps.
@@ -446,7 +446,7 @@ class ShardedRetriever:
         filter_scope="seeds": the passage prior and the DPR fallback normalised over the allowed passages of every shard
         (= HippoRAGEngine.retrieve(filter_scope="seeds"); the kept facts from score_facts(scope_filter=))."""
         from .engine import refuse_group_agg
-        refuse_group_agg("ShardedRetriever", {"group_agg": group_agg, "group_hits": group_hits})
+        refuse_group_agg("ShardedRetriever", {"group_agg": group_agg, "group_hits": group_hits, "fuse": fuse})
         scoped = serve_seeds_scope(getattr(self, "st", None), filter_scope)
         if scoped:
             from .engine import check_filter_scope
@@ -632,11 +632,11 @@ class NativeShardedRetriever:
 
     def retrieve(self, q_pass, kept_idx, kept_score, kept_count, *, link_top_k=5, damping=0.5, passage_node_weight=0.05,
                  ppr_iters=20, k=200, ppr_tol=0.0, ppr_max_iters=0, check_saturation=True, doc_filter=None,
-                 filter_scope: str = "ranking", group_agg=None, group_hits=None):
+                 filter_scope: str = "ranking", group_agg=None, group_hits=None, fuse=None):
         """Same contract as ShardedRetriever.retrieve: (doc ids, doc scores, flags[, residual, sweeps used]);
         doc_filter: hrag_shard_retrieve_filtered with the global filter (filter_scope="seeds": hrag_shard_retrieve_scoped)."""
         from .engine import refuse_group_agg
-        refuse_group_agg("NativeShardedRetriever", {"group_agg": group_agg, "group_hits": group_hits})
+        refuse_group_agg("NativeShardedRetriever", {"group_agg": group_agg, "group_hits": group_hits, "fuse": fuse})
         scoped = serve_seeds_scope(getattr(self, "st", None), filter_scope)
         if scoped:
             from .engine import check_filter_scope
@@ -761,6 +761,7 @@ def run_local_shards(world: int, sidx: "ShardedIndex", pass_emb, fact_emb, q_fac
     from .engine import ShardStages
     shared, results, errors = {}, [None] * world, []
     b = q_fact.shape[0]
+    filter_lock = threading.Lock()      # filter_fn is the caller's host code: one shard thread inside it at a time
 
     def worker(rank):
         try:
@@ -775,7 +776,8 @@ def run_local_shards(world: int, sidx: "ShardedIndex", pass_emb, fact_emb, q_fac
             idx, sc = rs.score_facts(q_fact, k=5, **_phase_a_scope(retrieve_kw))
             cnt = _kept_count(idx, retrieve_kw)
             if filter_fn is not None:
-                idx, sc, cnt = filter_fn(idx, sc)
+                with filter_lock:
+                    idx, sc, cnt = filter_fn(idx, sc)
             d_idx, d_sc, flags = rs.retrieve(q_pass, idx, sc, cnt, **retrieve_kw)[:3]   # ppr_tol > 0: + (residual, sweeps)
             torch.cuda.synchronize()
             if timings is not None and rank == 0:

@@ -57,6 +57,7 @@ def pack_mask(mask) -> np.ndarray:
 FILTER_SCOPES = ("ranking", "seeds")
 GROUP_AGGS = {"max": 0, "sum": 1}      # HRAG_GROUP_MAX / HRAG_GROUP_SUM
 GROUP_HITS_MAX = 64                    # HRAG_GROUP_HITS_MAX
+FUSE_MODES = {"sum": 0, "max": 1, "rrf": 2}     # HRAG_FUSE_SUM / HRAG_FUSE_MAX / HRAG_FUSE_RRF
 
 
 def check_group_agg(group_agg) -> Optional[int]:
@@ -82,6 +83,43 @@ def check_group_hits(group_hits, group_agg) -> Optional[int]:
     return int(group_hits)
 
 
+def check_fuse(fuse, member_ptr, batch: int, weights=None, rrf_c: int = 60, rrf_depth=None, depth_max=None):
+    """The arguments of a fused call (include/hrag.h, fused retrieval) as the library takes them: (mode, member_ptr int32
+    [Q + 1], weights fp32 [batch] or None, rrf_c, rrf_depth).  member_ptr runs from 0 to batch, strictly increasing; every
+    weight is finite and >= 0 and "max" takes none; "rrf": an int rrf_c >= 0 and 1 <= rrf_depth <= depth_max (min(max_topk,
+    n_passages) of the engine; not checked when None).  The other modes return rrf_c = 0, rrf_depth = 0."""
+    if fuse not in FUSE_MODES:
+        raise ValueError(f"fuse={fuse!r}: 'sum', 'max' or 'rrf' expected")
+    mp = np.asarray(member_ptr)
+    if mp.ndim != 1 or mp.shape[0] < 2 or mp.dtype.kind not in "iu":
+        raise ValueError("member_ptr: an integer array of Q + 1 >= 2 entries expected")
+    mp = mp.astype(np.int64)
+    if mp[0] != 0 or mp[-1] != batch:
+        raise ValueError(f"member_ptr must run from 0 to the batch of {batch} member rows (it runs from {mp[0]} to {mp[-1]})")
+    if (np.diff(mp) <= 0).any():
+        raise ValueError("member_ptr must be strictly increasing: every question has at least one member")
+    w = None
+    if weights is not None:
+        if fuse == "max":
+            raise ValueError('fuse="max" takes no weights')
+        w = np.asarray(weights, np.float32)
+        if w.shape != (batch,):
+            raise ValueError(f"weights of shape {w.shape}: one per member row, ({batch},), expected")
+        if not np.isfinite(w).all() or (w < 0).any():
+            raise ValueError("every weight must be finite and >= 0")
+        w = np.ascontiguousarray(w)
+    c = depth = 0
+    if fuse == "rrf":
+        if isinstance(rrf_c, bool) or not isinstance(rrf_c, (int, np.integer)) or not 0 <= int(rrf_c) < 2 ** 31:
+            raise ValueError(f"rrf_c={rrf_c!r}: an int >= 0 expected")
+        if isinstance(rrf_depth, bool) or not isinstance(rrf_depth, (int, np.integer)):
+            raise ValueError(f"rrf_depth={rrf_depth!r}: an int >= 1 expected")
+        if int(rrf_depth) < 1 or (depth_max is not None and int(rrf_depth) > depth_max):
+            raise ValueError(f"rrf_depth={rrf_depth}: outside [1, {depth_max if depth_max is not None else 'min(max_topk, n_passages)'}]")
+        c, depth = int(rrf_c), int(rrf_depth)
+    return FUSE_MODES[fuse], np.ascontiguousarray(mp, dtype=np.int32), w, c, depth
+
+
 def group_table_csr(group_of, n_groups: int):
     """The CSR the engine builds from a passage -> group table: (group_ptr int64 [n_groups + 1], members int32 [n],
     the members of a group in ascending passage position)."""
@@ -99,6 +137,10 @@ def refuse_group_agg(who: str, kw: dict) -> None:
     if kw.get("group_hits") is not None:
         raise NotImplementedError(f"{who} does not serve group_hits (the best passages of each ranked group): use "
                                   "HippoRAGEngine.retrieve")
+    if kw.get("fuse") is not None:
+        raise NotImplementedError(f"{who} does not serve fuse (one ranking per question from several member queries): the "
+                                  "fusion works on the score rows of one unsharded handle -- use HippoRAGEngine.retrieve + "
+                                  "last_fused")
 
 
 def check_filter_scope(filter_scope: str, doc_filter) -> bool:
@@ -496,6 +538,7 @@ class HippoRAGEngine:
         w._handle = C.c_void_p(0)
         w._workspaces = []
         w._parent = root
+        w._fuse_ws = w._fuse_host = None         # last_fused: a scratch buffer of its own
         with _torch().cuda.device(root.device):
             check(root._lib.hrag_workspace_create(root._handle, C.byref(w._handle)))
         if not hasattr(root, "_workspaces"):
@@ -677,6 +720,48 @@ class HippoRAGEngine:
                                              filter_words.data_ptr() if filter_words is not None else None, filter_ld,
                                              hi.data_ptr(), hs.data_ptr(), _stream()))
         return hi, hs
+
+    def last_fused(self, member_ptr, *, weights=None, fuse: str = "rrf", rrf_c: int = 60, rrf_depth: Optional[int] = None,
+                   k: int = 200, doc_filter=None, group_agg: Optional[str] = None,
+                   group_hits: Optional[int] = None) -> RetrieveOutput:
+        """One ranking per QUESTION from the score rows the last retrieve / retrieve_scored / grouped dense_retrieve on this
+        handle left (hrag_last_fused; include/hrag.h, fused retrieval): member_ptr int [Q + 1] cuts those B = member_ptr[-1]
+        rows into Q questions of consecutive member rows, weights [B] (None: all 1) weigh them, fuse = "sum" (fp64, in member
+        order), "max" or "rrf" (rrf_c, rrf_depth: default min(k, max_topk, n_passages)).  Returns doc_idx / doc_score [Q, k]
+        of the fused rows under doc_filter ([n] for every question or [Q, n]; for "rrf" also the filter of the member
+        rankings); with group_agg the grouped ranking instead (group_idx, group_score = doc_score, best_doc_idx = doc_idx)
+        and with group_hits=m its hits.  flags / residual / iters_used are None: they belong to the member rows.
+        Afterwards last_doc_scores(Q) returns the fused rows."""
+        torch = _torch()
+        agg = check_group_agg(group_agg)
+        hits = check_group_hits(group_hits, group_agg)
+        b = int(np.asarray(member_ptr).reshape(-1)[-1]) if np.size(member_ptr) else 0
+        dmax = min(self.max_topk, self.n_passages)
+        mode, mp, w, c, depth = check_fuse(fuse, member_ptr, b, weights, rrf_c,
+                                           min(k, dmax) if rrf_depth is None else rrf_depth, dmax)
+        nq = mp.shape[0] - 1
+        fw, fld = (None, 0) if doc_filter is None else doc_filter_words(doc_filter, self.n_passages, nq, self.device)
+        need = int(self._lib.hrag_fuse_workspace_bytes(b, self.n_passages, mode, depth, 1 if fld else 0))
+        if need < 0:
+            raise ValueError(f"hrag_fuse_workspace_bytes rejects batch={b}, mode={fuse!r}, depth={depth}")
+        ws = getattr(self, "_fuse_ws", None)
+        if ws is None or ws.numel() < need:
+            ws = self._fuse_ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        idx = self._empty((nq, k), torch.int32)
+        sc = self._empty((nq, k), torch.float32)
+        gi = self._empty((nq, k), torch.int32) if agg is not None else None
+        self._fuse_host = (getattr(self, "_fuse_host", None) or [])[-1:] + [(mp, w)]   # alive until the stream copied them
+        check(self._lib.hrag_last_fused(
+            self._handle, b, mp.ctypes.data, nq, w.ctypes.data if w is not None else None, mode, c, depth, k,
+            fw.data_ptr() if fw is not None else None, fld, -1 if agg is None else agg,
+            None if agg is not None else idx.data_ptr(), None if agg is not None else sc.data_ptr(),
+            gi.data_ptr() if agg is not None else None, sc.data_ptr() if agg is not None else None,
+            idx.data_ptr() if agg is not None else None, ws.data_ptr(), ws.numel(), _stream()))
+        out = RetrieveOutput(idx, sc, None)
+        out.group_idx = gi
+        if hits is not None:
+            out.hit_idx, out.hit_score = self.last_group_hits(gi, hits, fw, fld)
+        return out
 
     def retrieve_scored(self, pass_scores, kept_idx, kept_score, kept_count, *, link_top_k: int = 5,
                         damping: float = 0.5, passage_node_weight: float = 0.05, ppr_iters: int = 20, k: int = 200,

@@ -224,6 +224,8 @@ class BatchRows(list):
     group_idx = None     # grouped retrieval: int32 [b, k] group ids (doc_idx: each group's best passage, doc_score: its score)
     hit_idx = None       # group_hits=m: int32 [b, k, m] the best m allowed passages of each ranked group (-1 beyond them)
     hit_score = None     # fp32 [b, k, m] their own scores
+    all_scores = None    # keep_all_scores=True: the device tensor fp32 [b, Np] of every passage's score
+    repeated = False     # the convergence contract ran rows of the batch again: the engine's score rows are not the batch's
 
 
 def unpack_mask(words, n: int) -> np.ndarray:
@@ -309,6 +311,41 @@ def group_rank_rows(full, group_of, allowed, want: int, agg: str = "max", hits: 
     return gi, gs, rep
 
 
+def fuse_rows_host(full, member_ptr, fuse: str, weights=None, rrf_c: int = 60, rrf_depth: int = 1, allowed=None):
+    """The host form of the fusion (include/hrag.h, fused retrieval): member rows `full` fp32 [B, n] cut into questions by
+    member_ptr -> fused rows fp32 [Q, n].  "sum": fp64 in member order, rounded once; "max": the member score that ranks
+    first (any NaN wins; -0 as +0); "rrf": every member ranked at rrf_depth under its question's row of `allowed` (None,
+    bool [n] or [Q, n]), float32(w / (rrf_c + rank)) added in fp32 in member order."""
+    full = np.asarray(full, np.float32)
+    mp = np.asarray(member_ptr, np.int64)
+    nq, n = len(mp) - 1, full.shape[1]
+    w = np.ones(full.shape[0], np.float32) if weights is None else np.asarray(weights, np.float32)
+    out = np.zeros((nq, n), np.float32)
+    if fuse == "rrf":
+        allowed = np.ones((nq, n), bool) if allowed is None else np.broadcast_to(np.asarray(allowed, bool), (nq, n))
+        lists, _ = rank_allowed(full, np.repeat(allowed, np.diff(mp), axis=0), rrf_depth)
+        rank = np.arange(1, rrf_depth + 1, dtype=np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for q in range(nq):
+            rows = range(mp[q], mp[q + 1])
+            if fuse == "sum":
+                acc = np.zeros(n, np.float64)
+                for i in rows:
+                    acc = acc + np.float64(w[i]) * full[i].astype(np.float64)
+                out[q] = acc.astype(np.float32)
+            elif fuse == "max":
+                m = full[mp[q]: mp[q + 1]]
+                best = np.where(np.isnan(m), -np.inf, m).max(axis=0)
+                out[q] = np.where(np.isnan(m).any(axis=0), np.float32(np.nan), best) + np.float32(0)
+            else:
+                for i in rows:
+                    keep = lists[i] >= 0
+                    t = (np.float64(w[i]) / (np.float64(rrf_c) + rank)).astype(np.float32)
+                    out[q, lists[i][keep]] = out[q, lists[i][keep]] + t[keep]
+    out[np.isnan(out)] = np.float32(np.nan)
+    return out
+
+
 def masked_minmax_rows(raw, allowed):
     """The dense scores of the "seeds" scope on the host: per row, min_max_normalize over the allowed entries (a zero
     range gives 1), 0 elsewhere."""
@@ -343,7 +380,7 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
                           num_to_retrieve: int, n_passages: int, timers=None, ppr_tol: float = 0.0,
                           ppr_max_iters: int = 0, ppr_base_iters_narrow: Optional[int] = None, doc_filter=None,
                           filter_scope: str = "ranking", group_agg: Optional[str] = None, group_of=None,
-                          group_hits: Optional[int] = None):
+                          group_hits: Optional[int] = None, keep_all_scores: bool = False):
     """The body of retrieve() (HippoRAG.py:459-480), shared by the mirror class below and by
     reference_adapter.attach(): phase A on the device, the recognition-memory filter on the host (rerank_facts
     :1659-1707), phase B on the device, in batches of eng.max_batch queries.  Yields (offset of the batch, [(doc ids,
@@ -369,7 +406,9 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
     group_agg ("max" / "sum") with group_of (int array over the passages, already set on the engine): the rows rank
     GROUPS -- doc ids are each group's best passage, doc scores the group scores, rows.group_idx the group ids.
     group_hits=m (with group_agg): rows.hit_idx / rows.hit_score [b, k, m], the best m allowed passages of every ranked
-    group; the engine serves them right behind each batch's grouped call, the host form beyond max_topk."""
+    group; the engine serves them right behind each batch's grouped call, the host form beyond max_topk.
+    keep_all_scores: rows.all_scores is the device tensor of every passage's score of the batch and rows.repeated tells
+    whether the contract ran rows again (retrieve_fused: the engine's own score rows are then not the batch's)."""
     import torch
     from .engine import host_copy_async, host_wait
     k_f = int(linking_top_k)
@@ -451,7 +490,8 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
             # split is an argument about damping^9: csrc/engine.hip two_stage_ok; other damping factors keep the count above)
             base = max(11, min(int(ppr_base_iters_narrow), ppr_iters))     # narrow batch under the contract: latency mode
         kw = dict(link_top_k=k_f, damping=damping, passage_node_weight=passage_node_weight, ppr_iters=base,
-                  k=k_docs, ppr_tol=ppr_tol, ppr_max_iters=ppr_max_iters, **({"want_all_scores": True} if beyond else {}))
+                  k=k_docs, ppr_tol=ppr_tol, ppr_max_iters=ppr_max_iters,
+                  **({"want_all_scores": True} if beyond or keep_all_scores else {}))
         if doc_filter is not None:
             kw["doc_filter"] = scope_rows(doc_filter, bt.lo, b)
             if scoped:
@@ -513,6 +553,9 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
         rows = BatchRows()
         rows.doc_idx, rows.doc_score, rows.group_idx = d_idx, d_sc, g_idx
         rows.hit_idx, rows.hit_score = h_idx, h_sc
+        if keep_all_scores:
+            rows.all_scores = getattr(out, "all_scores", None)
+            rows.repeated = bt.pending is None or bt.pending.repeated
         for i in range(len(bt.qs)):
             if flags[i] & 4:      # :1541
                 raise AssertionError("count_nonzero(all_phrase_weights) != len(linking_score_map)")
@@ -1174,6 +1217,124 @@ class HippoRAG:
                     results.extend(self._group_solutions(queries[lo: lo + len(rows)], rows, table, num_to_retrieve))
                     continue
                 results.extend(self._build_query_solutions(queries[lo: lo + len(rows)], rows, num_to_retrieve))
+
+    # ------------------------------------------------------------------ fused retrieval
+    def retrieve_fused(self, questions: List[List[str]], weights=None, fuse: str = "rrf", rrf_c: int = 60,
+                       rrf_depth: Optional[int] = None, num_to_retrieve: Optional[int] = None, doc_filter=None,
+                       filter_scope: Optional[str] = None, group_by=None, group_agg: Optional[str] = None,
+                       group_hits: Optional[int] = None):
+        """One ranked list per QUESTION, each question given as several sub-queries -- a decomposition, paraphrases, the
+        thoughts of an IRCoT chain (include/hrag.h, fused retrieval).  Every sub-query runs phase A and phase B as in
+        retrieve(); the score rows of a question's sub-queries are fused ON THE DEVICE over all passages -- fuse="sum"
+        (weighted, fp64), "max" (what retrieve_ircot merges by, over every passage instead of the returned lists) or "rrf"
+        (reciprocal rank fusion, constant rrf_c, lists of rrf_depth entries: default num_to_retrieve) -- and the fused rows
+        are ranked like any other: doc_filter (one per QUESTION), filter_scope, group_by / group_agg / group_hits as in
+        retrieve().  weights: one list per question (or a flat array over all sub-queries), finite and >= 0, not with
+        "max".  Returns one QuerySolution per question; its `question` is the question's first sub-query.  A question's
+        sub-queries share one device batch: at most max_batch of them."""
+        from .engine import check_fuse
+        t_start = time.time()
+        cfg = self.global_config
+        if num_to_retrieve is None:
+            num_to_retrieve = cfg.retrieval_top_k
+        if not isinstance(questions, (list, tuple)) or any(
+                not isinstance(q, (list, tuple)) or not q or not all(isinstance(s, str) for s in q) for q in questions):
+            raise ValueError("questions: a list of non-empty lists of strings (the sub-queries of each question) expected")
+        sizes = np.asarray([len(q) for q in questions], np.int64)
+        member_ptr = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        flat = [s for q in questions for s in q]
+        w_flat = None
+        if weights is not None:
+            if len(weights) == len(questions) and all(np.ndim(w) == 1 for w in weights):
+                if [len(w) for w in weights] != sizes.tolist():
+                    raise ValueError("weights: one weight per sub-query of every question expected")
+                w_flat = np.concatenate([np.asarray(w, np.float32) for w in weights]) if questions else np.zeros(0, np.float32)
+            else:
+                w_flat = np.asarray(weights, np.float32)
+        if not questions:
+            return []
+        depth = num_to_retrieve if rrf_depth is None else rrf_depth
+        check_fuse(fuse, member_ptr, len(flat), w_flat, rrf_c, max(1, depth) if rrf_depth is None else depth)
+        self._ensure_ready()
+        eng = self.engine
+        if not hasattr(eng, "last_fused"):
+            raise NotImplementedError(f"{type(eng).__name__} does not serve fuse: the fusion works on the score rows of one "
+                                      "unsharded engine handle")
+        if int(sizes.max()) > eng.max_batch:
+            raise ValueError(f"a question of {int(sizes.max())} sub-queries exceeds max_batch={eng.max_batch}")
+        n_p = len(self.passage_node_keys)
+        dmax = min(eng.max_topk, n_p)
+        if fuse == "rrf":
+            if rrf_depth is not None and not 1 <= depth <= dmax:
+                raise ValueError(f"rrf_depth={rrf_depth}: outside [1, min(max_topk, n_passages) = {dmax}]")
+            depth = max(1, min(depth, dmax))
+        scope = self._scope(filter_scope, doc_filter)
+        words = self._doc_filter_words(doc_filter, len(questions))
+        agg, table = self._grouping(group_by, group_agg)
+        hits = self._hits(group_hits, agg)
+        if agg is not None:
+            self._engine_groups(table)
+        want = max(1, min(int(num_to_retrieve), n_p if agg is None else int(np.max(table[0])) + 1))
+        k_docs = min(want, eng.max_topk)
+        self.get_query_embeddings(flat)
+        # whole questions per device batch
+        chunks, lo = [], 0
+        while lo < len(questions):
+            hi = lo + 1
+            while hi < len(questions) and member_ptr[hi + 1] - member_ptr[lo] <= eng.max_batch:
+                hi += 1
+            chunks.append((lo, hi))
+            lo = hi
+        results: List[QuerySolution] = []
+        import torch
+        for lo, hi in chunks:
+            m0, m1 = int(member_ptr[lo]), int(member_ptr[hi])
+            mp = member_ptr[lo: hi + 1] - m0
+            q_words = None if words is None else (words if words.ndim == 1 else words[lo:hi])
+            extra = {}
+            if words is not None:       # the member runs: every sub-query under its question's filter
+                extra = {"doc_filter": words if words.ndim == 1 else np.repeat(words[lo:hi], sizes[lo:hi], axis=0),
+                         "filter_scope": scope}
+            (_, rows), = iter_batched_retrieve(eng, flat[m0:m1], self._q_tensor, self.facts if self.fact_node_keys else [],
+                                               self.rerank_filter, linking_top_k=cfg.linking_top_k, damping=cfg.damping,
+                                               passage_node_weight=cfg.passage_node_weight, ppr_iters=self._ppr_iters(),
+                                               ppr_tol=cfg.ppr_tol, ppr_max_iters=cfg.ppr_max_iters,
+                                               ppr_base_iters_narrow=cfg.ppr_base_iters_narrow, num_to_retrieve=1,
+                                               n_passages=n_p, timers=self, keep_all_scores=True, **extra)
+            w = None if w_flat is None else w_flat[m0:m1]
+            fused_rows = BatchRows()
+            if rows.repeated or k_docs < want:
+                # the contract ran some sub-queries again (the engine's rows are no longer this batch's), or more documents
+                # are wanted than the device ranks: the host form over the batch's score rows
+                allowed = None if q_words is None else unpack_mask(q_words, n_p)
+                fused = fuse_rows_host(rows.all_scores.cpu().numpy(), mp, fuse, w, rrf_c, depth, allowed)
+                if agg is not None:
+                    fused_rows.group_idx, fused_rows.doc_score, fused_rows.doc_idx, *h = group_rank_rows(
+                        fused, table[0], allowed, want, agg, hits)
+                    if h:
+                        fused_rows.hit_idx, fused_rows.hit_score = h
+                else:
+                    fused_rows.doc_idx, fused_rows.doc_score = rank_allowed(
+                        fused, np.ones(n_p, bool) if allowed is None else allowed, want)
+                    fused_rows.doc_score = fused_rows.doc_score + np.float32(0)
+            else:
+                flt = None if q_words is None else torch.from_numpy(np.ascontiguousarray(q_words).view(np.int32))
+                out = eng.last_fused(mp, weights=w, fuse=fuse, rrf_c=rrf_c, rrf_depth=depth if fuse == "rrf" else None,
+                                     k=k_docs, doc_filter=flt, group_agg=agg, group_hits=hits)
+                fused_rows.doc_idx, fused_rows.doc_score = out.doc_idx.cpu().numpy(), out.doc_score.cpu().numpy()
+                if agg is not None:
+                    fused_rows.group_idx = out.group_idx.cpu().numpy()
+                if hits is not None:
+                    fused_rows.hit_idx, fused_rows.hit_score = out.hit_idx.cpu().numpy(), out.hit_score.cpu().numpy()
+            for j in range(hi - lo):
+                seeds = [f for i in range(int(mp[j]), int(mp[j + 1])) for f in (rows[i][2] or [])]
+                fused_rows.append((fused_rows.doc_idx[j], fused_rows.doc_score[j], seeds))
+            firsts = [q[0] for q in questions[lo:hi]]
+            with gc_paused():
+                results.extend(self._group_solutions(firsts, fused_rows, table, num_to_retrieve) if agg is not None
+                               else self._build_query_solutions(firsts, fused_rows, num_to_retrieve))
+        self.all_retrieval_time += time.time() - t_start
+        return results
 
     # ------------------------------------------------------------------ retrieve_ircot :509-558
     def retrieve_ircot(self, queries: List[str], max_qa_steps: int, num_to_retrieve: Optional[int] = None,

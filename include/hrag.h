@@ -66,7 +66,9 @@ extern "C" {
  *        hrag_dense_retrieve_scoped;
  *        later in 0.8 (detect by the symbol): the scoped doc filter on row shards -- hrag_shard_score_facts_scoped,
  *        hrag_shard_passage_scores_scoped, hrag_shard_mask_prior, hrag_shard_score_facts_all_scoped,
- *        hrag_shard_retrieve_scoped (hrag_engine_set_fact_sources then accepts a row-shard engine). */
+ *        hrag_shard_retrieve_scoped (hrag_engine_set_fact_sources then accepts a row-shard engine);
+ *        later in 0.8 (detect by the symbol): fused retrieval -- hrag_fuse_rows, hrag_rrf_rows,
+ *        hrag_fuse_workspace_bytes, hrag_last_fused. */
 #define HRAG_VERSION_MAJOR 0
 #define HRAG_VERSION_MINOR 8
 
@@ -678,6 +680,72 @@ hrag_status hrag_group_hits_rows(const float *scores_dev, int32_t batch, int64_t
 hrag_status hrag_last_group_hits(hrag_engine *e, int32_t batch, const int32_t *group_idx_dev, int32_t k, int32_t hits,
                                  const uint32_t *filter_dev, int64_t filter_ld_words, int32_t *hit_idx_out_dev,
                                  float *hit_score_out_dev, hrag_stream stream);
+
+/* ---- fused retrieval: one ranking per QUESTION from several member queries ----
+ * A multi-hop caller sends a question as several strings -- sub-questions, paraphrases, the thoughts of an IRCoT chain
+ * (retrieve_ircot merges their document scores by max, HippoRAG.py:526-543) -- and wants ONE ranked list.  A batch of B
+ * member rows is cut into Q questions by member_ptr int32 [Q + 1]: member_ptr[0] = 0, member_ptr[Q] = B, strictly
+ * increasing -- every question has at least one member and its members are consecutive rows.  weight fp32 [B], NULL = all
+ * 1; every weight finite and >= 0.  With s_i(p) the final score of passage p for member i (hrag_last_doc_scores) the
+ * fused row of question q over ALL n_passages columns is
+ *   HRAG_FUSE_SUM  the fp64 chain acc = +0.0; acc += (double)w_i * (double)s_i(p) in member order, rounded once to fp32
+ *                  (the product of two fp32 values is exact in fp64); a NaN result is the quiet NaN 0x7fc00000;
+ *   HRAG_FUSE_MAX  the member score with the largest ranking key under the rule at the top of this header (any NaN wins),
+ *                  as the ranking returns scores: the quiet NaN, -0 as +0.  Takes no weights (HRAG_EINVAL);
+ *   HRAG_FUSE_RRF  reciprocal rank fusion with a constant c >= 0 (the usual 60) and a depth d, 1 <= d <= min(max_topk,
+ *                  n_passages): every member row is ranked at depth d by the rule at the top of this header, under its
+ *                  question's filter row; a passage at 1-based rank r of member i contributes
+ *                  t = (float)((double)w_i / (double)(c + r)), and the fused value is the fp32 chain acc = 0.0f;
+ *                  acc = acc + t in member order over the members that list the passage.  A passage no member lists has
+ *                  fused score +0.0 (among the allowed passages it ranks behind every listed one, by the usual tie rule).
+ * No atomics anywhere (csrc/fuse.hip): every value is one chain in a fixed order, bitwise reproducible.
+ * After a fusion rows [0, Q) of the handle's score rows hold the fused rows, the recorded batch of the rows becomes Q, rows
+ * >= Q are unspecified; the fused rows are then ranked exactly as a retrieve call ranks its rows -- hrag_last_doc_scores
+ * and hrag_last_group_hits with batch <= Q work on them unchanged. */
+#define HRAG_FUSE_SUM 0
+#define HRAG_FUSE_MAX 1
+#define HRAG_FUSE_RRF 2
+
+/* Sum / max alone, engine-free and IN PLACE: scores_dev fp32 [batch, ld] (n valid entries per row; the columns n .. ld
+ * are neither read nor written), member_ptr_dev int32 [n_fused + 1] and weight_dev fp32 [batch] (or NULL) DEVICE arrays
+ * that follow the rules above (they cannot be checked here; whatever they hold, nothing outside the rows is touched).
+ * mode: HRAG_FUSE_SUM / HRAG_FUSE_MAX.  Rows [0, n_fused) receive the fused rows.  Serves dense fusion over
+ * hrag_sim_scores output as well. */
+hrag_status hrag_fuse_rows(float *scores_dev, int32_t batch, int64_t n, int64_t ld, const int32_t *member_ptr_dev,
+                           int32_t n_fused, const float *weight_dev, int32_t mode, hrag_stream stream);
+
+/* The scatter of HRAG_FUSE_RRF alone, engine-free: list_idx_dev int32 [batch, depth] the ranked lists of the member rows
+ * (slot j = rank j + 1; -1 or an id outside [0, n): skipped; the ids of one row must be unique), device member_ptr /
+ * weight as above, c >= 0.  out_dev fp32 [n_fused, ld] is zeroed over its n columns and filled. */
+hrag_status hrag_rrf_rows(const int32_t *list_idx_dev, int32_t batch, int32_t depth, const int32_t *member_ptr_dev,
+                          int32_t n_fused, const float *weight_dev, int32_t c, float *out_dev, int64_t n, int64_t ld,
+                          hrag_stream stream);
+
+/* Bytes of workspace hrag_last_fused needs (16-byte aligned device memory, scratch only): the copies of member_ptr and
+ * weight; HRAG_FUSE_RRF adds the member lists [batch, depth] and, with one filter row per question
+ * (per_question_filter != 0), the per-member filter rows.  Negative on a bad argument. */
+int64_t hrag_fuse_workspace_bytes(int32_t batch, int64_t n_passages, int32_t mode, int32_t depth,
+                                  int32_t per_question_filter);
+
+/* The fusion over the score rows the handle's last retrieve, scored or grouped dense call left, then their ranking: a
+ * follow-up call like hrag_last_group_hits (same handle, stream and one-call-per-handle rules; a workspace handle has
+ * its own rows).  batch <= the recorded batch of the rows; member_ptr [n_fused + 1] and weight [batch] (or NULL) are
+ * HOST arrays, validated before anything is enqueued and copied into the workspace on `stream` (keep them valid until
+ * the stream has passed the call).  rrf_c / rrf_depth: HRAG_FUSE_RRF only.  filter_dev: NULL, one row for every question
+ * (filter_ld_words 0) or one row per QUESTION; it applies to the RRF member rankings and to the final ranking.
+ * Outputs, each set optional: doc_idx_out_dev / doc_score_out_dev [n_fused, k] the ungrouped ranking of the fused rows
+ * under the filter; group_agg >= 0 (HRAG_GROUP_MAX / HRAG_GROUP_SUM; negative: no grouping) the grouped ranking
+ * group_idx_out_dev / group_score_out_dev / best_doc_idx_out_dev [n_fused, k] as hrag_retrieve_grouped writes it.
+ * 1 <= k <= max_topk when an output is given.  Nothing is allocated, synchronised or read back.
+ * HRAG_EINVAL (nothing enqueued, outputs and rows untouched): a row-shard engine (its rows are slices of the passages),
+ * no rows written yet on this handle, batch above the recorded one, member_ptr / weight / mode / c / depth / k outside
+ * the rules above, weights with HRAG_FUSE_MAX, a workspace that is too small or misaligned. */
+hrag_status hrag_last_fused(hrag_engine *e, int32_t batch, const int32_t *member_ptr, int32_t n_fused,
+                            const float *weight, int32_t mode, int32_t rrf_c, int32_t rrf_depth, int32_t k,
+                            const uint32_t *filter_dev, int64_t filter_ld_words, int32_t group_agg,
+                            int32_t *doc_idx_out_dev, float *doc_score_out_dev, int32_t *group_idx_out_dev,
+                            float *group_score_out_dev, int32_t *best_doc_idx_out_dev, void *workspace_dev,
+                            size_t workspace_bytes, hrag_stream stream);
 
 /* ---- lower-level seams (used by the per-method adapters and by the parity tests) ---- */
 
