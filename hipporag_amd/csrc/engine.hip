@@ -81,26 +81,40 @@ hrag_status check_batch(const hrag_engine *e, int32_t batch) {
     return HRAG_OK;
 }
 
-// seeds + teleport are applied the same way at init (scale 1) and in every sweep (scale 1-alpha)
-hrag_status ppr_init(hrag_engine *e, const float *tele, int64_t tele_rows, const int32_t *r2t,
-                     const int32_t *sv, const float *sw, const int32_t *sc, int batch, float *x,
-                     SlabLayout lay, hipStream_t s) {
-    SpmmArgs a = e->spmm_args(nullptr, x, tele, tele_rows, r2t, 0.f);
-    HRAG_TRY(launch_ppr_init(a, lay, s));
-    if (sv)
-        HRAG_TRY(launch_seed_scatter(x, e->V, e->row_offset, e->n_rows, sv, sw, sc, kMaxSeeds, batch,
-                                     1.0f, lay, s));
+// the reset vector of the fp32 state: teleport rows (+ the row -> teleport-row map) and the seeds, either may be absent
+struct Reset32 {
+    const float *tele;
+    int64_t tele_rows;
+    const int32_t *r2t, *sv;
+    const float *sw;
+    const int32_t *sc;
+};
+
+// n steps of the fp32 state that ping-pongs between e->d_x and e->d_y: the final state ends in e->d_x (d_y: the step before)
+template <class Step>
+hrag_status ping_pong32(hrag_engine *e, int n, Step step) {
+    float *x = e->d_x, *y = e->d_y;
+    for (int it = 0; it < n; ++it, std::swap(x, y)) HRAG_TRY(step(it, x, y));
+    if (x != e->d_x) std::swap(e->d_x, e->d_y);
     return HRAG_OK;
 }
 
-hrag_status ppr_step(hrag_engine *e, const float *tele, int64_t tele_rows, const int32_t *r2t,
-                     const int32_t *sv, const float *sw, const int32_t *sc, int batch, float damping,
-                     const float *x, float *y, SlabLayout lay, bool main_only, hipStream_t s) {
-    SpmmArgs a = e->spmm_args(x, y, tele, tele_rows, r2t, damping);
+// seeds + teleport are applied the same way at init (scale 1) and in every sweep (scale 1-alpha)
+hrag_status ppr_init(hrag_engine *e, const Reset32 &v, int batch, float *x, SlabLayout lay, hipStream_t s) {
+    SpmmArgs a = e->spmm_args(nullptr, x, v.tele, v.tele_rows, v.r2t, 0.f);
+    HRAG_TRY(launch_ppr_init(a, lay, s));
+    if (v.sv)
+        HRAG_TRY(launch_seed_scatter(x, e->V, e->row_offset, e->n_rows, v.sv, v.sw, v.sc, kMaxSeeds, batch, 1.0f, lay, s));
+    return HRAG_OK;
+}
+
+hrag_status ppr_step(hrag_engine *e, const Reset32 &v, int batch, float damping, const float *x, float *y, SlabLayout lay,
+                     bool main_only, hipStream_t s) {
+    SpmmArgs a = e->spmm_args(x, y, v.tele, v.tele_rows, v.r2t, damping);
     HRAG_TRY(launch_ppr_spmm(a, lay, main_only, s));
-    if (sv && !main_only)
-        HRAG_TRY(launch_seed_scatter(y, e->V, e->row_offset, e->n_rows, sv, sw, sc, kMaxSeeds, batch,
-                                     1.0f - damping, lay, s));
+    if (v.sv && !main_only)
+        HRAG_TRY(launch_seed_scatter(y, e->V, e->row_offset, e->n_rows, v.sv, v.sw, v.sc, kMaxSeeds, batch, 1.0f - damping,
+                                     lay, s));
     return HRAG_OK;
 }
 
@@ -276,14 +290,13 @@ hrag_status build_sell8(const hrag_engine *e, const std::vector<int32_t> &row_pt
     return HRAG_OK;   // the arrival counters (lcount) are per workspace: alloc_workspace
 }
 
-Ppr16Args ppr16_args(const hrag_engine *e, const uint16_t *x, uint16_t *y, const uint16_t *aux,
-                     float damping) {
+Ppr16Args ppr16_args(const hrag_engine *e, const uint16_t *x, uint16_t *y, const uint16_t *aux, float damping,
+                     const Sell8Store *fin = nullptr) {   // fin: the final sweep's matrix (the passage rows: e->fsell)
+    const Sell8Store &m = fin ? *fin : e->sell;
     Ppr16Args a;
-    a.pairs = e->sell.pairs; a.pairs_bytes = e->sell.pairs_bytes();
-    a.chunk_meta = e->sell.chunk_meta; a.vrow = e->sell.vrow; a.n_chunks = e->sell.n_chunks;
-    a.lrow_row = e->sell.lrow_row; a.lrow_first = e->sell.lrow_first; a.lrow_cnt = e->sell.lrow_cnt;
-    a.n_lrow = e->sell.n_lrow; a.n_partial = e->sell.n_partial; a.partial = e->d_partial16;
-    a.seg_lrow = e->sell.seg_lrow; a.lcount = e->sell.lcount;
+    a.pairs = m.pairs; a.pairs_bytes = m.pairs_bytes(); a.chunk_meta = m.chunk_meta; a.vrow = m.vrow;
+    a.n_chunks = m.n_chunks; a.lrow_row = m.lrow_row; a.lrow_first = m.lrow_first; a.lrow_cnt = m.lrow_cnt;
+    a.n_lrow = m.n_lrow; a.n_partial = m.n_partial; a.seg_lrow = m.seg_lrow; a.lcount = m.lcount; a.partial = e->d_partial16;
     a.num_vertices = e->V; a.x = x; a.y = y; a.aux = aux; a.row_slot = e->d_row_slot;
     a.tele = e->d_tele16; a.tele_rows = e->tele16_rows;
     a.alpha = damping; a.beta = 1.0f - damping; a.cscale = kPpr16CScale;
@@ -365,10 +378,6 @@ static bool accel_plan16(int iters, float damping, int *k1_out, int *k2_out) {
     return true;
 }
 
-// h_0 = f16(v); K1 sweeps on h (the first one gathers only the columns where h_0 is non-zero: d_colmask); the
-// residual sweep; K2 sweeps on the correction, the last of them over the passage rows only (fsell), writing
-// x = h + c / cs in fp32 at the passages (d_xp8, passage order) -- nothing else is read afterwards
-// (HippoRAG.py:1745).  Buffers: d_h16[0], [1] ping-pong for h; [2] = r; the free h buffer and [3] ping-pong for c.
 // Extension stages the contract may add on the two-stage fp16 states (round 4): stage j + 1 of 1, 2, 3, 3 sweeps (the
 // schedule of the fp8 state, p8_ext_sweeps) = that many plain correction sweeps over ALL rows -- the first one redoes,
 // on every row, the sweep the previous final sweep did on the passage rows -- followed by a final sweep over the passage
@@ -380,64 +389,98 @@ static int ext_stages_for(int sweeps, int max_iters, float tol) {
     return e_max;
 }
 
-// *sweeps_out: the sweeps of the base plan (HRAG_OPT_ACCEL: fewer than `iters`, which then names the accuracy);
-// tol > 0 with est: up to *e_max_out extension stages follow, decided on the device (no host synchronisation)
-hrag_status ppr16_run(hrag_engine *e, int batch, float damping, int iters, hipStream_t s, int32_t *est = nullptr,
-                      int *sweeps_out = nullptr, bool allow_accel = false, float tol = 0.f, int max_iters = 0,
-                      int *e_max_out = nullptr) {
-    const int ns = n_slabs64(batch);
-    const int nt = (e->opt_flags & HRAG_OPT_TEMPORAL16) ? 0 : 3;
+// A two-stage run.  est: the final sweeps measure; with tol > 0 up to e_max extension stages follow, decided on the device (no
+// host synchronisation).  sweeps: those of the base plan (HRAG_OPT_ACCEL: fewer than `iters`, which then names the accuracy)
+struct TwoStagePlan {
+    int batch = 0, iters = 0, max_iters = 0;
+    float damping = 0.f, tol = 0.f;
+    int32_t *est = nullptr;
+    bool allow_accel = false;
+    int sweeps = 0, e_max = 0;   // out
+};
+
+// THE two-stage plan (the comments above): split16 / accel_plan16, K1 sweeps on h, the residual sweep, K2 - 1 sweeps on
+// the correction, the final sweep, then the contract's decide + gated extension stages.  `st` defines the five steps over
+// one state type (Steps16, StepsSv below); buf = h ping / pong, r, c.  Returns where h ended up in *h_out.
+template <class Steps>
+hrag_status two_stage_run(hrag_engine *e, const Steps &st, uint16_t *const buf[4], TwoStagePlan &p, uint16_t **h_out) {
+    const float damping = p.damping;
     int k1, k2, kc = 0;                                // kc: Chebyshev steps among the k2 correction sweeps
-    split16(iters, &k1, &k2);
-    const bool accel = allow_accel && (e->opt_flags & HRAG_OPT_ACCEL) && accel_plan16(iters, damping, &k1, &kc);
+    split16(p.iters, &k1, &k2);
+    const bool accel = p.allow_accel && (e->opt_flags & HRAG_OPT_ACCEL) && accel_plan16(p.iters, damping, &k1, &kc);
     if (accel) k2 = kc + 2;                            // + one plain correction sweep + the final sweep
-    const int sweeps = k1 + 1 + k2;
-    if (sweeps_out) *sweeps_out = sweeps;
-    uint16_t *h = e->d_h16[0], *hn = e->d_h16[1], *r = e->d_h16[2];
-    HRAG_TRY(launch_ppr16_init(ppr16_args(e, nullptr, h, nullptr, damping), ns, s));
-    for (int it = 0; it < k1; ++it) {
-        Ppr16Args a = ppr16_args(e, h, hn, nullptr, damping);
-        if (it == 0) { a.colmask = e->d_colmask; a.colmask_bytes = (uint32_t)(e->colmask_words * 4); }
-        if (accel && it > 0) { a.omega = (float)accel_omega(it + 1, damping); a.prev = hn; }   // h_{it+1} over h_{it-1}
-        HRAG_TRY(launch_ppr16_sweep(a, kPprModeH, ns, nt, false, s));
+    p.sweeps = k1 + 1 + k2;
+    uint16_t *h = buf[0], *hn = buf[1], *r = buf[2];
+    HRAG_TRY(st.init(h));
+    for (int it = 0; it < k1; ++it) {                  // accelerated: h_{it+1} over h_{it-1}
+        const bool cheb = accel && it > 0;
+        HRAG_TRY(st.sweep_h(h, hn, it == 0, cheb ? (float)accel_omega(it + 1, damping) : 1.f, cheb ? hn : nullptr));
         std::swap(h, hn);
     }
-    HRAG_TRY(launch_ppr16_sweep(ppr16_args(e, h, r, nullptr, damping), kPprModeR, ns, nt, false, s));
+    HRAG_TRY(st.sweep_r(h, r));
     const uint16_t *c = r;            // c_{K1+1} = r
-    uint16_t *cn = hn, *cn2 = e->d_h16[3];
-    // a correction sweep over all rows (c -> cn) / the final sweep over the passage rows from c (x = h + c' / cs, measured)
+    uint16_t *cn = hn, *cn2 = buf[3];
+    // a correction sweep over all rows (c -> cn); the final sweep over the passage rows from c (x = h + c' / cs, measured)
     auto sweep_c = [&](float omega, const uint16_t *prev, const int32_t *gate) {
-        Ppr16Args a = ppr16_args(e, c, cn, r, damping);
-        a.omega = omega; a.prev = prev; a.gate = gate; a.gate_want = 1;
-        const hrag_status st = launch_ppr16_sweep(a, kPprModeC, ns, nt, false, s);
+        const hrag_status rc = st.sweep_c(c, cn, r, h, omega, prev, gate);
         c = cn;
         std::swap(cn, cn2);
-        return st;
-    };
-    auto sweep_f = [&](const int32_t *gate) {
-        Ppr16Args a = ppr16_args(e, c, cn, r, damping);
-        const Sell8Store &m = e->fsell;
-        a.pairs = m.pairs; a.pairs_bytes = m.pairs_bytes(); a.chunk_meta = m.chunk_meta; a.vrow = m.vrow;
-        a.n_chunks = m.n_chunks; a.lrow_row = m.lrow_row; a.lrow_first = m.lrow_first; a.lrow_cnt = m.lrow_cnt;
-        a.n_lrow = m.n_lrow; a.n_partial = m.n_partial; a.seg_lrow = m.seg_lrow; a.lcount = m.lcount;
-        a.hfin = h; a.out = e->d_xp8; a.p_rows = e->p_rows;
-        a.est = est; a.est_ws = e->d_est_ws; a.batch = batch;
-        a.gate = gate; a.gate_want = 1;
-        return launch_ppr16_sweep(a, kPprModeF, ns, nt, false, s);
+        return rc;
     };
     for (int it = 0; it + 1 < k2; ++it) {
         // accelerated: step it + 2 of stage 2 -- c_0 = 0 (no history), c_1 = r, then the ping-pong buffers
         const bool cheb = accel && it < kc;
         HRAG_TRY(sweep_c(cheb ? (float)accel_omega(it + 2, damping) : 1.f, !cheb || it == 0 ? nullptr : it == 1 ? r : cn, nullptr));
     }
-    HRAG_TRY(sweep_f(nullptr));
-    const int e_max = est ? ext_stages_for(sweeps, max_iters, tol) : 0;
-    if (e_max_out) *e_max_out = e_max;
-    for (int j = 0; j < e_max; ++j) {
-        HRAG_TRY(launch_ppr8_decide(est, e->d_flags, batch, damping / (1.0f - damping), tol, j, e_max, e->d_ctl, s));
+    HRAG_TRY(st.sweep_f(c, cn, r, h, nullptr));
+    p.e_max = p.est ? ext_stages_for(p.sweeps, p.max_iters, p.tol) : 0;
+    for (int j = 0; j < p.e_max; ++j) {
+        HRAG_TRY(launch_ppr8_decide(p.est, e->d_flags, p.batch, damping / (1.0f - damping), p.tol, j, p.e_max, e->d_ctl, st.s));
         for (int i = p8_ext_sweeps(j); i < p8_ext_sweeps(j + 1); ++i) HRAG_TRY(sweep_c(1.f, nullptr, e->d_ctl + j));
-        HRAG_TRY(sweep_f(e->d_ctl + j));
+        HRAG_TRY(st.sweep_f(c, cn, r, h, e->d_ctl + j));
     }
+    *h_out = h;
+    return HRAG_OK;
+}
+
+// the steps of the plan on the 64-query fp16 state (ppr16.hip)
+struct Steps16 {
+    hrag_engine *e;
+    const TwoStagePlan &p;
+    hipStream_t s;
+    int ns() const { return n_slabs64(p.batch); }
+    int nt() const { return (e->opt_flags & HRAG_OPT_TEMPORAL16) ? 0 : 3; }
+    hrag_status init(uint16_t *h) const { return launch_ppr16_init(ppr16_args(e, nullptr, h, nullptr, p.damping), ns(), s); }
+    hrag_status sweep_h(const uint16_t *h, uint16_t *hn, bool first, float omega, const uint16_t *prev) const {
+        Ppr16Args a = ppr16_args(e, h, hn, nullptr, p.damping);
+        if (first) { a.colmask = e->d_colmask; a.colmask_bytes = (uint32_t)(e->colmask_words * 4); }
+        a.omega = omega; a.prev = prev;
+        return launch_ppr16_sweep(a, kPprModeH, ns(), nt(), false, s);
+    }
+    hrag_status sweep_r(const uint16_t *h, uint16_t *r) const {
+        return launch_ppr16_sweep(ppr16_args(e, h, r, nullptr, p.damping), kPprModeR, ns(), nt(), false, s);
+    }
+    hrag_status sweep_c(const uint16_t *c, uint16_t *cn, const uint16_t *r, const uint16_t *, float omega,
+                        const uint16_t *prev, const int32_t *gate) const {
+        Ppr16Args a = ppr16_args(e, c, cn, r, p.damping);
+        a.omega = omega; a.prev = prev; a.gate = gate; a.gate_want = 1;
+        return launch_ppr16_sweep(a, kPprModeC, ns(), nt(), false, s);
+    }
+    hrag_status sweep_f(const uint16_t *c, uint16_t *cn, const uint16_t *r, const uint16_t *h, const int32_t *gate) const {
+        Ppr16Args a = ppr16_args(e, c, cn, r, p.damping, &e->fsell);
+        a.hfin = h; a.out = e->d_xp8; a.p_rows = e->p_rows;
+        a.est = p.est; a.est_ws = e->d_est_ws; a.batch = p.batch; a.gate = gate; a.gate_want = 1;
+        return launch_ppr16_sweep(a, kPprModeF, ns(), nt(), false, s);
+    }
+};
+
+// h_0 = f16(v); K1 sweeps on h (the first one gathers only the columns where h_0 is non-zero: d_colmask); the
+// residual sweep; K2 sweeps on the correction, the last of them over the passage rows only (fsell), writing
+// x = h + c / cs in fp32 at the passages (d_xp8, passage order) -- nothing else is read afterwards
+// (HippoRAG.py:1745).  Buffers: d_h16[0], [1] ping-pong for h; [2] = r; the free h buffer and [3] ping-pong for c.
+hrag_status ppr16_run(hrag_engine *e, TwoStagePlan &p, hipStream_t s) {
+    uint16_t *h;
+    HRAG_TRY(two_stage_run(e, Steps16{e, p, s}, e->d_h16, p, &h));
     if (h != e->d_h16[0]) std::swap(e->d_h16[0], e->d_h16[1]);  // keep h in [0] for hrag_ppr_sweeps
     return HRAG_OK;
 }
@@ -472,94 +515,71 @@ inline bool use_sv_half(const hrag_engine *e, int iters, float damping) {
 // hrag_ppr (all rows wanted): x_0 = v, `iters` plain sweeps; the final state ends in e->d_x ([V][bp] fp32)
 hrag_status ppr_sv_run_full(hrag_engine *e, const int32_t *row_slot, const float *tele, int bp, float damping,
                             int iters, hipStream_t s) {
-    float *x = e->d_x, *y = e->d_y;
-    HRAG_TRY(launch_ppr_sv_init(ppr_sv_args(e, e->sell, nullptr, x, row_slot, tele, damping), bp, s));
-    for (int it = 0; it < iters; ++it) {
-        HRAG_TRY(launch_ppr_sv_sweep(ppr_sv_args(e, e->sell, x, y, row_slot, tele, damping), bp, false, s));
-        std::swap(x, y);
-    }
-    if (x != e->d_x) std::swap(e->d_x, e->d_y);
-    return HRAG_OK;
+    HRAG_TRY(launch_ppr_sv_init(ppr_sv_args(e, e->sell, nullptr, e->d_x, row_slot, tele, damping), bp, s));
+    return ping_pong32(e, iters, [&](int, float *x, float *y) {
+        return launch_ppr_sv_sweep(ppr_sv_args(e, e->sell, x, y, row_slot, tele, damping), bp, false, s);
+    });
 }
+
+// the steps of the plan on the small-batch fp16 state (ppr_sv.hip): [V][8] buffers, x = h + c / cs lands in e->d_x
+struct StepsSv {
+    hrag_engine *e;
+    const TwoStagePlan &p;
+    const int32_t *row_slot;
+    const float *tele;
+    int bp;
+    hipStream_t s;
+    PprSvArgs args(const Sell8Store &m, const void *x, void *y, int mode) const {
+        PprSvArgs a = ppr_sv_args(e, m, x, y, row_slot, tele, p.damping);
+        a.half_state = 1; a.mode = mode; a.cscale = kPpr16CScale;
+        return a;
+    }
+    PprSvArgs args_c(const Sell8Store &m, const uint16_t *c, uint16_t *cn, const uint16_t *r, const uint16_t *h, int mode) const {
+        PprSvArgs a = args(m, c, cn, mode);
+        a.aux16 = r; a.h16 = h; a.xout = e->d_x; a.gate_want = 1;
+        return a;
+    }
+    hrag_status init(uint16_t *h) const { return launch_ppr_sv_init(args(e->sell, nullptr, h, 0), bp, s); }
+    hrag_status sweep_h(const uint16_t *h, uint16_t *hn, bool first, float omega, const uint16_t *prev) const {
+        PprSvArgs a = args(e->sell, h, hn, 0);
+        a.colmask = first ? e->d_colmask : nullptr;
+        a.omega = omega; a.prev = prev;
+        return launch_ppr_sv_sweep(a, bp, false, s);
+    }
+    hrag_status sweep_r(const uint16_t *h, uint16_t *r) const {
+        return launch_ppr_sv_sweep(args(e->sell, h, r, 1), bp, false, s);
+    }
+    hrag_status sweep_c(const uint16_t *c, uint16_t *cn, const uint16_t *r, const uint16_t *h, float omega,
+                        const uint16_t *prev, const int32_t *gate) const {
+        PprSvArgs a = args_c(e->sell, c, cn, r, h, 2);
+        a.omega = omega; a.prev = prev; a.gate = gate;
+        return launch_ppr_sv_sweep(a, bp, false, s);
+    }
+    hrag_status sweep_f(const uint16_t *c, uint16_t *cn, const uint16_t *r, const uint16_t *h, const int32_t *gate) const {
+        PprSvArgs a = args_c(e->fsell, c, cn, r, h, 3);
+        a.est = p.est; a.est_ws = e->d_est_ws; a.batch = p.batch; a.gate = gate;
+        return launch_ppr_sv_sweep(a, bp, false, s);
+    }
+};
 
 // hrag_retrieve, batch <= 8 (ppr_sv.hip header): x_0 = v; the first sweep gathers only the passage / seed columns
 // (d_colmask), the last one runs over the passage rows only and leaves x (fp32 [V][bp], passage rows valid) in
 // e->d_x; with >= 16 sweeps the state in between is the two-stage fp16 one (v must carry the per-query scale).
-hrag_status ppr_sv_run(hrag_engine *e, const int32_t *row_slot, const float *tele, int bp, float damping,
-                       int iters, hipStream_t s, int32_t *est = nullptr, int batch = 0, int *sweeps_out = nullptr,
-                       bool allow_accel = false, float tol = 0.f, int max_iters = 0, int *e_max_out = nullptr) {
-    if (sweeps_out) *sweeps_out = iters;
-    if (e_max_out) *e_max_out = 0;
-    if (iters < 1) return ppr_sv_run_full(e, row_slot, tele, bp, damping, iters, s);
-    if (!use_sv_half(e, iters, damping)) {
-        float *x = e->d_x, *y = e->d_y;
-        HRAG_TRY(launch_ppr_sv_init(ppr_sv_args(e, e->sell, nullptr, x, row_slot, tele, damping), bp, s));
-        for (int it = 0; it < iters; ++it) {
-            PprSvArgs a = ppr_sv_args(e, it + 1 == iters ? e->fsell : e->sell, x, y, row_slot, tele, damping);
-            a.colmask = it == 0 ? e->d_colmask : nullptr;
-            if (it + 1 == iters) { a.est = est; a.est_ws = e->d_est_ws; a.batch = batch; }
-            HRAG_TRY(launch_ppr_sv_sweep(a, bp, false, s));
-            std::swap(x, y);
-        }
-        if (x != e->d_x) std::swap(e->d_x, e->d_y);
-        return HRAG_OK;
+hrag_status ppr_sv_run(hrag_engine *e, const int32_t *row_slot, const float *tele, int bp, TwoStagePlan &p, hipStream_t s) {
+    p.sweeps = p.iters;
+    p.e_max = 0;
+    if (p.iters < 1) return ppr_sv_run_full(e, row_slot, tele, bp, p.damping, p.iters, s);
+    if (use_sv_half(e, p.iters, p.damping)) {
+        uint16_t *h;
+        return two_stage_run(e, StepsSv{e, p, row_slot, tele, bp, s}, e->d_sv16, p, &h);
     }
-    int k1, k2, kc = 0;                                // the plan of ppr16_run, Chebyshev steps included (accel_plan16)
-    split16(iters, &k1, &k2);
-    const bool accel = allow_accel && (e->opt_flags & HRAG_OPT_ACCEL) && accel_plan16(iters, damping, &k1, &kc);
-    if (accel) k2 = kc + 2;
-    const int sweeps = k1 + 1 + k2;
-    if (sweeps_out) *sweeps_out = sweeps;
-    uint16_t *h = e->d_sv16[0], *hn = e->d_sv16[1], *r = e->d_sv16[2];
-    {
-        PprSvArgs a = ppr_sv_args(e, e->sell, nullptr, h, row_slot, tele, damping);
-        a.half_state = 1;
-        HRAG_TRY(launch_ppr_sv_init(a, bp, s));
-    }
-    for (int it = 0; it < k1; ++it) {
-        PprSvArgs a = ppr_sv_args(e, e->sell, h, hn, row_slot, tele, damping);
-        a.half_state = 1; a.mode = 0; a.colmask = it == 0 ? e->d_colmask : nullptr;
-        if (accel && it > 0) { a.omega = (float)accel_omega(it + 1, damping); a.prev = hn; }
-        HRAG_TRY(launch_ppr_sv_sweep(a, bp, false, s));
-        std::swap(h, hn);
-    }
-    {
-        PprSvArgs a = ppr_sv_args(e, e->sell, h, r, row_slot, tele, damping);
-        a.half_state = 1; a.mode = 1; a.cscale = kPpr16CScale;
-        HRAG_TRY(launch_ppr_sv_sweep(a, bp, false, s));
-    }
-    const uint16_t *c = r;                 // c_{K1+1} = r
-    uint16_t *cn = hn, *cn2 = e->d_sv16[3];
-    // a correction sweep over all rows (c -> cn) / the final sweep over the passage rows from c (see ppr16_run)
-    auto sweep_c = [&](float omega, const uint16_t *prev, const int32_t *gate) {
-        PprSvArgs a = ppr_sv_args(e, e->sell, c, cn, row_slot, tele, damping);
-        a.half_state = 1; a.mode = 2; a.aux16 = r; a.cscale = kPpr16CScale; a.h16 = h; a.xout = e->d_x;
-        a.omega = omega; a.prev = prev; a.gate = gate; a.gate_want = 1;
-        const hrag_status st = launch_ppr_sv_sweep(a, bp, false, s);
-        c = cn;
-        std::swap(cn, cn2);
-        return st;
-    };
-    auto sweep_f = [&](const int32_t *gate) {
-        PprSvArgs a = ppr_sv_args(e, e->fsell, c, cn, row_slot, tele, damping);
-        a.half_state = 1; a.mode = 3; a.aux16 = r; a.cscale = kPpr16CScale; a.h16 = h; a.xout = e->d_x;
-        a.est = est; a.est_ws = e->d_est_ws; a.batch = batch;
-        a.gate = gate; a.gate_want = 1;
+    HRAG_TRY(launch_ppr_sv_init(ppr_sv_args(e, e->sell, nullptr, e->d_x, row_slot, tele, p.damping), bp, s));
+    return ping_pong32(e, p.iters, [&](int it, float *x, float *y) {
+        PprSvArgs a = ppr_sv_args(e, it + 1 == p.iters ? e->fsell : e->sell, x, y, row_slot, tele, p.damping);
+        a.colmask = it == 0 ? e->d_colmask : nullptr;
+        if (it + 1 == p.iters) { a.est = p.est; a.est_ws = e->d_est_ws; a.batch = p.batch; }
         return launch_ppr_sv_sweep(a, bp, false, s);
-    };
-    for (int j = 0; j + 1 < k2; ++j) {
-        const bool cheb = accel && j < kc;
-        HRAG_TRY(sweep_c(cheb ? (float)accel_omega(j + 2, damping) : 1.f, !cheb || j == 0 ? nullptr : j == 1 ? r : cn, nullptr));
-    }
-    HRAG_TRY(sweep_f(nullptr));
-    const int e_max = est ? ext_stages_for(sweeps, max_iters, tol) : 0;
-    if (e_max_out) *e_max_out = e_max;
-    for (int j = 0; j < e_max; ++j) {   // extension stages of the contract, decided on the device (ppr16_run)
-        HRAG_TRY(launch_ppr8_decide(est, e->d_flags, batch, damping / (1.0f - damping), tol, j, e_max, e->d_ctl, s));
-        for (int i = p8_ext_sweeps(j); i < p8_ext_sweeps(j + 1); ++i) HRAG_TRY(sweep_c(1.f, nullptr, e->d_ctl + j));
-        HRAG_TRY(sweep_f(e->d_ctl + j));
-    }
-    return HRAG_OK;
+    });
 }
 
 }  // namespace
@@ -567,14 +587,6 @@ hrag_status ppr_sv_run(hrag_engine *e, const int32_t *row_slot, const float *tel
 // The per-call half of an engine handle, sized once for max_batch: scores, PPR states of every width, seeds, flags,
 // counters.  hrag_engine_create builds it after the index; hrag_workspace_create builds ONLY this for a handle that
 // borrows the index of another engine.  Needs e->want_sell / want_f16 / has_facts / f8_ready and the SELL-8 metadata.
-// what a grouped call adds to its ungrouped form (include/hrag.h, grouped retrieval)
-struct GroupOut {
-    int32_t agg;
-    int32_t *group_idx;
-    float *group_score;
-    int32_t *best_doc;
-};
-
 // argument checks of a grouped call, before anything is enqueued
 static hrag_status check_grouped(const hrag_engine *e, const GroupOut *g) {
     if (!e->d_grp_ptr || !e->d_gscore) {
@@ -1346,8 +1358,7 @@ hrag_status hrag_stage_ppr_init(hrag_engine *e, const float *tele, const int32_t
                                 const int32_t *sc, int32_t batch, float *x, hrag_stream stream) {
     HRAG_TRY(check_batch(e, batch));
     HRAG_REQUIRE(tele && x, "NULL argument");
-    return ppr_init(e, tele, e->n_passages, e->d_row_to_tele, sv, sw, sc, batch, x, e->layout(batch),
-                    (hipStream_t)stream);
+    return ppr_init(e, {tele, e->n_passages, e->d_row_to_tele, sv, sw, sc}, batch, x, e->layout(batch), (hipStream_t)stream);
 }
 
 hrag_status hrag_stage_ppr_step(hrag_engine *e, const float *tele, const int32_t *sv, const float *sw,
@@ -1355,8 +1366,8 @@ hrag_status hrag_stage_ppr_step(hrag_engine *e, const float *tele, const int32_t
                                 float *y, hrag_stream stream) {
     HRAG_TRY(check_batch(e, batch));
     HRAG_REQUIRE(tele && x && y && x != y, "bad argument");
-    return ppr_step(e, tele, e->n_passages, e->d_row_to_tele, sv, sw, sc, batch, damping, x, y,
-                    e->layout(batch), false, (hipStream_t)stream);
+    return ppr_step(e, {tele, e->n_passages, e->d_row_to_tele, sv, sw, sc}, batch, damping, x, y, e->layout(batch), false,
+                    (hipStream_t)stream);
 }
 
 int64_t hrag_colsum_workspace_bytes(hrag_engine *e, int32_t batch) {
@@ -1386,250 +1397,300 @@ hrag_status hrag_stage_doc_scores(hrag_engine *e, const float *x, const double *
     return HRAG_OK;
 }
 
-// hrag_retrieve / hrag_retrieve_scored: the passage scores come from this engine's embeddings (q_pass) or from the
-// caller (pass_scores fp32 [batch, pass_ld] raw cosine scores in passage order)
-static hrag_status retrieve_impl(hrag_engine *e, const uint16_t *q_pass, const float *pass_scores, int64_t pass_ld,
-                                 int32_t batch, const int32_t *kept_idx, const float *kept_score,
-                                 const int32_t *kept_count, int32_t kf, int32_t link_top_k, float damping,
-                                 float passage_node_weight, int32_t ppr_iters, int32_t ppr_max_iters, float ppr_tol,
-                                 int32_t k, int32_t *doc_idx_out, float *doc_score_out, int32_t *flags_out,
-                                 float *residual_out, int32_t *iters_out, hrag_stream stream,
-                                 const uint32_t *filter, int64_t filter_ld_words, bool scoped = false,
-                                 const GroupOut *grp = nullptr) {
-    HRAG_TRY(check_batch(e, batch));
-    TopkMask fm;
-    const TopkMask *mask = nullptr;
-    HRAG_TRY(doc_filter(e, filter, filter_ld_words, fm, &mask));
-    HRAG_REQUIRE(!scoped || mask, "NULL filter (the scoped call needs the allowed passages)");
-    if (grp) HRAG_TRY(check_grouped(e, grp));
-    HRAG_REQUIRE(ppr_tol >= 0.f && ppr_tol == ppr_tol, "ppr_tol must be >= 0");
-    HRAG_REQUIRE(ppr_tol == 0.f || ppr_tol >= HRAG_PPR_TOL_MIN,
-                 "ppr_tol=%g is below HRAG_PPR_TOL_MIN=%g: fp32 arithmetic leaves an error floor of %g however small the "
-                 "measured residual reads (include/hrag.h: error <= max(%g * residual, floor))", (double)ppr_tol,
-                 (double)HRAG_PPR_TOL_MIN, (double)HRAG_PPR_ERR_FLOOR_F32, (double)HRAG_PPR_ERR_K);
-    HRAG_REQUIRE(ppr_tol == 0.f || ppr_max_iters >= ppr_iters, "ppr_max_iters=%d < ppr_iters=%d", ppr_max_iters, ppr_iters);
-    HRAG_REQUIRE((q_pass || pass_scores) && kept_idx && kept_score && kept_count, "NULL argument");
-    // a grouped call may leave the ungrouped ranking out (both pointers NULL)
-    HRAG_REQUIRE(grp ? (doc_idx_out != nullptr) == (doc_score_out != nullptr) : doc_idx_out && doc_score_out, "NULL argument");
-    HRAG_REQUIRE(e->n_rows == e->V && e->p_rows == e->n_passages,
-                 "hrag_retrieve needs an unsharded engine; sharded engines use the hrag_stage_* operators");
-    HRAG_REQUIRE(pass_scores || e->d_pemb, "the engine was created without passage embeddings: use hrag_retrieve_scored");
-    HRAG_REQUIRE(!pass_scores || pass_ld >= e->n_passages, "pass_ld=%lld < n_passages", (long long)pass_ld);
-    HRAG_REQUIRE(k >= 1 && k <= e->max_topk, "k=%d outside [1, max_topk=%d]", k, e->max_topk);
-    HRAG_REQUIRE(ppr_iters >= 0, "ppr_iters must be >= 0");
-    HRAG_REQUIRE(damping >= 0.f && damping < 1.f, "damping %g outside [0, 1)", (double)damping);
-    HRAG_REQUIRE(e->n_passages >= 1, "engine has no passages");
-    hipStream_t s = (hipStream_t)stream;
-    HRAG_ENGINE_CALL(e, stream);
-    e->rows_batch = 0;   // the score rows are being rewritten (hrag_last_group_hits); set again when all is enqueued
-    const bool sv = use_sv(e, batch);
-    const bool f8 = !sv && batch > 64 && e->d_pool8[0] && ppr8_usable(e, batch, ppr_iters, damping);
-    const int f8_iters = ppr_iters;
-    const bool f16 = !sv && !f8 && use_f16(e, batch, ppr_iters, damping);
-    const int bp = sv_width(batch);
-    SlabLayout lay = e->layout(batch);
-    if (f16 || f8) { lay.bc = 64; lay.n_slabs = n_slabs64(batch); }
-    if (sv) { lay.bc = bp; lay.n_slabs = 1; }
-    const bool prof = e->profiling;
-
-    // convergence contract on the fp16 / small-batch / fp32 states: the fixed count runs, the last sweep measures the
-    // relative update of the passage scores (residual_out, flags bit 4); the fp8 and the fp16 states extend on the
-    // device (gate words, ext_max below), the fp32 state reports and leaves the repeat to the caller
-    int sweeps_run = ppr_iters;   // fp16 states under HRAG_OPT_ACCEL: fewer (ppr_iters then names the accuracy)
-    int ext_max = 0;              // fp16 states: extension stages enqueued (the device decides which of them run)
-    const bool want_est = residual_out != nullptr || ppr_tol > 0.f;
-    int32_t *est = (want_est && !f8 && ppr_iters >= 1) ? e->d_est_f : nullptr;
-    {
-        BlitList z;   // the call's small fills in one launch (common.h)
-        z.zero(e->d_flags, (int64_t)batch * sizeof(int32_t));
-        z.zero(est, (int64_t)batch * sizeof(int32_t));
-        if (!f8) z.zero(e->d_ctl, (int64_t)(kP8MaxExt + 1) * sizeof(int32_t));   // read by the finalize step below
-        HRAG_TRY(launch_blits(z, s));
+// ---- hrag_retrieve & co.: retrieve_impl validates the call and picks the PPR state; retrieve_front is what every state
+//      shares ahead of it, retrieve_f8 / _f16 / _sv / _f32 are one state each (teleport build, p.mark(EV_SEED), sweeps,
+//      p.mark(EV_PPR), doc scores), retrieve_back is what they share behind it
+// what the path choice fixes for one call.  Convergence contract on the fp16 / small-batch / fp32 states: the fixed count
+// runs, the last sweep measures the relative update of the passage scores (plan.est -> residual, flags bit 4); the fp8 and
+// the fp16 states extend on the device (gate words, plan.e_max), the fp32 state reports and leaves the repeat to the caller
+struct RetrievePath {
+    int32_t state = HRAG_PPR_STATE_F32;   // HRAG_PPR_STATE_*
+    SlabLayout lay;
+    int bp = 0;                           // small-batch width
+    TwoStagePlan plan;                    // est: nullptr on the fp8 state (its session measures); sweeps / e_max as run
+    hipStream_t s = nullptr;
+    const hipEvent_t *ev = nullptr;       // the profiling events, nullptr when profiling is off
+    bool f8() const { return state == HRAG_PPR_STATE_FP8; }
+    hrag_status mark(EvId id) const {     // the profiling marker: records ev[id] where the call stands on its stream
+        if (ev) HRAG_HIP_TRY(hipEventRecord(ev[id], s));
+        return HRAG_OK;
     }
-    if (prof) HRAG_HIP_TRY(hipEventRecord(e->ev[EV_START], s));
-    // dense_passage_retrieval: raw scores + min / max (HippoRAG.py:1496-1498)
-    if (pass_scores) {
-        HRAG_HIP_TRY(hipMemcpy2DAsync(e->d_spass, (size_t)e->ld_p * sizeof(float), pass_scores,
-                                      (size_t)pass_ld * sizeof(float), (size_t)e->n_passages * sizeof(float),
-                                      (size_t)batch, hipMemcpyDeviceToDevice, s));
+};
+
+// the small fills, the raw passage scores + min / max (HippoRAG.py:1496-1498), the entity seeds (HippoRAG.py:1574-1638)
+static hrag_status retrieve_front(hrag_engine *e, const RetrieveCall &c, const TopkMask *mask, const RetrievePath &p) {
+    const int32_t batch = c.batch;
+    BlitList z;   // the call's small fills in one launch (common.h)
+    z.zero(e->d_flags, (int64_t)batch * sizeof(int32_t));
+    z.zero(p.plan.est, (int64_t)batch * sizeof(int32_t));
+    if (!p.f8()) z.zero(e->d_ctl, (int64_t)(kP8MaxExt + 1) * sizeof(int32_t));   // read by the finalize step of the back
+    HRAG_TRY(launch_blits(z, p.s));
+    HRAG_TRY(p.mark(EV_START));
+    if (c.pass_scores) {
+        HRAG_HIP_TRY(hipMemcpy2DAsync(e->d_spass, (size_t)e->ld_p * sizeof(float), c.pass_scores,
+                                      (size_t)c.pass_ld * sizeof(float), (size_t)e->n_passages * sizeof(float),
+                                      (size_t)batch, hipMemcpyDeviceToDevice, p.s));
     } else {
-        HRAG_TRY(prep_query(e, q_pass, batch, s, &q_pass));
-        HRAG_TRY(launch_sim_gemm(e->d_pemb, e->p_rows, e->kdim, q_pass, batch, e->d_spass, e->ld_p, s, 0, e->emb_dtype));
+        const uint16_t *q = c.q_pass;
+        HRAG_TRY(prep_query(e, q, batch, p.s, &q));
+        HRAG_TRY(launch_sim_gemm(e->d_pemb, e->p_rows, e->kdim, q, batch, e->d_spass, e->ld_p, p.s, 0, e->emb_dtype));
     }
     // "seeds" scope: the prior normalised over the allowed passages, 0 elsewhere -- the min / max below are then 0 / 1
     // and every prior kernel's own normalisation is exact identity on these rows (include/hrag.h)
-    if (scoped) HRAG_TRY(launch_masked_prior(e->d_spass, batch, e->n_passages, e->ld_p, *mask, s));
-    const bool sv_half = sv && use_sv_half(e, ppr_iters, damping);
-    HRAG_TRY(launch_row_minmax(e->d_spass, batch, e->n_passages, e->ld_p, e->d_mn_p, e->d_mx_p, s));
-    if (prof) HRAG_HIP_TRY(hipEventRecord(e->ev[EV_SIM], s));
-    // reset vector: entity seeds + passage prior (HippoRAG.py:1574-1638)
-    if (e->d_subj) {
-        HRAG_TRY(hrag_stage_seeds(e, kept_idx, kept_score, kept_count, kf, link_top_k, batch, e->d_seed_vtx,
-                                  e->d_seed_w, e->d_seed_cnt, e->d_flags, stream));
-    } else {
-        // an index without facts (no triples extracted): every query takes the DPR ranking, as the
-        // reference does when rerank_facts returns nothing (HippoRAG.py:467-469, :1453-1455)
-        HRAG_TRY(launch_fill_i32(e->d_flags, 1, batch, s));
-        HRAG_HIP_TRY(hipMemsetAsync(e->d_seed_cnt, 0, (size_t)batch * sizeof(int32_t), s));
+    if (c.scoped) HRAG_TRY(launch_masked_prior(e->d_spass, batch, e->n_passages, e->ld_p, *mask, p.s));
+    HRAG_TRY(launch_row_minmax(e->d_spass, batch, e->n_passages, e->ld_p, e->d_mn_p, e->d_mx_p, p.s));
+    HRAG_TRY(p.mark(EV_SIM));
+    if (e->d_subj)
+        return hrag_stage_seeds(e, c.kept_idx, c.kept_score, c.kept_count, c.kf, c.link_top_k, batch, e->d_seed_vtx,
+                                e->d_seed_w, e->d_seed_cnt, e->d_flags, c.stream);
+    // an index without facts (no triples extracted): every query takes the DPR ranking, as the
+    // reference does when rerank_facts returns nothing (HippoRAG.py:467-469, :1453-1455)
+    HRAG_TRY(launch_fill_i32(e->d_flags, 1, batch, p.s));
+    HRAG_HIP_TRY(hipMemsetAsync(e->d_seed_cnt, 0, (size_t)batch * sizeof(int32_t), p.s));
+    return HRAG_OK;
+}
+
+// The seeds become extra teleport rows behind the passages, i.e. v is one array that every sweep reads identically (fp16
+// and small-batch states; tele = [slabs][tele_rows][width], tele_rows 0 for the one slab of a small batch).  Those rows
+// start from zero, the row -> teleport-row map and the column bitmap (the columns where x_0 can be non-zero: passage
+// vertices + this batch's seeds) from their static parts
+static hrag_status seed_teleport_rows(hrag_engine *e, float *tele, int64_t tele_rows, int width, int slabs, const float *qs,
+                                      int32_t batch, hipStream_t s) {
+    BlitList z;
+    z.zero(tele + (size_t)e->n_passages * width, (int64_t)batch * kMaxSeeds * width * sizeof(float), slabs,
+           (int64_t)tele_rows * width * sizeof(float));
+    z.copy(e->d_row_slot, e->d_row_to_tele, (int64_t)e->V * sizeof(int32_t));
+    z.copy(e->d_colmask, e->d_colmask_static, (int64_t)e->colmask_words * sizeof(uint32_t));
+    HRAG_TRY(launch_blits(z, s));
+    HRAG_TRY(launch_ppr16_seed_rows(e->d_seed_vtx, e->d_seed_w, e->d_seed_cnt, qs, batch, e->n_passages, e->V, e->d_row_slot,
+                                    tele, tele_rows, width, s));
+    return launch_ppr8_mask_seeds(e->d_seed_vtx, e->d_seed_cnt, batch, e->V, e->d_colmask, s);
+}
+
+// staged fp8 state (ppr8.hip / shard.hip): the single-GPU engine is the row shard that owns everything
+static hrag_status retrieve_f8(hrag_engine *e, const RetrieveCall &c, RetrievePath &p) {
+    const int32_t batch = c.batch;
+    hrag_shard_layout sl;
+    HRAG_TRY(ppr8_layout(e, batch, 0, &sl));   // narrowest groups: two adjacent slabs per vertex
+    HRAG_TRY(ppr8_prior(e, e->d_mn_p, e->d_mx_p, c.passage_node_weight, e->d_flags, batch, e->d_zmax, e->d_mass, p.s));
+    HRAG_TRY(ppr8_begin(e, e->d_mn_p, e->d_mx_p, e->d_zmax, e->d_mass, c.passage_node_weight, e->d_seed_vtx,
+                        e->d_seed_w, e->d_seed_cnt, e->d_flags, batch, c.damping, c.ppr_iters, sl, e->d_pool8, p.s,
+                        c.ppr_max_iters, c.ppr_tol, c.residual != nullptr, true));
+    HRAG_TRY(p.mark(EV_SEED));
+    // `ppr_iters` sweeps + the conditional steps of the convergence contract (their gate words decide on the device)
+    // more than 256 queries: one launch per group of two slabs instead of one launch over all of them -- a launch then
+    // gathers from ONE group's 256 MB of state (configs[2]'s working set, which the Infinity Cache still helps with)
+    // instead of B / 256 times that: batch 1024 on configs[2]'s graph 69.8 -> 67.0 ms per call, 14.67 k -> 15.28 k queries/s
+    // (profiles/r06w_bench_cfg4_groupwise_ab.json: the rate of four batches of 256); results
+    // are bit-identical (the row shards have always issued their sweeps per group: tests/test_gpu_full_size.py)
+    const bool per_group = e->p8.n_groups > 1 && p8_groupwise_enabled();
+    for (int it = 0; it < e->p8.n_steps; ++it) {
+        if (per_group)
+            for (int g = 0; g < e->p8.n_groups; ++g) HRAG_TRY(ppr8_sweep(e, it, g, nullptr, p.s));
+        else
+            HRAG_TRY(ppr8_sweep(e, it, -1, nullptr, p.s));
+        HRAG_TRY(ppr8_decide(e, it, p.s));
     }
-    if (f8) {
-        // staged fp8 state (ppr8.hip / shard.hip): the single-GPU engine is the row shard that owns everything
-        hrag_shard_layout sl;
-        HRAG_TRY(ppr8_layout(e, batch, 0, &sl));   // narrowest groups: two adjacent slabs per vertex
-        HRAG_TRY(ppr8_prior(e, e->d_mn_p, e->d_mx_p, passage_node_weight, e->d_flags, batch, e->d_zmax, e->d_mass, s));
-        HRAG_TRY(ppr8_begin(e, e->d_mn_p, e->d_mx_p, e->d_zmax, e->d_mass, passage_node_weight, e->d_seed_vtx,
-                            e->d_seed_w, e->d_seed_cnt, e->d_flags, batch, damping, f8_iters, sl, e->d_pool8, s,
-                            ppr_max_iters, ppr_tol, residual_out != nullptr, true));
-    } else if (f16) {
-        // v is scaled per query by a power of two so that every iterate fits fp16 (ppr16.hip); the seeds
-        // become extra teleport rows, i.e. v is one array that every sweep reads identically
-        HRAG_TRY(launch_ppr16_scale(e->d_spass, e->ld_p, e->n_passages, e->d_mn_p, e->d_mx_p, passage_node_weight,
-                                    e->d_seed_w, e->d_seed_cnt, e->d_flags, batch, e->d_prior_sum, e->d_qscale, s));
-        HRAG_TRY(launch_rows_to_slab(e->d_spass, e->ld_p, e->n_passages, batch, kMinMaxScale, e->d_mn_p,
-                                     e->d_mx_p, passage_node_weight, e->d_flags, e->d_tele16, lay, s,
-                                     e->tele16_rows, e->d_qscale));
-        {
-            // seed rows of the teleport matrix start from zero, row -> teleport-row map and the column bitmap (the
-            // columns where h_0 = f16(v) can be non-zero: passage vertices + this batch's seeds) from their static parts
-            BlitList z;
-            z.zero(e->d_tele16 + (size_t)e->n_passages * 64, (int64_t)batch * kMaxSeeds * 64 * sizeof(float), lay.n_slabs,
-                   (int64_t)e->tele16_rows * 64 * sizeof(float));
-            z.copy(e->d_row_slot, e->d_row_to_tele, (int64_t)e->V * sizeof(int32_t));
-            z.copy(e->d_colmask, e->d_colmask_static, (int64_t)e->colmask_words * sizeof(uint32_t));
-            HRAG_TRY(launch_blits(z, s));
-        }
-        HRAG_TRY(launch_ppr16_seed_rows(e->d_seed_vtx, e->d_seed_w, e->d_seed_cnt, e->d_qscale, batch,
-                                        e->n_passages, e->V, e->d_row_slot, e->d_tele16, e->tele16_rows, 64, s));
-        HRAG_TRY(launch_ppr8_mask_seeds(e->d_seed_vtx, e->d_seed_cnt, batch, e->V, e->d_colmask, s));
-    } else if (sv) {
-        // small batch (ppr_sv.hip): v = [Np + seed rows][bp] fp32, same "seeds are teleport rows" form; with the
-        // fp16 state v carries the per-query power-of-two scale of ppr16.hip (every iterate fits fp16)
-        const float *qs = nullptr;
-        if (sv_half) {
-            HRAG_TRY(launch_ppr16_scale(e->d_spass, e->ld_p, e->n_passages, e->d_mn_p, e->d_mx_p, passage_node_weight,
-                                        e->d_seed_w, e->d_seed_cnt, e->d_flags, batch, e->d_prior_sum,
-                                        e->d_qscale, s));
-            qs = e->d_qscale;
-        }
-        HRAG_TRY(launch_ppr_sv_tele(e->d_spass, e->ld_p, e->n_passages, batch, e->d_mn_p, e->d_mx_p,
-                                    passage_node_weight, e->d_flags, e->d_tele_sv, bp, s, qs));
-        {
-            BlitList z;   // as on the fp16 path: zeroed seed rows, row map and column bitmap from their static parts
-            z.zero(e->d_tele_sv + (size_t)e->n_passages * bp, (int64_t)batch * kMaxSeeds * bp * sizeof(float));
-            z.copy(e->d_row_slot, e->d_row_to_tele, (int64_t)e->V * sizeof(int32_t));
-            z.copy(e->d_colmask, e->d_colmask_static, (int64_t)e->colmask_words * sizeof(uint32_t));
-            HRAG_TRY(launch_blits(z, s));
-        }
-        HRAG_TRY(launch_ppr16_seed_rows(e->d_seed_vtx, e->d_seed_w, e->d_seed_cnt, qs, batch,
-                                        e->n_passages, e->V, e->d_row_slot, e->d_tele_sv, 0, bp, s));
-        HRAG_TRY(launch_ppr8_mask_seeds(e->d_seed_vtx, e->d_seed_cnt, batch, e->V, e->d_colmask, s));
-    } else {
-        HRAG_TRY(hrag_stage_teleport(e, e->d_spass, e->ld_p, e->d_mn_p, e->d_mx_p, passage_node_weight,
-                                     e->d_flags, batch, e->d_tele, stream));
+    HRAG_TRY(p.mark(EV_PPR));
+    return ppr8_doc_scores(e, e->d_mn_p, e->d_mx_p, e->d_flags, batch, p.s, true);   // d_sums: the analytic mass
+}
+
+// two-stage fp16 state (ppr16.hip)
+static hrag_status retrieve_f16(hrag_engine *e, const RetrieveCall &c, RetrievePath &p) {
+    const int32_t batch = c.batch;
+    // v is scaled per query by a power of two so that every iterate fits fp16 (ppr16.hip)
+    HRAG_TRY(launch_ppr16_scale(e->d_spass, e->ld_p, e->n_passages, e->d_mn_p, e->d_mx_p, c.passage_node_weight,
+                                e->d_seed_w, e->d_seed_cnt, e->d_flags, batch, e->d_prior_sum, e->d_qscale, p.s));
+    HRAG_TRY(launch_rows_to_slab(e->d_spass, e->ld_p, e->n_passages, batch, kMinMaxScale, e->d_mn_p,
+                                 e->d_mx_p, c.passage_node_weight, e->d_flags, e->d_tele16, p.lay, p.s,
+                                 e->tele16_rows, e->d_qscale));
+    HRAG_TRY(seed_teleport_rows(e, e->d_tele16, e->tele16_rows, 64, p.lay.n_slabs, e->d_qscale, batch, p.s));
+    HRAG_TRY(p.mark(EV_SEED));
+    HRAG_TRY(ppr16_run(e, p.plan, p.s));
+    HRAG_TRY(p.mark(EV_PPR));
+    // the same tail as the fp8 path: closed-form mass, x at the passages already in passage order
+    HRAG_TRY(launch_ppr_sv_mass(e->d_tele16, 64, e->tele16_rows, e->n_passages,
+                                e->n_passages + (int64_t)batch * kMaxSeeds, e->d_piso, e->d_iso, e->d_row_to_tele,
+                                e->d_seed_vtx, e->d_seed_w, e->d_seed_cnt, e->d_qscale, e->V, batch, c.damping,
+                                c.ppr_iters, e->d_colsum_partial, e->d_sums, p.s));
+    return ppr8_doc_scores(e, e->d_mn_p, e->d_mx_p, e->d_flags, batch, p.s, false);
+}
+
+// small batch (ppr_sv.hip): v = [Np + seed rows][bp] fp32, same "seeds are teleport rows" form; with the
+// fp16 state v carries the per-query power-of-two scale of ppr16.hip (every iterate fits fp16)
+static hrag_status retrieve_sv(hrag_engine *e, const RetrieveCall &c, RetrievePath &p) {
+    const int32_t batch = c.batch;
+    const int bp = p.bp;
+    const float *qs = nullptr;
+    if (use_sv_half(e, c.ppr_iters, c.damping)) {
+        HRAG_TRY(launch_ppr16_scale(e->d_spass, e->ld_p, e->n_passages, e->d_mn_p, e->d_mx_p, c.passage_node_weight,
+                                    e->d_seed_w, e->d_seed_cnt, e->d_flags, batch, e->d_prior_sum,
+                                    e->d_qscale, p.s));
+        qs = e->d_qscale;
     }
-    if (prof) HRAG_HIP_TRY(hipEventRecord(e->ev[EV_SEED], s));
-    // PPR (HippoRAG.py:1736-1743): fixed-count leaky power iteration
-    if (f8) {
-        // `f8_iters` sweeps + the conditional steps of the convergence contract (their gate words decide on the device)
-        // more than 256 queries: one launch per group of two slabs instead of one launch over all of them -- a launch then
-        // gathers from ONE group's 256 MB of state (configs[2]'s working set, which the Infinity Cache still helps with)
-        // instead of B / 256 times that: batch 1024 on configs[2]'s graph 69.8 -> 67.0 ms per call, 14.67 k -> 15.28 k queries/s
-        // (profiles/r06w_bench_cfg4_groupwise_ab.json: the rate of four batches of 256); results
-        // are bit-identical (the row shards have always issued their sweeps per group: tests/test_gpu_full_size.py)
-        const bool per_group = e->p8.n_groups > 1 && p8_groupwise_enabled();
-        for (int it = 0; it < e->p8.n_steps; ++it) {
-            if (per_group)
-                for (int g = 0; g < e->p8.n_groups; ++g) HRAG_TRY(ppr8_sweep(e, it, g, nullptr, s));
-            else
-                HRAG_TRY(ppr8_sweep(e, it, -1, nullptr, s));
-            HRAG_TRY(ppr8_decide(e, it, s));
-        }
-    } else if (f16) {
-        HRAG_TRY(ppr16_run(e, batch, damping, ppr_iters, s, est, &sweeps_run, ppr_tol == 0.f, ppr_tol, ppr_max_iters, &ext_max));
-    } else if (sv) {
-        HRAG_TRY(ppr_sv_run(e, e->d_row_slot, e->d_tele_sv, bp, damping, ppr_iters, s, est, batch, &sweeps_run, ppr_tol == 0.f,
-                            ppr_tol, ppr_max_iters, &ext_max));
-    } else {
-        float *x = e->d_x, *y = e->d_y;
-        HRAG_TRY(ppr_init(e, e->d_tele, e->n_passages, e->d_row_to_tele, e->d_seed_vtx, e->d_seed_w,
-                          e->d_seed_cnt, batch, x, lay, s));
-        for (int it = 0; it < ppr_iters; ++it) {
-            HRAG_TRY(ppr_step(e, e->d_tele, e->n_passages, e->d_row_to_tele, e->d_seed_vtx, e->d_seed_w,
-                              e->d_seed_cnt, batch, damping, x, y, lay, false, s));
-            std::swap(x, y);
-        }
-        if (x != e->d_x) std::swap(e->d_x, e->d_y);  // keep the final state in d_x (d_y: the sweep before)
-        if (est) HRAG_TRY(launch_passage_delta(e->d_x, e->d_y, e->V, e->d_passage_vertex, e->n_passages, batch, lay, est, s));
+    HRAG_TRY(launch_ppr_sv_tele(e->d_spass, e->ld_p, e->n_passages, batch, e->d_mn_p, e->d_mx_p,
+                                c.passage_node_weight, e->d_flags, e->d_tele_sv, bp, p.s, qs));
+    HRAG_TRY(seed_teleport_rows(e, e->d_tele_sv, 0, bp, 1, qs, batch, p.s));
+    HRAG_TRY(p.mark(EV_SEED));
+    HRAG_TRY(ppr_sv_run(e, e->d_row_slot, e->d_tele_sv, bp, p.plan, p.s));
+    HRAG_TRY(p.mark(EV_PPR));
+    // normalisation: the closed-form mass of the K-sweep iterate (the last sweep only produced the passage rows)
+    HRAG_TRY(launch_ppr_sv_mass(e->d_tele_sv, bp, 0, e->n_passages, e->n_passages + (int64_t)batch * kMaxSeeds,
+                                e->d_piso, e->d_iso, e->d_row_to_tele, e->d_seed_vtx, e->d_seed_w, e->d_seed_cnt,
+                                qs, e->V, batch, c.damping, c.ppr_iters, e->d_colsum_partial, e->d_sums, p.s));
+    return launch_ppr_sv_rows(e->d_x, e->d_passage_vertex, e->n_passages, batch, e->d_sums, e->d_doc,
+                              e->ld_p, e->d_spass, e->ld_p, e->d_mn_p, e->d_mx_p, e->d_flags, bp, p.s);
+}
+
+// fp32 state over the CSR (ppr_spmm.hip), HippoRAG.py:1736-1743: fixed-count leaky power iteration
+static hrag_status retrieve_f32(hrag_engine *e, const RetrieveCall &c, RetrievePath &p) {
+    const int32_t batch = c.batch;
+    HRAG_TRY(hrag_stage_teleport(e, e->d_spass, e->ld_p, e->d_mn_p, e->d_mx_p, c.passage_node_weight,
+                                 e->d_flags, batch, e->d_tele, c.stream));
+    HRAG_TRY(p.mark(EV_SEED));
+    const Reset32 v{e->d_tele, e->n_passages, e->d_row_to_tele, e->d_seed_vtx, e->d_seed_w, e->d_seed_cnt};
+    HRAG_TRY(ppr_init(e, v, batch, e->d_x, p.lay, p.s));
+    HRAG_TRY(ping_pong32(e, c.ppr_iters, [&](int, float *x, float *y) { return ppr_step(e, v, batch, c.damping, x, y, p.lay, false, p.s); }));
+    if (p.plan.est)
+        HRAG_TRY(launch_passage_delta(e->d_x, e->d_y, e->V, e->d_passage_vertex, e->n_passages, batch, p.lay, p.plan.est, p.s));
+    HRAG_TRY(p.mark(EV_PPR));
+    HRAG_TRY(launch_colsum(e->d_x, e->V, 0, e->V, batch, p.lay, e->d_colsum_partial, e->d_sums, p.s));
+    return launch_slab_to_rows(e->d_x, e->V, e->d_passage_vertex, e->n_passages, batch, e->d_sums, e->d_doc, e->ld_p,
+                               e->d_spass, e->ld_p, e->d_mn_p, e->d_mx_p, e->d_flags, p.lay, p.s);
+}
+
+// zero-mass flag, the ranking(p.s) (HippoRAG.py:1745-1747, :503), the contract's results, the per-query outputs, bookkeeping
+static hrag_status retrieve_back(hrag_engine *e, const RetrieveCall &c, const TopkMask *mask, const RetrievePath &p) {
+    const int32_t batch = c.batch;
+    int32_t *est = p.plan.est;
+    HRAG_TRY(launch_flag_zero_mass(e->d_sums, batch, e->d_flags, 2, p.s));
+    if (c.doc_idx)
+        HRAG_TRY(rank_rows(e, e->d_doc, batch, e->n_passages, c.k, 0, kNormNone, c.doc_idx, c.doc_score, p.s, mask));
+    if (c.grp) HRAG_TRY(rank_groups(e, e->d_doc, batch, c.k, mask, c.grp, p.s));
+    const bool measured = p.f8() || est != nullptr;
+    if (!p.f8() && est)
+        HRAG_TRY(launch_ppr8_finalize(est, e->d_flags, batch, c.damping / (1.0f - c.damping), c.ppr_tol, p.plan.sweeps,
+                                      e->d_ctl, p.plan.e_max, nullptr, 0, e->d_sums, e->d_resid, e->d_iters_used, p.s));
+    BlitList out;   // the per-query results in one launch
+    out.copy(c.flags, e->d_flags, (int64_t)batch * sizeof(int32_t));
+    if (measured) {
+        out.copy(c.residual, e->d_resid, (int64_t)batch * sizeof(float));
+        out.copy(c.iters, e->d_iters_used, (int64_t)batch * sizeof(int32_t));
     }
-    if (prof) HRAG_HIP_TRY(hipEventRecord(e->ev[EV_PPR], s));
-    // doc scores + ranking (HippoRAG.py:1745-1747, :503)
-    if (sv) {
-        // normalisation: the closed-form mass of the K-sweep iterate (the last sweep only produced the passage rows)
-        HRAG_TRY(launch_ppr_sv_mass(e->d_tele_sv, bp, 0, e->n_passages, e->n_passages + (int64_t)batch * kMaxSeeds,
-                                    e->d_piso, e->d_iso, e->d_row_to_tele, e->d_seed_vtx, e->d_seed_w, e->d_seed_cnt,
-                                    sv_half ? e->d_qscale : nullptr, e->V, batch, damping, ppr_iters,
-                                    e->d_colsum_partial, e->d_sums, s));
-        HRAG_TRY(launch_ppr_sv_rows(e->d_x, e->d_passage_vertex, e->n_passages, batch, e->d_sums, e->d_doc,
-                                    e->ld_p, e->d_spass, e->ld_p, e->d_mn_p, e->d_mx_p, e->d_flags, bp, s));
-    } else if (f8) {
-        HRAG_TRY(ppr8_doc_scores(e, e->d_mn_p, e->d_mx_p, e->d_flags, batch, s, true));   // d_sums: the analytic mass
-    } else if (f16) {
-        // the same tail as the fp8 path: closed-form mass, x at the passages already in passage order
-        HRAG_TRY(launch_ppr_sv_mass(e->d_tele16, 64, e->tele16_rows, e->n_passages,
-                                    e->n_passages + (int64_t)batch * kMaxSeeds, e->d_piso, e->d_iso, e->d_row_to_tele,
-                                    e->d_seed_vtx, e->d_seed_w, e->d_seed_cnt, e->d_qscale, e->V, batch, damping,
-                                    ppr_iters, e->d_colsum_partial, e->d_sums, s));
-        HRAG_TRY(ppr8_doc_scores(e, e->d_mn_p, e->d_mx_p, e->d_flags, batch, s, false));
-    } else {
-        HRAG_TRY(launch_colsum(e->d_x, e->V, 0, e->V, batch, lay, e->d_colsum_partial, e->d_sums, s));
-        HRAG_TRY(launch_slab_to_rows(e->d_x, e->V, e->d_passage_vertex, e->n_passages, batch, e->d_sums,
-                                     e->d_doc, e->ld_p, e->d_spass, e->ld_p, e->d_mn_p, e->d_mx_p, e->d_flags,
-                                     lay, s));
-    }
-    HRAG_TRY(launch_flag_zero_mass(e->d_sums, batch, e->d_flags, 2, s));
-    if (doc_idx_out)
-        HRAG_TRY(rank_rows(e, e->d_doc, batch, e->n_passages, k, 0, kNormNone, doc_idx_out, doc_score_out, s, mask));
-    if (grp) HRAG_TRY(rank_groups(e, e->d_doc, batch, k, mask, grp, s));
-    const bool measured = f8 || est != nullptr;
-    if (!f8 && est)
-        HRAG_TRY(launch_ppr8_finalize(est, e->d_flags, batch, damping / (1.0f - damping), ppr_tol, sweeps_run, e->d_ctl,
-                                      ext_max, nullptr, 0, e->d_sums, e->d_resid, e->d_iters_used, s));
-    {
-        BlitList out;   // the per-query results in one launch
-        out.copy(flags_out, e->d_flags, (int64_t)batch * sizeof(int32_t));
-        if (measured) {
-            out.copy(residual_out, e->d_resid, (int64_t)batch * sizeof(float));
-            out.copy(iters_out, e->d_iters_used, (int64_t)batch * sizeof(int32_t));
-        }
-        HRAG_TRY(launch_blits(out, s));
-    }
+    HRAG_TRY(launch_blits(out, p.s));
     if (!measured) {   // no sweep measured anything (ppr_iters == 0, or nothing asked for): -1 / the count as given
-        if (residual_out) HRAG_TRY(launch_fill_i32(reinterpret_cast<int32_t *>(residual_out), (int32_t)0xbf800000u, batch, s));
-        if (iters_out) HRAG_TRY(launch_fill_i32(iters_out, sweeps_run, batch, s));
+        if (c.residual) HRAG_TRY(launch_fill_i32(reinterpret_cast<int32_t *>(c.residual), (int32_t)0xbf800000u, batch, p.s));
+        if (c.iters) HRAG_TRY(launch_fill_i32(c.iters, p.plan.sweeps, batch, p.s));
     }
-    if (prof) {
-        HRAG_HIP_TRY(hipEventRecord(e->ev[EV_RANK], s));
-        e->have_retrieve_ev = true;
-    }
-    e->last.ppr_iters = ppr_iters;
-    e->last.n_slabs = lay.n_slabs;
-    e->last.slab_width = f8 ? 128 : lay.bc;
-    e->last_ppr_state = f8 ? HRAG_PPR_STATE_FP8 : f16 ? HRAG_PPR_STATE_F16 : sv ? HRAG_PPR_STATE_SMALL : HRAG_PPR_STATE_F32;
+    HRAG_TRY(p.mark(EV_RANK));
+    if (p.ev) e->have_retrieve_ev = true;
+    e->last.ppr_iters = c.ppr_iters;
+    e->last.n_slabs = p.lay.n_slabs;
+    e->last.slab_width = p.f8() ? 128 : p.lay.bc;
+    e->last_ppr_state = p.state;
     e->rows_batch = batch;
     e->counters.retrieve.fetch_add(1);
     e->counters.queries.fetch_add(batch);
     return HRAG_OK;
 }
 
+// hrag_retrieve / hrag_retrieve_scored and their filtered, scoped and grouped forms: the passage scores come from this
+// engine's embeddings (c.q_pass) or from the caller (c.pass_scores fp32 [batch, pass_ld] raw cosine scores, passage order)
+static hrag_status retrieve_impl(hrag_engine *e, const RetrieveCall &c) {
+    const int32_t batch = c.batch;
+    HRAG_TRY(check_batch(e, batch));
+    TopkMask fm;
+    const TopkMask *mask = nullptr;
+    HRAG_TRY(doc_filter(e, c.words, c.ld_words, fm, &mask));
+    HRAG_REQUIRE(!c.scoped || mask, "NULL filter (the scoped call needs the allowed passages)");
+    if (c.grp) HRAG_TRY(check_grouped(e, c.grp));
+    HRAG_REQUIRE(c.ppr_tol >= 0.f && c.ppr_tol == c.ppr_tol, "ppr_tol must be >= 0");
+    HRAG_REQUIRE(c.ppr_tol == 0.f || c.ppr_tol >= HRAG_PPR_TOL_MIN,
+                 "ppr_tol=%g is below HRAG_PPR_TOL_MIN=%g: fp32 arithmetic leaves an error floor of %g however small the "
+                 "measured residual reads (include/hrag.h: error <= max(%g * residual, floor))", (double)c.ppr_tol,
+                 (double)HRAG_PPR_TOL_MIN, (double)HRAG_PPR_ERR_FLOOR_F32, (double)HRAG_PPR_ERR_K);
+    HRAG_REQUIRE(c.ppr_tol == 0.f || c.ppr_max_iters >= c.ppr_iters, "ppr_max_iters=%d < ppr_iters=%d", c.ppr_max_iters,
+                 c.ppr_iters);
+    HRAG_REQUIRE((c.q_pass || c.pass_scores) && c.kept_idx && c.kept_score && c.kept_count, "NULL argument");
+    // a grouped call may leave the ungrouped ranking out (both pointers NULL)
+    HRAG_REQUIRE(c.grp ? (c.doc_idx != nullptr) == (c.doc_score != nullptr) : c.doc_idx && c.doc_score, "NULL argument");
+    HRAG_REQUIRE(e->n_rows == e->V && e->p_rows == e->n_passages,
+                 "hrag_retrieve needs an unsharded engine; sharded engines use the hrag_stage_* operators");
+    HRAG_REQUIRE(c.pass_scores || e->d_pemb, "the engine was created without passage embeddings: use hrag_retrieve_scored");
+    HRAG_REQUIRE(!c.pass_scores || c.pass_ld >= e->n_passages, "pass_ld=%lld < n_passages", (long long)c.pass_ld);
+    HRAG_REQUIRE(c.k >= 1 && c.k <= e->max_topk, "k=%d outside [1, max_topk=%d]", c.k, e->max_topk);
+    HRAG_REQUIRE(c.ppr_iters >= 0, "ppr_iters must be >= 0");
+    HRAG_REQUIRE(c.damping >= 0.f && c.damping < 1.f, "damping %g outside [0, 1)", (double)c.damping);
+    HRAG_REQUIRE(e->n_passages >= 1, "engine has no passages");
+    HRAG_ENGINE_CALL(e, c.stream);
+    e->rows_batch = 0;   // the score rows are being rewritten (hrag_last_group_hits); set again when all is enqueued
+    RetrievePath p;
+    p.s = (hipStream_t)c.stream;
+    p.ev = e->profiling ? e->ev : nullptr;
+    const bool sv = use_sv(e, batch);
+    const bool f8 = !sv && batch > 64 && e->d_pool8[0] && ppr8_usable(e, batch, c.ppr_iters, c.damping);
+    const bool f16 = !sv && !f8 && use_f16(e, batch, c.ppr_iters, c.damping);
+    p.state = f8 ? HRAG_PPR_STATE_FP8 : f16 ? HRAG_PPR_STATE_F16 : sv ? HRAG_PPR_STATE_SMALL : HRAG_PPR_STATE_F32;
+    p.bp = sv_width(batch);
+    p.lay = e->layout(batch);
+    if (f16 || f8) { p.lay.bc = 64; p.lay.n_slabs = n_slabs64(batch); }
+    if (sv) { p.lay.bc = p.bp; p.lay.n_slabs = 1; }
+    const bool want_est = c.residual != nullptr || c.ppr_tol > 0.f;
+    p.plan.batch = batch; p.plan.iters = p.plan.sweeps = c.ppr_iters; p.plan.damping = c.damping;
+    p.plan.est = (want_est && !f8 && c.ppr_iters >= 1) ? e->d_est_f : nullptr;
+    p.plan.allow_accel = c.ppr_tol == 0.f;   // under a tolerance the two-stage states keep the plain plan (accel_plan16)
+    p.plan.tol = c.ppr_tol; p.plan.max_iters = c.ppr_max_iters;
+    HRAG_TRY(retrieve_front(e, c, mask, p));
+    HRAG_TRY((f8 ? retrieve_f8 : f16 ? retrieve_f16 : sv ? retrieve_sv : retrieve_f32)(e, c, p));
+    return retrieve_back(e, c, mask, p);
+}
+
+// hrag_dense_retrieve and its filtered, scoped and grouped forms
+static hrag_status dense_impl(hrag_engine *e, const RetrieveCall &c) {
+    const int32_t batch = c.batch;
+    HRAG_TRY(check_batch(e, batch));
+    TopkMask fm;
+    const TopkMask *mask = nullptr;
+    HRAG_TRY(doc_filter(e, c.words, c.ld_words, fm, &mask));
+    HRAG_REQUIRE(!c.scoped || mask, "NULL filter (the scoped call needs the allowed passages)");
+    if (c.grp) HRAG_TRY(check_grouped(e, c.grp));
+    HRAG_REQUIRE(c.q_pass != nullptr, "NULL argument");
+    HRAG_REQUIRE(c.grp ? (c.doc_idx != nullptr) == (c.doc_score != nullptr) : c.doc_idx && c.doc_score, "NULL argument");
+    HRAG_REQUIRE(e->p_rows == e->n_passages && e->d_pemb, "hrag_dense_retrieve needs the whole passage matrix");
+    HRAG_REQUIRE(c.k >= 1 && c.k <= e->max_topk, "k=%d outside [1, max_topk=%d]", c.k, e->max_topk);
+    hipStream_t s = (hipStream_t)c.stream;
+    HRAG_ENGINE_CALL(e, c.stream);
+    e->counters.dense.fetch_add(1);
+    e->counters.queries.fetch_add(batch);
+    const uint16_t *q = c.q_pass;
+    HRAG_TRY(prep_query(e, q, batch, s, &q));
+    HRAG_TRY(launch_sim_gemm(e->d_pemb, e->p_rows, e->kdim, q, batch, e->d_spass, e->ld_p, s, 0, e->emb_dtype));
+    // "seeds" scope: normalised over the allowed passages first; the ranking's own min-max is then identity
+    if (c.scoped) HRAG_TRY(launch_masked_prior(e->d_spass, batch, e->n_passages, e->ld_p, *mask, s));
+    if (c.doc_idx)
+        HRAG_TRY(rank_rows(e, e->d_spass, batch, e->n_passages, c.k, 0, kNormMinMax, c.doc_idx, c.doc_score, s, mask));
+    if (c.grp) {
+        // the groups are formed over the scores the dense ranking returns: the rows normalised as its top-k does
+        e->rows_batch = 0;
+        HRAG_TRY(launch_row_minmax(e->d_spass, batch, e->n_passages, e->ld_p, e->d_mn_p, e->d_mx_p, s));
+        HRAG_TRY(launch_minmax_rows(e->d_spass, batch, e->n_passages, e->ld_p, e->d_mn_p, e->d_mx_p, e->d_doc, e->ld_p, s));
+        HRAG_TRY(rank_groups(e, e->d_doc, batch, c.k, mask, c.grp, s));
+        e->rows_batch = batch;
+    }
+    return HRAG_OK;
+}
+
+// ---- the exported forms: each states its own preconditions, fills the record and calls the impl
 hrag_status hrag_retrieve(hrag_engine *e, const uint16_t *q_pass, int32_t batch,
                           const int32_t *kept_idx, const float *kept_score, const int32_t *kept_count,
                           int32_t kf, int32_t link_top_k, float damping, float passage_node_weight,
                           int32_t ppr_iters, int32_t ppr_max_iters, float ppr_tol, int32_t k, int32_t *doc_idx_out,
                           float *doc_score_out, int32_t *flags_out, float *residual_out, int32_t *iters_out,
                           hrag_stream stream) {
-    return hrag_retrieve_filtered(e, q_pass, batch, kept_idx, kept_score, kept_count, kf, link_top_k, damping,
-                                  passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol, k, doc_idx_out, doc_score_out,
-                                  flags_out, residual_out, iters_out, stream, nullptr, 0);
+    HRAG_REQUIRE(q_pass != nullptr, "NULL argument");
+    return retrieve_impl(e, RetrieveCall(q_pass, batch, stream).facts(kept_idx, kept_score, kept_count, kf, link_top_k)
+                                .ppr(damping, passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol)
+                                .out(k, doc_idx_out, doc_score_out, flags_out, residual_out, iters_out));
 }
 
 hrag_status hrag_retrieve_filtered(hrag_engine *e, const uint16_t *q_pass, int32_t batch,
@@ -1639,9 +1700,10 @@ hrag_status hrag_retrieve_filtered(hrag_engine *e, const uint16_t *q_pass, int32
                                    float *doc_score_out, int32_t *flags_out, float *residual_out, int32_t *iters_out,
                                    hrag_stream stream, const uint32_t *filter_dev, int64_t filter_ld_words) {
     HRAG_REQUIRE(q_pass != nullptr, "NULL argument");
-    return retrieve_impl(e, q_pass, nullptr, 0, batch, kept_idx, kept_score, kept_count, kf, link_top_k, damping,
-                         passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol, k, doc_idx_out, doc_score_out,
-                         flags_out, residual_out, iters_out, stream, filter_dev, filter_ld_words);
+    return retrieve_impl(e, RetrieveCall(q_pass, batch, stream).facts(kept_idx, kept_score, kept_count, kf, link_top_k)
+                                .ppr(damping, passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol)
+                                .out(k, doc_idx_out, doc_score_out, flags_out, residual_out, iters_out)
+                                .filter(filter_dev, filter_ld_words));
 }
 
 hrag_status hrag_retrieve_scoped(hrag_engine *e, const uint16_t *q_pass, int32_t batch, const int32_t *kept_idx,
@@ -1652,9 +1714,51 @@ hrag_status hrag_retrieve_scoped(hrag_engine *e, const uint16_t *q_pass, int32_t
                                  int64_t filter_ld_words) {
     HRAG_REQUIRE(e != nullptr && q_pass != nullptr, "NULL argument");
     HRAG_TRY(refuse_row_shard(e, "hrag_retrieve_scoped", false));
-    return retrieve_impl(e, q_pass, nullptr, 0, batch, kept_idx, kept_score, kept_count, kf, link_top_k, damping,
-                         passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol, k, doc_idx_out, doc_score_out,
-                         flags_out, residual_out, iters_out, stream, filter_dev, filter_ld_words, true);
+    return retrieve_impl(e, RetrieveCall(q_pass, batch, stream).facts(kept_idx, kept_score, kept_count, kf, link_top_k)
+                                .ppr(damping, passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol)
+                                .out(k, doc_idx_out, doc_score_out, flags_out, residual_out, iters_out)
+                                .filter(filter_dev, filter_ld_words, true));
+}
+
+hrag_status hrag_retrieve_grouped(hrag_engine *e, const uint16_t *q_pass, int32_t batch, const int32_t *kept_idx,
+                                  const float *kept_score, const int32_t *kept_count, int32_t kf, int32_t link_top_k,
+                                  float damping, float passage_node_weight, int32_t ppr_iters, int32_t ppr_max_iters,
+                                  float ppr_tol, int32_t k, int32_t *doc_idx_out, float *doc_score_out, int32_t *flags_out,
+                                  float *residual_out, int32_t *iters_out, hrag_stream stream, const uint32_t *filter_dev,
+                                  int64_t filter_ld_words, int32_t scoped, int32_t agg, int32_t *group_idx_out,
+                                  float *group_score_out, int32_t *best_doc_idx_out) {
+    HRAG_REQUIRE(e != nullptr && q_pass != nullptr, "NULL argument");
+    const GroupOut g{agg, group_idx_out, group_score_out, best_doc_idx_out};
+    return retrieve_impl(e, RetrieveCall(q_pass, batch, stream).facts(kept_idx, kept_score, kept_count, kf, link_top_k)
+                                .ppr(damping, passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol)
+                                .out(k, doc_idx_out, doc_score_out, flags_out, residual_out, iters_out)
+                                .filter(filter_dev, filter_ld_words, scoped != 0, &g));
+}
+
+hrag_status hrag_retrieve_scored(hrag_engine *e, const float *pass_scores, int64_t pass_ld, int32_t batch,
+                                 const int32_t *kept_idx, const float *kept_score, const int32_t *kept_count,
+                                 int32_t kf, int32_t link_top_k, float damping, float passage_node_weight,
+                                 int32_t ppr_iters, int32_t ppr_max_iters, float ppr_tol, int32_t k,
+                                 int32_t *doc_idx_out, float *doc_score_out, int32_t *flags_out, float *residual_out,
+                                 int32_t *iters_out, hrag_stream stream) {
+    HRAG_REQUIRE(pass_scores != nullptr, "NULL argument");
+    return retrieve_impl(e, RetrieveCall(pass_scores, pass_ld, batch, stream).facts(kept_idx, kept_score, kept_count, kf, link_top_k)
+                                .ppr(damping, passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol)
+                                .out(k, doc_idx_out, doc_score_out, flags_out, residual_out, iters_out));
+}
+
+hrag_status hrag_retrieve_scored_filtered(hrag_engine *e, const float *pass_scores, int64_t pass_ld, int32_t batch,
+                                          const int32_t *kept_idx, const float *kept_score, const int32_t *kept_count,
+                                          int32_t kf, int32_t link_top_k, float damping, float passage_node_weight,
+                                          int32_t ppr_iters, int32_t ppr_max_iters, float ppr_tol, int32_t k,
+                                          int32_t *doc_idx_out, float *doc_score_out, int32_t *flags_out,
+                                          float *residual_out, int32_t *iters_out, hrag_stream stream,
+                                          const uint32_t *filter_dev, int64_t filter_ld_words) {
+    HRAG_REQUIRE(pass_scores != nullptr, "NULL argument");
+    return retrieve_impl(e, RetrieveCall(pass_scores, pass_ld, batch, stream).facts(kept_idx, kept_score, kept_count, kf, link_top_k)
+                                .ppr(damping, passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol)
+                                .out(k, doc_idx_out, doc_score_out, flags_out, residual_out, iters_out)
+                                .filter(filter_dev, filter_ld_words));
 }
 
 hrag_status hrag_retrieve_scored_scoped(hrag_engine *e, const float *pass_scores, int64_t pass_ld, int32_t batch,
@@ -1666,33 +1770,56 @@ hrag_status hrag_retrieve_scored_scoped(hrag_engine *e, const float *pass_scores
                                         const uint32_t *filter_dev, int64_t filter_ld_words) {
     HRAG_REQUIRE(e != nullptr && pass_scores != nullptr, "NULL argument");
     HRAG_TRY(refuse_row_shard(e, "hrag_retrieve_scored_scoped", false));
-    return retrieve_impl(e, nullptr, pass_scores, pass_ld, batch, kept_idx, kept_score, kept_count, kf, link_top_k,
-                         damping, passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol, k, doc_idx_out, doc_score_out,
-                         flags_out, residual_out, iters_out, stream, filter_dev, filter_ld_words, true);
+    return retrieve_impl(e, RetrieveCall(pass_scores, pass_ld, batch, stream).facts(kept_idx, kept_score, kept_count, kf, link_top_k)
+                                .ppr(damping, passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol)
+                                .out(k, doc_idx_out, doc_score_out, flags_out, residual_out, iters_out)
+                                .filter(filter_dev, filter_ld_words, true));
 }
 
-hrag_status hrag_retrieve_scored(hrag_engine *e, const float *pass_scores, int64_t pass_ld, int32_t batch,
-                                 const int32_t *kept_idx, const float *kept_score, const int32_t *kept_count,
-                                 int32_t kf, int32_t link_top_k, float damping, float passage_node_weight,
-                                 int32_t ppr_iters, int32_t ppr_max_iters, float ppr_tol, int32_t k,
-                                 int32_t *doc_idx_out, float *doc_score_out, int32_t *flags_out, float *residual_out,
-                                 int32_t *iters_out, hrag_stream stream) {
-    return hrag_retrieve_scored_filtered(e, pass_scores, pass_ld, batch, kept_idx, kept_score, kept_count, kf, link_top_k,
-                                         damping, passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol, k, doc_idx_out,
-                                         doc_score_out, flags_out, residual_out, iters_out, stream, nullptr, 0);
+hrag_status hrag_retrieve_scored_grouped(hrag_engine *e, const float *pass_scores, int64_t pass_ld, int32_t batch,
+                                         const int32_t *kept_idx, const float *kept_score, const int32_t *kept_count,
+                                         int32_t kf, int32_t link_top_k, float damping, float passage_node_weight,
+                                         int32_t ppr_iters, int32_t ppr_max_iters, float ppr_tol, int32_t k,
+                                         int32_t *doc_idx_out, float *doc_score_out, int32_t *flags_out,
+                                         float *residual_out, int32_t *iters_out, hrag_stream stream,
+                                         const uint32_t *filter_dev, int64_t filter_ld_words, int32_t scoped, int32_t agg,
+                                         int32_t *group_idx_out, float *group_score_out, int32_t *best_doc_idx_out) {
+    HRAG_REQUIRE(e != nullptr && pass_scores != nullptr, "NULL argument");
+    const GroupOut g{agg, group_idx_out, group_score_out, best_doc_idx_out};
+    return retrieve_impl(e, RetrieveCall(pass_scores, pass_ld, batch, stream).facts(kept_idx, kept_score, kept_count, kf, link_top_k)
+                                .ppr(damping, passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol)
+                                .out(k, doc_idx_out, doc_score_out, flags_out, residual_out, iters_out)
+                                .filter(filter_dev, filter_ld_words, scoped != 0, &g));
 }
 
-hrag_status hrag_retrieve_scored_filtered(hrag_engine *e, const float *pass_scores, int64_t pass_ld, int32_t batch,
-                                          const int32_t *kept_idx, const float *kept_score, const int32_t *kept_count,
-                                          int32_t kf, int32_t link_top_k, float damping, float passage_node_weight,
-                                          int32_t ppr_iters, int32_t ppr_max_iters, float ppr_tol, int32_t k,
-                                          int32_t *doc_idx_out, float *doc_score_out, int32_t *flags_out,
-                                          float *residual_out, int32_t *iters_out, hrag_stream stream,
-                                          const uint32_t *filter_dev, int64_t filter_ld_words) {
-    HRAG_REQUIRE(pass_scores != nullptr, "NULL argument");
-    return retrieve_impl(e, nullptr, pass_scores, pass_ld, batch, kept_idx, kept_score, kept_count, kf, link_top_k,
-                         damping, passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol, k, doc_idx_out, doc_score_out,
-                         flags_out, residual_out, iters_out, stream, filter_dev, filter_ld_words);
+hrag_status hrag_dense_retrieve(hrag_engine *e, const uint16_t *q_pass, int32_t batch, int32_t k,
+                                int32_t *doc_idx_out, float *doc_score_out, hrag_stream stream) {
+    return dense_impl(e, RetrieveCall(q_pass, batch, stream).out(k, doc_idx_out, doc_score_out));
+}
+
+hrag_status hrag_dense_retrieve_filtered(hrag_engine *e, const uint16_t *q_pass, int32_t batch, int32_t k,
+                                         int32_t *doc_idx_out, float *doc_score_out, hrag_stream stream,
+                                         const uint32_t *filter_dev, int64_t filter_ld_words) {
+    return dense_impl(e, RetrieveCall(q_pass, batch, stream).out(k, doc_idx_out, doc_score_out).filter(filter_dev, filter_ld_words));
+}
+
+hrag_status hrag_dense_retrieve_scoped(hrag_engine *e, const uint16_t *q_pass, int32_t batch, int32_t k,
+                                       int32_t *doc_idx_out, float *doc_score_out, hrag_stream stream,
+                                       const uint32_t *filter_dev, int64_t filter_ld_words) {
+    HRAG_REQUIRE(e != nullptr && filter_dev != nullptr, "NULL argument / NULL filter (the scoped call needs the allowed passages)");
+    HRAG_TRY(refuse_row_shard(e, "hrag_dense_retrieve_scoped", false));
+    return dense_impl(e, RetrieveCall(q_pass, batch, stream).out(k, doc_idx_out, doc_score_out)
+                             .filter(filter_dev, filter_ld_words, true));
+}
+
+hrag_status hrag_dense_retrieve_grouped(hrag_engine *e, const uint16_t *q_pass, int32_t batch, int32_t k,
+                                        int32_t *doc_idx_out, float *doc_score_out, hrag_stream stream,
+                                        const uint32_t *filter_dev, int64_t filter_ld_words, int32_t scoped, int32_t agg,
+                                        int32_t *group_idx_out, float *group_score_out, int32_t *best_doc_idx_out) {
+    HRAG_REQUIRE(e != nullptr, "engine is NULL");
+    const GroupOut g{agg, group_idx_out, group_score_out, best_doc_idx_out};
+    return dense_impl(e, RetrieveCall(q_pass, batch, stream).out(k, doc_idx_out, doc_score_out)
+                             .filter(filter_dev, filter_ld_words, scoped != 0, &g));
 }
 
 hrag_status hrag_last_doc_scores(hrag_engine *e, int32_t batch, float *out, int64_t ld, hrag_stream stream) {
@@ -1706,60 +1833,7 @@ hrag_status hrag_last_doc_scores(hrag_engine *e, int32_t batch, float *out, int6
     return HRAG_OK;
 }
 
-hrag_status hrag_dense_retrieve(hrag_engine *e, const uint16_t *q_pass, int32_t batch, int32_t k,
-                                int32_t *doc_idx_out, float *doc_score_out, hrag_stream stream) {
-    return hrag_dense_retrieve_filtered(e, q_pass, batch, k, doc_idx_out, doc_score_out, stream, nullptr, 0);
-}
-
-static hrag_status dense_impl(hrag_engine *e, const uint16_t *q_pass, int32_t batch, int32_t k, int32_t *doc_idx_out,
-                              float *doc_score_out, hrag_stream stream, const uint32_t *filter_dev,
-                              int64_t filter_ld_words, bool scoped, const GroupOut *grp = nullptr) {
-    HRAG_TRY(check_batch(e, batch));
-    TopkMask fm;
-    const TopkMask *mask = nullptr;
-    HRAG_TRY(doc_filter(e, filter_dev, filter_ld_words, fm, &mask));
-    HRAG_REQUIRE(!scoped || mask, "NULL filter (the scoped call needs the allowed passages)");
-    if (grp) HRAG_TRY(check_grouped(e, grp));
-    HRAG_REQUIRE(q_pass != nullptr, "NULL argument");
-    HRAG_REQUIRE(grp ? (doc_idx_out != nullptr) == (doc_score_out != nullptr) : doc_idx_out && doc_score_out, "NULL argument");
-    HRAG_REQUIRE(e->p_rows == e->n_passages && e->d_pemb, "hrag_dense_retrieve needs the whole passage matrix");
-    HRAG_REQUIRE(k >= 1 && k <= e->max_topk, "k=%d outside [1, max_topk=%d]", k, e->max_topk);
-    hipStream_t s = (hipStream_t)stream;
-    HRAG_ENGINE_CALL(e, stream);
-    e->counters.dense.fetch_add(1);
-    e->counters.queries.fetch_add(batch);
-    HRAG_TRY(prep_query(e, q_pass, batch, s, &q_pass));
-    HRAG_TRY(launch_sim_gemm(e->d_pemb, e->p_rows, e->kdim, q_pass, batch, e->d_spass, e->ld_p, s, 0, e->emb_dtype));
-    // "seeds" scope: normalised over the allowed passages first; the ranking's own min-max is then identity
-    if (scoped) HRAG_TRY(launch_masked_prior(e->d_spass, batch, e->n_passages, e->ld_p, *mask, s));
-    if (doc_idx_out)
-        HRAG_TRY(rank_rows(e, e->d_spass, batch, e->n_passages, k, 0, kNormMinMax, doc_idx_out, doc_score_out, s, mask));
-    if (grp) {
-        // the groups are formed over the scores the dense ranking returns: the rows normalised as its top-k does
-        e->rows_batch = 0;
-        HRAG_TRY(launch_row_minmax(e->d_spass, batch, e->n_passages, e->ld_p, e->d_mn_p, e->d_mx_p, s));
-        HRAG_TRY(launch_minmax_rows(e->d_spass, batch, e->n_passages, e->ld_p, e->d_mn_p, e->d_mx_p, e->d_doc, e->ld_p, s));
-        HRAG_TRY(rank_groups(e, e->d_doc, batch, k, mask, grp, s));
-        e->rows_batch = batch;
-    }
-    return HRAG_OK;
-}
-
-hrag_status hrag_dense_retrieve_filtered(hrag_engine *e, const uint16_t *q_pass, int32_t batch, int32_t k,
-                                         int32_t *doc_idx_out, float *doc_score_out, hrag_stream stream,
-                                         const uint32_t *filter_dev, int64_t filter_ld_words) {
-    return dense_impl(e, q_pass, batch, k, doc_idx_out, doc_score_out, stream, filter_dev, filter_ld_words, false);
-}
-
-hrag_status hrag_dense_retrieve_scoped(hrag_engine *e, const uint16_t *q_pass, int32_t batch, int32_t k,
-                                       int32_t *doc_idx_out, float *doc_score_out, hrag_stream stream,
-                                       const uint32_t *filter_dev, int64_t filter_ld_words) {
-    HRAG_REQUIRE(e != nullptr && filter_dev != nullptr, "NULL argument / NULL filter (the scoped call needs the allowed passages)");
-    HRAG_TRY(refuse_row_shard(e, "hrag_dense_retrieve_scoped", false));
-    return dense_impl(e, q_pass, batch, k, doc_idx_out, doc_score_out, stream, filter_dev, filter_ld_words, true);
-}
-
-// ---- grouped retrieval (include/hrag.h): the passage -> group table and the grouped forms of the three calls
+// ---- grouped retrieval (include/hrag.h): the passage -> group table
 hrag_status hrag_engine_set_passage_groups(hrag_engine *e, const int32_t *group_of, int64_t n_groups) {
     HRAG_REQUIRE(e != nullptr, "engine is NULL");
     HRAG_REQUIRE(!e->borrowed, "passage groups belong to the shared index: set them on the root engine, not on a workspace");
@@ -1820,44 +1894,6 @@ hrag_status hrag_engine_set_passage_groups(hrag_engine *e, const int32_t *group_
         HRAG_TRY(alloc_group_rows(e));
     }
     return HRAG_OK;
-}
-
-hrag_status hrag_retrieve_grouped(hrag_engine *e, const uint16_t *q_pass, int32_t batch, const int32_t *kept_idx,
-                                  const float *kept_score, const int32_t *kept_count, int32_t kf, int32_t link_top_k,
-                                  float damping, float passage_node_weight, int32_t ppr_iters, int32_t ppr_max_iters,
-                                  float ppr_tol, int32_t k, int32_t *doc_idx_out, float *doc_score_out, int32_t *flags_out,
-                                  float *residual_out, int32_t *iters_out, hrag_stream stream, const uint32_t *filter_dev,
-                                  int64_t filter_ld_words, int32_t scoped, int32_t agg, int32_t *group_idx_out,
-                                  float *group_score_out, int32_t *best_doc_idx_out) {
-    HRAG_REQUIRE(e != nullptr && q_pass != nullptr, "NULL argument");
-    const GroupOut g{agg, group_idx_out, group_score_out, best_doc_idx_out};
-    return retrieve_impl(e, q_pass, nullptr, 0, batch, kept_idx, kept_score, kept_count, kf, link_top_k, damping,
-                         passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol, k, doc_idx_out, doc_score_out,
-                         flags_out, residual_out, iters_out, stream, filter_dev, filter_ld_words, scoped != 0, &g);
-}
-
-hrag_status hrag_retrieve_scored_grouped(hrag_engine *e, const float *pass_scores, int64_t pass_ld, int32_t batch,
-                                         const int32_t *kept_idx, const float *kept_score, const int32_t *kept_count,
-                                         int32_t kf, int32_t link_top_k, float damping, float passage_node_weight,
-                                         int32_t ppr_iters, int32_t ppr_max_iters, float ppr_tol, int32_t k,
-                                         int32_t *doc_idx_out, float *doc_score_out, int32_t *flags_out,
-                                         float *residual_out, int32_t *iters_out, hrag_stream stream,
-                                         const uint32_t *filter_dev, int64_t filter_ld_words, int32_t scoped, int32_t agg,
-                                         int32_t *group_idx_out, float *group_score_out, int32_t *best_doc_idx_out) {
-    HRAG_REQUIRE(e != nullptr && pass_scores != nullptr, "NULL argument");
-    const GroupOut g{agg, group_idx_out, group_score_out, best_doc_idx_out};
-    return retrieve_impl(e, nullptr, pass_scores, pass_ld, batch, kept_idx, kept_score, kept_count, kf, link_top_k,
-                         damping, passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol, k, doc_idx_out, doc_score_out,
-                         flags_out, residual_out, iters_out, stream, filter_dev, filter_ld_words, scoped != 0, &g);
-}
-
-hrag_status hrag_dense_retrieve_grouped(hrag_engine *e, const uint16_t *q_pass, int32_t batch, int32_t k,
-                                        int32_t *doc_idx_out, float *doc_score_out, hrag_stream stream,
-                                        const uint32_t *filter_dev, int64_t filter_ld_words, int32_t scoped, int32_t agg,
-                                        int32_t *group_idx_out, float *group_score_out, int32_t *best_doc_idx_out) {
-    HRAG_REQUIRE(e != nullptr, "engine is NULL");
-    const GroupOut g{agg, group_idx_out, group_score_out, best_doc_idx_out};
-    return dense_impl(e, q_pass, batch, k, doc_idx_out, doc_score_out, stream, filter_dev, filter_ld_words, scoped != 0, &g);
 }
 
 hrag_status hrag_group_rows(const float *scores, int32_t batch, int64_t n, int64_t ld, const int64_t *group_ptr,
@@ -2052,14 +2088,9 @@ hrag_status hrag_ppr(hrag_engine *e, const float *reset, int32_t batch, float da
     const SlabLayout lay = e->layout(batch);
     HRAG_TRY(launch_rows_to_slab(reset, e->V, e->V, batch, kSanitize, nullptr, nullptr, 1.f, nullptr,
                                  e->d_tele_dense, lay, s));
-    float *x = e->d_x, *y = e->d_y;
-    HRAG_TRY(ppr_init(e, e->d_tele_dense, e->V, nullptr, nullptr, nullptr, nullptr, batch, x, lay, s));
-    for (int it = 0; it < iters; ++it) {
-        HRAG_TRY(ppr_step(e, e->d_tele_dense, e->V, nullptr, nullptr, nullptr, nullptr, batch, damping, x,
-                          y, lay, false, s));
-        std::swap(x, y);
-    }
-    if (x != e->d_x) std::swap(e->d_x, e->d_y);
+    const Reset32 v{e->d_tele_dense, e->V, nullptr, nullptr, nullptr, nullptr};   // dense over all vertices, no seeds
+    HRAG_TRY(ppr_init(e, v, batch, e->d_x, lay, s));
+    HRAG_TRY(ping_pong32(e, iters, [&](int, float *x, float *y) { return ppr_step(e, v, batch, damping, x, y, lay, false, s); }));
     HRAG_TRY(launch_colsum(e->d_x, e->V, 0, e->V, batch, lay, e->d_colsum_partial, e->d_sums, s));
     HRAG_TRY(launch_slab_to_rows(e->d_x, e->V, nullptr, e->V, batch, e->d_sums, x_out, e->V, nullptr, 0,
                                  nullptr, nullptr, nullptr, lay, s));
@@ -2077,14 +2108,10 @@ hrag_status hrag_ppr_sweeps(hrag_engine *e, int32_t batch, int32_t n, float damp
     if (flags & 4) {
         HRAG_REQUIRE(use_sv(e, batch), "small-batch kernels need an unsharded engine and batch <= 8");
         const int bp = sv_width(batch);
-        float *x = e->d_x, *y = e->d_y;
-        for (int it = 0; it < n; ++it) {
-            HRAG_TRY(launch_ppr_sv_sweep(ppr_sv_args(e, e->sell, x, y, e->d_row_slot, e->d_tele_sv, damping), bp,
-                                         (flags & 1) != 0, (hipStream_t)stream));
-            std::swap(x, y);
-        }
-        if (x != e->d_x) std::swap(e->d_x, e->d_y);
-        return HRAG_OK;
+        return ping_pong32(e, n, [&](int, float *x, float *y) {
+            return launch_ppr_sv_sweep(ppr_sv_args(e, e->sell, x, y, e->d_row_slot, e->d_tele_sv, damping), bp,
+                                       (flags & 1) != 0, (hipStream_t)stream);
+        });
     }
     if (flags & 8) {   // fp8 sweeps over the state the last hrag_retrieve left; flags bits 4..5 pick the mode
         HRAG_REQUIRE(e->f8_ready && e->d_pool8[0] && e->p8.active && e->p8.batch == batch,
@@ -2111,14 +2138,10 @@ hrag_status hrag_ppr_sweeps(hrag_engine *e, int32_t batch, int32_t n, float damp
     }
     HRAG_REQUIRE(e->d_x && e->d_tele, "the fp32-state sweep hook needs an unsharded engine");
     const SlabLayout lay = e->layout(batch);
-    float *x = e->d_x, *y = e->d_y;
-    for (int it = 0; it < n; ++it) {
-        HRAG_TRY(ppr_step(e, e->d_tele, e->n_passages, e->d_row_to_tele, e->d_seed_vtx, e->d_seed_w,
-                          e->d_seed_cnt, batch, damping, x, y, lay, (flags & 1) != 0, (hipStream_t)stream));
-        std::swap(x, y);
-    }
-    if (x != e->d_x) std::swap(e->d_x, e->d_y);
-    return HRAG_OK;
+    const Reset32 v{e->d_tele, e->n_passages, e->d_row_to_tele, e->d_seed_vtx, e->d_seed_w, e->d_seed_cnt};
+    return ping_pong32(e, n, [&](int, float *x, float *y) {
+        return ppr_step(e, v, batch, damping, x, y, lay, (flags & 1) != 0, (hipStream_t)stream);
+    });
 }
 
 }  // extern "C"

@@ -381,6 +381,64 @@ inline hrag_status prep_query(hrag_engine *e, const uint16_t *q, int32_t batch, 
     *out = e->d_qsplit;
     return HRAG_OK;
 }
+// what a grouped call adds to its ungrouped form (include/hrag.h, grouped retrieval)
+struct GroupOut {
+    int32_t agg;
+    int32_t *group_idx;
+    float *group_score;
+    int32_t *best_doc;
+};
+
+// One retrieve call, as an exported entry point describes it to retrieve_impl / dense_impl (engine.hip) and to
+// shard_retrieve (shard_driver.hip): every hrag_retrieve*, hrag_dense_retrieve* and hrag_shard_retrieve* function fills
+// one of these -- by name, through the setters -- and hands it on.  A dense call uses the source, k, the two doc
+// outputs, the filter and the group outputs only.
+struct RetrieveCall {
+    const uint16_t *q_pass = nullptr;     // passage source: queries against the engine's embeddings, or ...
+    const float *pass_scores = nullptr;   // ... the caller's raw scores fp32 [batch, pass_ld]
+    int64_t pass_ld = 0;
+    int32_t batch = 0;
+    hrag_stream stream = nullptr;
+    const int32_t *kept_idx = nullptr;    // the kept facts
+    const float *kept_score = nullptr;
+    const int32_t *kept_count = nullptr;
+    int32_t kf = 0, link_top_k = 0;
+    float damping = 0.f, passage_node_weight = 0.f;   // the PPR
+    int32_t ppr_iters = 0, ppr_max_iters = 0;
+    float ppr_tol = 0.f;
+    int32_t k = 0;
+    int32_t *doc_idx = nullptr;           // outputs
+    float *doc_score = nullptr;
+    int32_t *flags = nullptr;
+    float *residual = nullptr;
+    int32_t *iters = nullptr;
+    const uint32_t *words = nullptr;      // doc filter (doc_filter above); scoped: the "seeds" scope
+    int64_t ld_words = 0;
+    bool scoped = false;
+    const GroupOut *grp = nullptr;        // grouped call
+
+    RetrieveCall(const uint16_t *q, int32_t b, hrag_stream st) : q_pass(q), batch(b), stream(st) {}
+    RetrieveCall(const float *scores, int64_t ld, int32_t b, hrag_stream st)
+        : pass_scores(scores), pass_ld(ld), batch(b), stream(st) {}
+    RetrieveCall &facts(const int32_t *idx, const float *score, const int32_t *count, int32_t kf_, int32_t link) {
+        kept_idx = idx; kept_score = score; kept_count = count; kf = kf_; link_top_k = link;
+        return *this;
+    }
+    RetrieveCall &ppr(float damp, float weight, int32_t n, int32_t max_n, float tol) {
+        damping = damp; passage_node_weight = weight; ppr_iters = n; ppr_max_iters = max_n; ppr_tol = tol;
+        return *this;
+    }
+    RetrieveCall &out(int32_t k_, int32_t *idx, float *score, int32_t *flags_ = nullptr, float *residual_ = nullptr,
+                      int32_t *iters_ = nullptr) {
+        k = k_; doc_idx = idx; doc_score = score; flags = flags_; residual = residual_; iters = iters_;
+        return *this;
+    }
+    RetrieveCall &filter(const uint32_t *w, int64_t ld, bool scoped_ = false, const GroupOut *g = nullptr) {
+        words = w; ld_words = ld; scoped = scoped_; grp = g;
+        return *this;
+    }
+};
+
 // ---- shared between engine.hip and shard.hip
 // The fp8 path serves a batch when the truncation error of `iters` sweeps is below the parity bar
 // (damping^iters <= 2^-18) and the stage plan fits.

@@ -150,30 +150,29 @@ int64_t hrag_shard_workspace_bytes(hrag_engine *e, int32_t world, int32_t batch,
 namespace {
 
 // phase A of a row shard: local candidates (scoped: among the allowed facts, min / max over them), the global min / max,
-// the merge
-hrag_status score_facts_all(hrag_engine *e, const hrag_comm *comm, const uint16_t *q_fact, int32_t batch, int32_t k,
-                            void *workspace, int64_t workspace_bytes, int32_t *idx_out, float *score_out,
-                            hrag_stream stream, bool scoped, const uint32_t *filter_dev, int64_t filter_ld_words) {
+// the merge.  The record is used for what phase A has of it: q_pass = the FACT queries, out() = the fact outputs, the filter
+hrag_status score_facts_all(hrag_engine *e, const hrag_comm *comm, const RetrieveCall &c, void *workspace,
+                            int64_t workspace_bytes) {
+    const int32_t batch = c.batch, k = c.k;
     HRAG_TRY(check_comm(comm));
-    HRAG_REQUIRE(e && q_fact && workspace && idx_out && score_out && k >= 1, "bad argument");
-    HRAG_REQUIRE(!scoped || filter_dev, "NULL filter (the scoped call needs the allowed passages)");
+    HRAG_REQUIRE(e && c.q_pass && workspace && c.doc_idx && c.doc_score && k >= 1, "bad argument");
+    HRAG_REQUIRE(!c.scoped || c.words, "NULL filter (the scoped call needs the allowed passages)");
     HRAG_REQUIRE(workspace_bytes >= hrag_shard_workspace_bytes(e, comm->world, batch, k), "workspace too small: %lld < %lld bytes",
                  (long long)workspace_bytes, (long long)hrag_shard_workspace_bytes(e, comm->world, batch, k));
-    hipStream_t s = (hipStream_t)stream;
     Carver ws{static_cast<char *>(workspace), workspace_bytes};
     float *mn = ws.take<float>(batch), *mx = ws.take<float>(batch);
     int32_t *lidx = ws.take<int32_t>((int64_t)batch * k);
     float *lval = ws.take<float>((int64_t)batch * k);
     HRAG_REQUIRE(mn && mx && lidx && lval, "workspace too small");
-    if (scoped)
-        HRAG_TRY(hrag_shard_score_facts_scoped(e, q_fact, batch, k, lidx, lval, mn, mx, stream, filter_dev, filter_ld_words));
+    if (c.scoped)
+        HRAG_TRY(hrag_shard_score_facts_scoped(e, c.q_pass, batch, k, lidx, lval, mn, mx, c.stream, c.words, c.ld_words));
     else
-        HRAG_TRY(hrag_shard_score_facts(e, q_fact, batch, k, lidx, lval, mn, mx, stream));
+        HRAG_TRY(hrag_shard_score_facts(e, c.q_pass, batch, k, lidx, lval, mn, mx, c.stream));
     if (comm->world > 1) {
-        COMM_TRY(comm->all_reduce(comm->user, mn, batch, HRAG_COMM_F32, HRAG_COMM_MIN, stream), "all_reduce");
-        COMM_TRY(comm->all_reduce(comm->user, mx, batch, HRAG_COMM_F32, HRAG_COMM_MAX, stream), "all_reduce");
+        COMM_TRY(comm->all_reduce(comm->user, mn, batch, HRAG_COMM_F32, HRAG_COMM_MIN, c.stream), "all_reduce");
+        COMM_TRY(comm->all_reduce(comm->user, mx, batch, HRAG_COMM_F32, HRAG_COMM_MAX, c.stream), "all_reduce");
     }
-    return merge_topk(comm, lidx, lval, batch, k, ws, mn, mx, idx_out, score_out, s);
+    return merge_topk(comm, lidx, lval, batch, k, ws, mn, mx, c.doc_idx, c.doc_score, (hipStream_t)c.stream);
 }
 
 }  // namespace
@@ -183,53 +182,44 @@ extern "C" {
 hrag_status hrag_shard_score_facts_all(hrag_engine *e, const hrag_comm *comm, const uint16_t *q_fact, int32_t batch, int32_t k,
                                        void *workspace, int64_t workspace_bytes, int32_t *idx_out, float *score_out,
                                        hrag_stream stream) {
-    return score_facts_all(e, comm, q_fact, batch, k, workspace, workspace_bytes, idx_out, score_out, stream, false,
-                           nullptr, 0);
+    return score_facts_all(e, comm, RetrieveCall(q_fact, batch, stream).out(k, idx_out, score_out), workspace, workspace_bytes);
 }
 
 hrag_status hrag_shard_score_facts_all_scoped(hrag_engine *e, const hrag_comm *comm, const uint16_t *q_fact, int32_t batch,
                                               int32_t k, void *workspace, int64_t workspace_bytes, int32_t *idx_out,
                                               float *score_out, hrag_stream stream, const uint32_t *filter_dev,
                                               int64_t filter_ld_words) {
-    return score_facts_all(e, comm, q_fact, batch, k, workspace, workspace_bytes, idx_out, score_out, stream, true,
-                           filter_dev, filter_ld_words);
-}
-
-hrag_status hrag_shard_retrieve(hrag_engine *e, const hrag_comm *comm, const uint16_t *q_pass, int32_t batch,
-                                const int32_t *kept_idx, const float *kept_score, const int32_t *kept_count, int32_t kf,
-                                int32_t link_top_k, float damping, float passage_node_weight, int32_t ppr_iters,
-                                int32_t ppr_max_iters, float ppr_tol, int32_t k, int32_t n_groups, void *state0, void *state1,
-                                void *state2, void *workspace, int64_t workspace_bytes, int32_t *doc_idx_out,
-                                float *doc_score_out, int32_t *flags_out, float *residual_out, int32_t *iters_out,
-                                hrag_stream stream) {
-    return hrag_shard_retrieve_filtered(e, comm, q_pass, batch, kept_idx, kept_score, kept_count, kf, link_top_k, damping,
-                                        passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol, k, n_groups, state0, state1,
-                                        state2, workspace, workspace_bytes, doc_idx_out, doc_score_out, flags_out,
-                                        residual_out, iters_out, stream, nullptr, 0);
+    return score_facts_all(e, comm, RetrieveCall(q_fact, batch, stream).out(k, idx_out, score_out)
+                                        .filter(filter_dev, filter_ld_words, true), workspace, workspace_bytes);
 }
 
 }  // extern "C"
 
 namespace {
 
-// phase B of a row shard (hrag_shard_retrieve_filtered / hrag_shard_retrieve_scoped)
-hrag_status shard_retrieve(hrag_engine *e, const hrag_comm *comm, const uint16_t *q_pass, int32_t batch,
-                           const int32_t *kept_idx, const float *kept_score, const int32_t *kept_count, int32_t kf,
-                           int32_t link_top_k, float damping, float passage_node_weight, int32_t ppr_iters,
-                           int32_t ppr_max_iters, float ppr_tol, int32_t k, int32_t n_groups, void *state0, void *state1,
-                           void *state2, void *workspace, int64_t workspace_bytes, int32_t *doc_idx_out,
-                           float *doc_score_out, int32_t *flags_out, float *residual_out, int32_t *iters_out,
-                           hrag_stream stream, const uint32_t *filter_dev, int64_t filter_ld_words, bool scoped) {
+// what a row-shard retrieve call brings besides the record: exchange groups, the three state buffers, the workspace
+struct ShardBuffers {
+    int32_t n_groups;
+    void *state[3];
+    void *workspace;
+    int64_t workspace_bytes;
+};
+
+// phase B of a row shard (hrag_shard_retrieve and its filtered / scoped forms)
+hrag_status shard_retrieve(hrag_engine *e, const hrag_comm *comm, const RetrieveCall &c, const ShardBuffers &b) {
+    const int32_t batch = c.batch, k = c.k;
+    hrag_stream stream = c.stream;
+    void *const *bufs = b.state;
     HRAG_TRY(check_comm(comm));
-    HRAG_REQUIRE(e && q_pass && kept_idx && kept_score && kept_count && state0 && state1 && state2 && workspace &&
-                 doc_idx_out && doc_score_out && flags_out, "NULL argument");
-    HRAG_REQUIRE(!scoped || filter_dev, "NULL filter (the scoped call needs the allowed passages)");
-    HRAG_REQUIRE(workspace_bytes >= hrag_shard_workspace_bytes(e, comm->world, batch, k), "workspace too small: %lld < %lld bytes",
-                 (long long)workspace_bytes, (long long)hrag_shard_workspace_bytes(e, comm->world, batch, k));
+    HRAG_REQUIRE(e && c.q_pass && c.kept_idx && c.kept_score && c.kept_count && bufs[0] && bufs[1] && bufs[2] && b.workspace &&
+                 c.doc_idx && c.doc_score && c.flags, "NULL argument");
+    HRAG_REQUIRE(!c.scoped || c.words, "NULL filter (the scoped call needs the allowed passages)");
+    HRAG_REQUIRE(b.workspace_bytes >= hrag_shard_workspace_bytes(e, comm->world, batch, k), "workspace too small: %lld < %lld bytes",
+                 (long long)b.workspace_bytes, (long long)hrag_shard_workspace_bytes(e, comm->world, batch, k));
     const int32_t w = comm->world;
     hipStream_t s = (hipStream_t)stream;
     hrag_shard_layout lay;
-    HRAG_TRY(hrag_shard_layout_query(e, batch, n_groups, &lay));
+    HRAG_TRY(hrag_shard_layout_query(e, batch, b.n_groups, &lay));
     if (w > 1) {
         HRAG_REQUIRE(lay.own_offset == (int64_t)comm->rank * lay.own_bytes,
                      "the state exchange needs equal-sized row shards in rank order (own_offset %lld != rank %d * own_bytes %lld)",
@@ -237,7 +227,7 @@ hrag_status shard_retrieve(hrag_engine *e, const hrag_comm *comm, const uint16_t
         HRAG_REQUIRE((int64_t)w * lay.own_bytes + (int64_t)lay.slabs_per_group * 128 <= lay.group_bytes,
                      "the state exchange would overwrite the zero row: the shards do not tile [0, V)");
     }
-    Carver ws{static_cast<char *>(workspace), workspace_bytes};
+    Carver ws{static_cast<char *>(b.workspace), b.workspace_bytes};
     float *mn = ws.take<float>(batch), *mx = ws.take<float>(batch), *zmax = ws.take<float>(batch), *est = ws.take<float>(batch);
     double *mass = ws.take<double>(2 * (int64_t)batch);
     int32_t *sv = ws.take<int32_t>((int64_t)batch * HRAG_SEED_STRIDE);
@@ -257,32 +247,31 @@ hrag_status shard_retrieve(hrag_engine *e, const hrag_comm *comm, const uint16_t
     HRAG_HIP_TRY(hipMemsetAsync(sc, 0, (size_t)batch * sizeof(int32_t), s));
     HRAG_HIP_TRY(hipMemsetAsync(flags, 0, (size_t)batch * sizeof(int32_t), s));
     // ---- similarity of the owned passages, the reset vector's statistics over ALL shards
-    if (scoped) {
+    if (c.scoped) {
         // "seeds" scope: the min / max over the ALLOWED passages of every shard (zmax / est are free until the prior
         // statistics), the owned rows rewritten with them, then the min / max of the rewritten rows over every shard --
         // what hrag_retrieve_scoped's launch_row_minmax sees after its masked prior
-        HRAG_TRY(hrag_shard_passage_scores_scoped(e, q_pass, batch, zmax, est, stream, filter_dev, filter_ld_words));
+        HRAG_TRY(hrag_shard_passage_scores_scoped(e, c.q_pass, batch, zmax, est, stream, c.words, c.ld_words));
         HRAG_TRY(reduce(zmax, batch, HRAG_COMM_F32, HRAG_COMM_MIN));
         HRAG_TRY(reduce(est, batch, HRAG_COMM_F32, HRAG_COMM_MAX));
-        HRAG_TRY(hrag_shard_mask_prior(e, zmax, est, batch, mn, mx, stream, filter_dev, filter_ld_words));
+        HRAG_TRY(hrag_shard_mask_prior(e, zmax, est, batch, mn, mx, stream, c.words, c.ld_words));
     } else {
-        HRAG_TRY(hrag_shard_passage_scores(e, q_pass, batch, mn, mx, stream));
+        HRAG_TRY(hrag_shard_passage_scores(e, c.q_pass, batch, mn, mx, stream));
     }
     HRAG_TRY(reduce(mn, batch, HRAG_COMM_F32, HRAG_COMM_MIN));
     HRAG_TRY(reduce(mx, batch, HRAG_COMM_F32, HRAG_COMM_MAX));
-    HRAG_TRY(hrag_stage_seeds(e, kept_idx, kept_score, kept_count, kf, link_top_k, batch, sv, sw, sc, flags, stream));
-    HRAG_TRY(hrag_shard_prior_stats(e, mn, mx, passage_node_weight, flags, batch, zmax, mass, stream));
+    HRAG_TRY(hrag_stage_seeds(e, c.kept_idx, c.kept_score, c.kept_count, c.kf, c.link_top_k, batch, sv, sw, sc, flags, stream));
+    HRAG_TRY(hrag_shard_prior_stats(e, mn, mx, c.passage_node_weight, flags, batch, zmax, mass, stream));
     HRAG_TRY(reduce(zmax, batch, HRAG_COMM_F32, HRAG_COMM_MAX));
     HRAG_TRY(reduce(mass, 2 * (int64_t)batch, HRAG_COMM_F64, HRAG_COMM_SUM));
-    const bool contract = ppr_tol > 0.f;
+    const bool contract = c.ppr_tol > 0.f;
     int32_t n_steps = 0;
-    HRAG_TRY(hrag_shard_ppr_begin(e, mn, mx, zmax, mass, passage_node_weight, sv, sw, sc, flags, batch, damping, ppr_iters,
-                                  std::max(ppr_max_iters, ppr_iters), contract ? ppr_tol : 0.f, lay.n_groups, state0, state1,
-                                  state2, &n_steps, stream));
-    if (!contract) n_steps = ppr_iters;
+    HRAG_TRY(hrag_shard_ppr_begin(e, mn, mx, zmax, mass, c.passage_node_weight, sv, sw, sc, flags, batch, c.damping,
+                                  c.ppr_iters, std::max(c.ppr_max_iters, c.ppr_iters), contract ? c.ppr_tol : 0.f, lay.n_groups,
+                                  bufs[0], bufs[1], bufs[2], &n_steps, stream));
+    if (!contract) n_steps = c.ppr_iters;
     // ---- the sweeps: group g's exchange overlaps with the sweeps of the other groups; a sweep of group g only waits for
     //      group g's previous exchange
-    void *bufs[3] = {state0, state1, state2};
     std::vector<char> pending((size_t)lay.n_groups, 0);
     // an error return between exchange_begin and exchange_wait must not leave the host's collective handles open (the
     // next call on the same hrag_comm would start from a half-finished exchange): wait for what was begun, ignore the rc
@@ -337,14 +326,14 @@ hrag_status shard_retrieve(hrag_engine *e, const hrag_comm *comm, const uint16_t
         HRAG_TRY(reduce(est, batch, HRAG_COMM_F32, HRAG_COMM_MAX));
         HRAG_TRY(hrag_shard_ppr_est(e, est, 1, stream));
     }
-    HRAG_TRY(hrag_shard_finish_filtered(e, mn, mx, flags, batch, k, lidx, lval, contract ? residual_out : nullptr,
-                                        contract ? iters_out : nullptr, stream, filter_dev, filter_ld_words));
-    HRAG_TRY(merge_topk(comm, lidx, lval, batch, k, ws, nullptr, nullptr, doc_idx_out, doc_score_out, s));
+    HRAG_TRY(hrag_shard_finish_filtered(e, mn, mx, flags, batch, k, lidx, lval, contract ? c.residual : nullptr,
+                                        contract ? c.iters : nullptr, stream, c.words, c.ld_words));
+    HRAG_TRY(merge_topk(comm, lidx, lval, batch, k, ws, nullptr, nullptr, c.doc_idx, c.doc_score, s));
     // a saturated value is raised on the shard that owns the row: every shard reports it (never clipped scores unnoticed)
     hipLaunchKernelGGL(sat_extract_kernel, dim3((unsigned)ceil_div(batch, 256)), dim3(256), 0, s, flags, batch, sat);
     HRAG_LAUNCH_CHECK();
     HRAG_TRY(reduce(sat, batch, HRAG_COMM_I32, HRAG_COMM_MAX));
-    hipLaunchKernelGGL(sat_merge_kernel, dim3((unsigned)ceil_div(batch, 256)), dim3(256), 0, s, flags, sat, batch, flags_out);
+    hipLaunchKernelGGL(sat_merge_kernel, dim3((unsigned)ceil_div(batch, 256)), dim3(256), 0, s, flags, sat, batch, c.flags);
     HRAG_LAUNCH_CHECK();
     return HRAG_OK;
 }
@@ -352,6 +341,20 @@ hrag_status shard_retrieve(hrag_engine *e, const hrag_comm *comm, const uint16_t
 }  // namespace
 
 extern "C" {
+
+hrag_status hrag_shard_retrieve(hrag_engine *e, const hrag_comm *comm, const uint16_t *q_pass, int32_t batch,
+                                const int32_t *kept_idx, const float *kept_score, const int32_t *kept_count, int32_t kf,
+                                int32_t link_top_k, float damping, float passage_node_weight, int32_t ppr_iters,
+                                int32_t ppr_max_iters, float ppr_tol, int32_t k, int32_t n_groups, void *state0, void *state1,
+                                void *state2, void *workspace, int64_t workspace_bytes, int32_t *doc_idx_out,
+                                float *doc_score_out, int32_t *flags_out, float *residual_out, int32_t *iters_out,
+                                hrag_stream stream) {
+    return shard_retrieve(e, comm,
+                          RetrieveCall(q_pass, batch, stream).facts(kept_idx, kept_score, kept_count, kf, link_top_k)
+                              .ppr(damping, passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol)
+                              .out(k, doc_idx_out, doc_score_out, flags_out, residual_out, iters_out),
+                          {n_groups, {state0, state1, state2}, workspace, workspace_bytes});
+}
 
 hrag_status hrag_shard_retrieve_filtered(hrag_engine *e, const hrag_comm *comm, const uint16_t *q_pass, int32_t batch,
                                          const int32_t *kept_idx, const float *kept_score, const int32_t *kept_count,
@@ -361,10 +364,12 @@ hrag_status hrag_shard_retrieve_filtered(hrag_engine *e, const hrag_comm *comm, 
                                          int32_t *doc_idx_out, float *doc_score_out, int32_t *flags_out,
                                          float *residual_out, int32_t *iters_out, hrag_stream stream,
                                          const uint32_t *filter_dev, int64_t filter_ld_words) {
-    return shard_retrieve(e, comm, q_pass, batch, kept_idx, kept_score, kept_count, kf, link_top_k, damping,
-                          passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol, k, n_groups, state0, state1, state2,
-                          workspace, workspace_bytes, doc_idx_out, doc_score_out, flags_out, residual_out, iters_out,
-                          stream, filter_dev, filter_ld_words, false);
+    return shard_retrieve(e, comm,
+                          RetrieveCall(q_pass, batch, stream).facts(kept_idx, kept_score, kept_count, kf, link_top_k)
+                              .ppr(damping, passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol)
+                              .out(k, doc_idx_out, doc_score_out, flags_out, residual_out, iters_out)
+                              .filter(filter_dev, filter_ld_words),
+                          {n_groups, {state0, state1, state2}, workspace, workspace_bytes});
 }
 
 hrag_status hrag_shard_retrieve_scoped(hrag_engine *e, const hrag_comm *comm, const uint16_t *q_pass, int32_t batch,
@@ -375,10 +380,12 @@ hrag_status hrag_shard_retrieve_scoped(hrag_engine *e, const hrag_comm *comm, co
                                          int32_t *doc_idx_out, float *doc_score_out, int32_t *flags_out,
                                          float *residual_out, int32_t *iters_out, hrag_stream stream,
                                          const uint32_t *filter_dev, int64_t filter_ld_words) {
-    return shard_retrieve(e, comm, q_pass, batch, kept_idx, kept_score, kept_count, kf, link_top_k, damping,
-                          passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol, k, n_groups, state0, state1, state2,
-                          workspace, workspace_bytes, doc_idx_out, doc_score_out, flags_out, residual_out, iters_out,
-                          stream, filter_dev, filter_ld_words, true);
+    return shard_retrieve(e, comm,
+                          RetrieveCall(q_pass, batch, stream).facts(kept_idx, kept_score, kept_count, kf, link_top_k)
+                              .ppr(damping, passage_node_weight, ppr_iters, ppr_max_iters, ppr_tol)
+                              .out(k, doc_idx_out, doc_score_out, flags_out, residual_out, iters_out)
+                              .filter(filter_dev, filter_ld_words, true),
+                          {n_groups, {state0, state1, state2}, workspace, workspace_bytes});
 }
 
 }  // extern "C"

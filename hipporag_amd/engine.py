@@ -661,50 +661,58 @@ class HippoRAGEngine:
         scores (group_score = doc_score) and each group's best passage (best_doc_idx = doc_idx); composes with both.
         group_hits=m (with group_agg; hrag_last_group_hits right behind the grouped call): hit_idx / hit_score [B, k, m],
         the m best allowed passages of each ranked group with their own scores; every other output is unchanged."""
+        return self._retrieve("hrag_retrieve", q_pass, (kept_idx, kept_score, kept_count),
+                              (link_top_k, damping, passage_node_weight, ppr_iters, max(ppr_max_iters, ppr_iters), ppr_tol), k,
+                              want_residual or ppr_tol > 0, doc_filter=doc_filter, filter_scope=filter_scope,
+                              group_agg=group_agg, group_hits=group_hits)
+
+    def _retrieve(self, base, source, kept, ppr, k, report, *, doc_filter, filter_scope, group_agg, group_hits):
+        """The one binding behind retrieve / retrieve_scored / dense_retrieve (base = "hrag_retrieve", "hrag_retrieve_scored"
+        or "hrag_dense_retrieve"): the scope / agg / hits checks, inputs and outputs on the device, the filter words, the
+        argument list from its named pieces, and the exported function that serves this combination -- base itself, or base +
+        "_filtered" / "_scoped" / "_grouped".  kept (idx, score, count) and ppr (link_top_k .. ppr_tol, in the ABI's order)
+        are None / () for the dense call, which has no flags either; report: allocate residual / iters_used."""
         torch = _torch()
         scoped = check_filter_scope(filter_scope, doc_filter)
         agg = check_group_agg(group_agg)
         hits = check_group_hits(group_hits, group_agg)
-        q = self._q(q_pass)
-        b = q.shape[0]
-        kept_idx = kept_idx.to(self.device, torch.int32).contiguous()
-        kept_score = kept_score.to(self.device, torch.float32).contiguous()
-        kept_count = kept_count.to(self.device, torch.int32).contiguous()
-        kf = kept_idx.shape[1]
-        if kept_idx.shape != (b, kf) or kept_score.shape != (b, kf) or kept_count.shape != (b,):
-            raise ValueError("kept_idx / kept_score must be [B, kf], kept_count [B]")
-        idx = self._empty((b, k), torch.int32)
-        sc = self._empty((b, k), torch.float32)
-        flags = self._empty((b,), torch.int32)
-        resid = self._empty((b,), torch.float32) if want_residual or ppr_tol > 0 else None
-        used = self._empty((b,), torch.int32) if resid is not None else None
-        args = (self._handle, q.data_ptr(), b, kept_idx.data_ptr(), kept_score.data_ptr(), kept_count.data_ptr(), kf,
-                link_top_k, damping, passage_node_weight, ppr_iters, max(ppr_max_iters, ppr_iters), ppr_tol, k,
-                idx.data_ptr(), sc.data_ptr(), flags.data_ptr(), resid.data_ptr() if resid is not None else None,
-                used.data_ptr() if used is not None else None, _stream())
-        if agg is not None:
-            return self._grouped(self._lib.hrag_retrieve_grouped, args, 14, doc_filter, scoped, agg, b, k,
-                                 RetrieveOutput(idx, sc, flags, resid, used), hits)
-        if doc_filter is None:
-            check(self._lib.hrag_retrieve(*args))
+        if base == "hrag_retrieve_scored":      # raw passage scores fp32 [B, >= Np], any row stride
+            src = source.to(self.device, torch.float32)
+            if src.stride(-1) != 1:
+                src = src.contiguous()
+            head = (self._handle, src.data_ptr(), src.stride(0), src.shape[0])
         else:
-            fw, fld = doc_filter_words(doc_filter, self.n_passages, b, self.device)
-            fn = self._lib.hrag_retrieve_scoped if scoped else self._lib.hrag_retrieve_filtered
-            check(fn(*args, fw.data_ptr(), fld))
-        return RetrieveOutput(idx, sc, flags, resid, used)
-
-    def _grouped(self, fn, args, doc_at, doc_filter, scoped, agg, b, k, out, hits=None):
-        """A grouped call: `args` of the ungrouped form with the two ungrouped outputs (at doc_at) left out.  hits: the
-        follow-up hrag_last_group_hits over the rows this call leaves, with its group ids and its filter."""
-        torch = _torch()
+            src = self._q(source)
+            head = (self._handle, src.data_ptr(), src.shape[0])
+        b = src.shape[0]
+        out = RetrieveOutput(self._empty((b, k), torch.int32), self._empty((b, k), torch.float32), None)
+        tail = (_stream(),)
+        if kept is not None:
+            kept_idx = kept[0].to(self.device, torch.int32).contiguous()
+            kept_score = kept[1].to(self.device, torch.float32).contiguous()
+            kept_count = kept[2].to(self.device, torch.int32).contiguous()
+            kf = kept_idx.shape[1]
+            if base == "hrag_retrieve" and (kept_idx.shape != (b, kf) or kept_score.shape != (b, kf) or kept_count.shape != (b,)):
+                raise ValueError("kept_idx / kept_score must be [B, kf], kept_count [B]")
+            head += (kept_idx.data_ptr(), kept_score.data_ptr(), kept_count.data_ptr(), kf) + tuple(ppr)
+            out.flags = self._empty((b,), torch.int32)
+            if report:
+                out.residual, out.iters_used = self._empty((b,), torch.float32), self._empty((b,), torch.int32)
+            tail = (out.flags.data_ptr(), out.residual.data_ptr() if report else None,
+                    out.iters_used.data_ptr() if report else None, _stream())
         fw, fld = (None, 0) if doc_filter is None else doc_filter_words(doc_filter, self.n_passages, b, self.device)
-        gi = self._empty((b, k), torch.int32)
-        args = args[:doc_at] + (None, None) + args[doc_at + 2:]
-        check(fn(*args, fw.data_ptr() if fw is not None else None, fld, 1 if scoped else 0, agg, gi.data_ptr(),
-                 out.doc_score.data_ptr(), out.doc_idx.data_ptr()))
-        out.group_idx = gi
-        if hits is not None:
-            out.hit_idx, out.hit_score = self.last_group_hits(gi, hits, fw, fld)
+        docs = (out.doc_idx.data_ptr(), out.doc_score.data_ptr())
+        if agg is not None:     # the ungrouped ranking is left out; its two tensors carry the group scores / representatives
+            out.group_idx = self._empty((b, k), torch.int32)
+            check(getattr(self._lib, base + "_grouped")(
+                *head, k, None, None, *tail, fw.data_ptr() if fw is not None else None, fld, 1 if scoped else 0, agg,
+                out.group_idx.data_ptr(), docs[1], docs[0]))
+            if hits is not None:    # over the rows this call left, with its group ids and its filter
+                out.hit_idx, out.hit_score = self.last_group_hits(out.group_idx, hits, fw, fld)
+        elif fw is None:
+            check(getattr(self._lib, base)(*head, k, *docs, *tail))
+        else:
+            check(getattr(self._lib, base + ("_scoped" if scoped else "_filtered"))(*head, k, *docs, *tail, fw.data_ptr(), fld))
         return out
 
     def last_group_hits(self, group_idx, hits: int, filter_words=None, filter_ld: int = 0):
@@ -769,34 +777,10 @@ class HippoRAGEngine:
                         filter_scope: str = "ranking", group_agg: Optional[str] = None,
                         group_hits: Optional[int] = None) -> RetrieveOutput:
         """retrieve() with the raw passage scores fp32 [B, >= Np] supplied by the caller (hrag_retrieve_scored)."""
-        torch = _torch()
-        scoped = check_filter_scope(filter_scope, doc_filter)
-        agg = check_group_agg(group_agg)
-        hits = check_group_hits(group_hits, group_agg)
-        sc_in = pass_scores.to(self.device, torch.float32)
-        if sc_in.stride(-1) != 1:
-            sc_in = sc_in.contiguous()
-        b = sc_in.shape[0]
-        kept_idx = kept_idx.to(self.device, torch.int32).contiguous()
-        kept_score = kept_score.to(self.device, torch.float32).contiguous()
-        kept_count = kept_count.to(self.device, torch.int32).contiguous()
-        kf = kept_idx.shape[1]
-        idx, sc = self._empty((b, k), torch.int32), self._empty((b, k), torch.float32)
-        flags, resid, used = self._empty((b,), torch.int32), self._empty((b,), torch.float32), self._empty((b,), torch.int32)
-        args = (self._handle, sc_in.data_ptr(), sc_in.stride(0), b, kept_idx.data_ptr(), kept_score.data_ptr(),
-                kept_count.data_ptr(), kf, link_top_k, damping, passage_node_weight, ppr_iters,
-                max(ppr_max_iters, ppr_iters), ppr_tol, k, idx.data_ptr(), sc.data_ptr(), flags.data_ptr(), resid.data_ptr(),
-                used.data_ptr(), _stream())
-        if agg is not None:
-            return self._grouped(self._lib.hrag_retrieve_scored_grouped, args, 15, doc_filter, scoped, agg, b, k,
-                                 RetrieveOutput(idx, sc, flags, resid, used), hits)
-        if doc_filter is None:
-            check(self._lib.hrag_retrieve_scored(*args))
-        else:
-            fw, fld = doc_filter_words(doc_filter, self.n_passages, b, self.device)
-            fn = self._lib.hrag_retrieve_scored_scoped if scoped else self._lib.hrag_retrieve_scored_filtered
-            check(fn(*args, fw.data_ptr(), fld))
-        return RetrieveOutput(idx, sc, flags, resid, used)
+        return self._retrieve("hrag_retrieve_scored", pass_scores, (kept_idx, kept_score, kept_count),
+                              (link_top_k, damping, passage_node_weight, ppr_iters, max(ppr_max_iters, ppr_iters), ppr_tol), k,
+                              True, doc_filter=doc_filter, filter_scope=filter_scope, group_agg=group_agg,
+                              group_hits=group_hits)
 
     def retrieve_converged(self, q_pass, kept_idx, kept_score, kept_count, *, damping: float = 0.5,
                            ppr_iters: int = 20, ppr_tol: float = 1.5e-6, ppr_max_iters: int = 400,
@@ -852,28 +836,11 @@ class HippoRAGEngine:
         """DPR top-k; filter_scope="seeds": normalised over the allowed passages (hrag_dense_retrieve_scoped).
         group_agg="max" | "sum": (group ids, group scores, best passage of each group) over the normalised scores
         (hrag_dense_retrieve_grouped); group_hits=m adds two entries, (hit_idx, hit_score) [B, k, m] over those scores."""
-        torch = _torch()
-        scoped = check_filter_scope(filter_scope, doc_filter)
-        agg = check_group_agg(group_agg)
-        hits = check_group_hits(group_hits, group_agg)
-        q = self._q(q_pass)
-        b = q.shape[0]
-        idx = self._empty((b, k), torch.int32)
-        sc = self._empty((b, k), torch.float32)
-        if agg is not None:
-            out = self._grouped(self._lib.hrag_dense_retrieve_grouped, (self._handle, q.data_ptr(), b, k, None, None, _stream()),
-                                4, doc_filter, scoped, agg, b, k, RetrieveOutput(idx, sc, None), hits)
-            if hits is not None:
-                return out.group_idx, out.doc_score, out.doc_idx, out.hit_idx, out.hit_score
-            return out.group_idx, out.doc_score, out.doc_idx
-        if doc_filter is None:
-            check(self._lib.hrag_dense_retrieve(self._handle, q.data_ptr(), b, k, idx.data_ptr(),
-                                                sc.data_ptr(), _stream()))
-        else:
-            fw, fld = doc_filter_words(doc_filter, self.n_passages, b, self.device)
-            fn = self._lib.hrag_dense_retrieve_scoped if scoped else self._lib.hrag_dense_retrieve_filtered
-            check(fn(self._handle, q.data_ptr(), b, k, idx.data_ptr(), sc.data_ptr(), _stream(), fw.data_ptr(), fld))
-        return idx, sc
+        out = self._retrieve("hrag_dense_retrieve", q_pass, None, (), k, False, doc_filter=doc_filter,
+                             filter_scope=filter_scope, group_agg=group_agg, group_hits=group_hits)
+        if out.group_idx is None:
+            return out.doc_idx, out.doc_score
+        return (out.group_idx, out.doc_score, out.doc_idx) + (() if out.hit_idx is None else (out.hit_idx, out.hit_score))
 
     # ------------------------------------------------------------------ seams
     def sim_scores(self, which: str, q):
