@@ -143,6 +143,11 @@ SIGNATURES = {
     "hrag_fuse_workspace_bytes": (C.c_int64, [_I32, _I64, _I32, _I32, _I32]),
     "hrag_last_fused": (C.c_int, [_P, _I32, _P, _I32, _P, _I32, _I32, _I32, _I32, _P, _I64, _I32, _P, _P, _P, _P, _P, _P,
                                   C.c_size_t, _P]),
+    "hrag_gram_rows": (C.c_int, [_P, _I64, _I32, _I32, _I32, _P, _I32, _I32, _P, _I64, _P]),
+    "hrag_mmr_rows": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _I32, _F32, _I32, _P, _P, _P, _P, _P]),
+    "hrag_mmr_workspace_bytes": (C.c_int64, [_I32, _I32]),
+    "hrag_mmr": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _F32, _I32, _P, _P, _P, _P, C.c_size_t, _P]),
+    "hrag_mmr_sel": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _F32, _I32, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "hrag_ppr_sweeps": (C.c_int, [_P, _I32, _I32, _F32, _I32, _P]),
     "hrag_ppr_layout": (C.c_int, [_P, _I32, C.POINTER(_I32), C.POINTER(_I32)]),
     "hrag_row_minmax": (C.c_int, [_P, _I32, _I64, _I64, _P, _P, _P]),

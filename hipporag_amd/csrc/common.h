@@ -555,6 +555,19 @@ hrag_status launch_rrf_rows(const int32_t *list_idx, int32_t batch, int32_t dept
 hrag_status launch_expand_filter(const uint32_t *src, int64_t src_ld, int64_t words, const int32_t *member_ptr,
                                  int32_t batch, int32_t n_fused, uint32_t *dst, hipStream_t s);
 
+// mmr.hip : diversified retrieval (include/hrag.h, hrag_gram_rows / hrag_mmr_rows).  launch_gram_rows: out fp32
+// [batch][c][ld] = the gathered Gram of each query's candidate rows cand int32 [batch][c] (an id outside [0, rows): a zero
+// row), element [i][j], i <= j, the sim_gemm chain of row cand[i] against row cand[j] as the query (split != 0: the query
+// side reads the thirds of the stored [hi | lo | hi] row as (0, 2, 1); that layout is FP16 halves, as hrag_split_f32 writes
+// it: dtype HRAG_FP16), mirrored to [j][i]; the columns c .. ld untouched
+hrag_status launch_gram_rows(const uint16_t *emb, int64_t rows, int32_t kdim, int32_t dtype, int32_t split,
+                             const int32_t *cand, int32_t batch, int32_t c, float *out, int64_t ld, hipStream_t s);
+// the greedy MMR selection of k of the c candidates over sim fp32 [batch][c][ld]; n_ids > 0: an id >= n_ids is an empty
+// slot like a negative one; sel_out may be NULL
+hrag_status launch_mmr_rows(const float *score, const int32_t *cand, const float *sim, int64_t ld, int32_t batch, int32_t c,
+                            int32_t k, float lambda, int32_t normalize, int64_t n_ids, int32_t *sel_out, int32_t *idx_out,
+                            float *score_out, float *value_out, hipStream_t s);
+
 // knn.hip : fp32 rows -> the 3 * dim bf16 layout of HRAG_F32_SPLIT engines ([hi | lo | hi]; queries [hi | hi | lo])
 hrag_status launch_split3(const float *x, int64_t rows, int32_t dim, int32_t as_query, uint16_t *out, hipStream_t s,
                           int32_t normalize = 0);

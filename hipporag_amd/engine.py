@@ -58,6 +58,8 @@ FILTER_SCOPES = ("ranking", "seeds")
 GROUP_AGGS = {"max": 0, "sum": 1}      # HRAG_GROUP_MAX / HRAG_GROUP_SUM
 GROUP_HITS_MAX = 64                    # HRAG_GROUP_HITS_MAX
 FUSE_MODES = {"sum": 0, "max": 1, "rrf": 2}     # HRAG_FUSE_SUM / HRAG_FUSE_MAX / HRAG_FUSE_RRF
+MMR_MAX_CANDIDATES = 1024              # HRAG_MMR_MAX_CANDIDATES
+MMR_WORKSPACE_CAP = 256 << 20          # bytes of Gram workspace one hrag_mmr call may take: larger batches go in slices
 
 
 def check_group_agg(group_agg) -> Optional[int]:
@@ -118,6 +120,46 @@ def check_fuse(fuse, member_ptr, batch: int, weights=None, rrf_c: int = 60, rrf_
             raise ValueError(f"rrf_depth={rrf_depth}: outside [1, {depth_max if depth_max is not None else 'min(max_topk, n_passages)'}]")
         c, depth = int(rrf_c), int(rrf_depth)
     return FUSE_MODES[fuse], np.ascontiguousarray(mp, dtype=np.int32), w, c, depth
+
+
+def check_mmr(lam, k, c) -> float:
+    """The arguments of an MMR call (include/hrag.h, diversified retrieval) as the library takes them: lambda a real number
+    in [0, 1] (not NaN, not a bool), ints 1 <= k <= c <= MMR_MAX_CANDIDATES.  Returns lambda as a float."""
+    if isinstance(lam, bool) or not isinstance(lam, (int, float, np.integer, np.floating)):
+        raise ValueError(f"mmr_lambda={lam!r}: a number in [0, 1] expected")
+    lam = float(lam)
+    if not 0.0 <= lam <= 1.0:           # (False for NaN)
+        raise ValueError(f"mmr_lambda={lam}: outside [0, 1]")
+    for name, v in (("k", k), ("mmr_candidates", c)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name}={v!r}: an int expected")
+    if not 1 <= int(c) <= MMR_MAX_CANDIDATES:
+        raise ValueError(f"mmr_candidates={c}: outside [1, {MMR_MAX_CANDIDATES}]")
+    if not 1 <= int(k) <= int(c):
+        raise ValueError(f"k={k}: outside [1, mmr_candidates={c}]")
+    return lam
+
+
+def mmr_plan(mmr_lambda, mmr_candidates, k: int):
+    """None without mmr_lambda (mmr_candidates then has to be None too), else (lambda, c): the call ranks
+    c = max(mmr_candidates, k) entries (mmr_candidates None: k) and MMR picks k of them."""
+    if mmr_lambda is None:
+        if mmr_candidates is not None:
+            raise ValueError("mmr_candidates needs mmr_lambda")
+        return None
+    c = k if mmr_candidates is None else mmr_candidates
+    if isinstance(c, bool) or not isinstance(c, (int, np.integer)):
+        raise ValueError(f"mmr_candidates={c!r}: an int expected")
+    c = max(int(c), int(k))
+    return check_mmr(mmr_lambda, k, c), c
+
+
+def refuse_mmr(who: str, kw: dict) -> None:
+    """The callers that do not serve MMR name the argument they refuse."""
+    for name in ("mmr_lambda", "mmr_candidates"):
+        if kw.get(name) is not None:
+            raise ValueError(f"{who} does not serve {name}: MMR reads the passage embeddings of one unsharded engine after a "
+                             "plain ranking -- use HippoRAGEngine.retrieve(mmr_lambda=...) or HippoRAGEngine.mmr")
 
 
 def group_table_csr(group_of, n_groups: int):
@@ -235,6 +277,8 @@ class RetrieveOutput:
     hit_idx: "object" = None     # group_hits=m: torch int32 [B, k, m], the m best allowed passages of each ranked group, best
                                  # first (entry 0 is the representative), -1 beyond the group's allowed members
     hit_score: "object" = None   # torch fp32 [B, k, m]: each hit's own passage score (0 where hit_idx is -1)
+    mmr_value: "object" = None   # mmr_lambda=: torch fp32 [B, k], the MMR value of each pick; doc_idx / doc_score then hold
+                                 # the picks in MMR order with their own retrieval scores
 
     @property
     def group_score(self):       # the grouped call's names for the two tensors above
@@ -339,6 +383,8 @@ class PendingRetrieve:
                 out.group_idx[rt] = o2.group_idx
             if out.hit_idx is not None:
                 out.hit_idx[rt], out.hit_score[rt] = o2.hit_idx, o2.hit_score
+            if out.mmr_value is not None:
+                out.mmr_value[rt] = o2.mmr_value
             out.flags[rt], out.residual[rt], out.iters_used[rt] = o2.flags, o2.residual, o2.iters_used
             if self.want_all_scores:
                 out.all_scores[rt] = o2.all_scores
@@ -538,7 +584,7 @@ class HippoRAGEngine:
         w._handle = C.c_void_p(0)
         w._workspaces = []
         w._parent = root
-        w._fuse_ws = w._fuse_host = None         # last_fused: a scratch buffer of its own
+        w._fuse_ws = w._fuse_host = w._mmr_ws = None         # last_fused / mmr: scratch buffers of its own
         with _torch().cuda.device(root.device):
             check(root._lib.hrag_workspace_create(root._handle, C.byref(w._handle)))
         if not hasattr(root, "_workspaces"):
@@ -649,7 +695,8 @@ class HippoRAGEngine:
                  damping: float = 0.5, passage_node_weight: float = 0.05, ppr_iters: int = 20,
                  k: int = 200, ppr_tol: float = 0.0, ppr_max_iters: int = 0,
                  want_residual: bool = True, doc_filter=None, filter_scope: str = "ranking",
-                 group_agg: Optional[str] = None, group_hits: Optional[int] = None) -> RetrieveOutput:
+                 group_agg: Optional[str] = None, group_hits: Optional[int] = None,
+                 mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None) -> RetrieveOutput:
         """Phase B: seeds + passage prior + PPR + ranking (DPR ranking where kept_count == 0).
         ppr_tol / ppr_max_iters: the convergence contract of include/hrag.h (0 = exactly ppr_iters sweeps);
         the output carries the per-query residual and the sweeps that ran.
@@ -660,19 +707,26 @@ class HippoRAGEngine:
         group_agg="max" | "sum" (after set_passage_groups; hrag_retrieve_grouped): the k best GROUPS -- group_idx, their
         scores (group_score = doc_score) and each group's best passage (best_doc_idx = doc_idx); composes with both.
         group_hits=m (with group_agg; hrag_last_group_hits right behind the grouped call): hit_idx / hit_score [B, k, m],
-        the m best allowed passages of each ranked group with their own scores; every other output is unchanged."""
+        the m best allowed passages of each ranked group with their own scores; every other output is unchanged.
+        mmr_lambda in [0, 1] (include/hrag.h, diversified retrieval; hrag_mmr behind the ranking): the call ranks
+        c = max(mmr_candidates, k) <= min(max_topk, 1024) entries (mmr_candidates None: k) and returns the k MMR picks among
+        them in doc_idx / doc_score (their own scores, MMR order) and mmr_value; relevance is the min-max of the candidates'
+        scores.  With group_agg the candidates are the groups' best passages with the group scores, and group_idx / the
+        hits follow the picks.  None: the call and its outputs are exactly the plain ones."""
         return self._retrieve("hrag_retrieve", q_pass, (kept_idx, kept_score, kept_count),
                               (link_top_k, damping, passage_node_weight, ppr_iters, max(ppr_max_iters, ppr_iters), ppr_tol), k,
                               want_residual or ppr_tol > 0, doc_filter=doc_filter, filter_scope=filter_scope,
-                              group_agg=group_agg, group_hits=group_hits)
+                              group_agg=group_agg, group_hits=group_hits, mmr=mmr_plan(mmr_lambda, mmr_candidates, k))
 
-    def _retrieve(self, base, source, kept, ppr, k, report, *, doc_filter, filter_scope, group_agg, group_hits):
+    def _retrieve(self, base, source, kept, ppr, k, report, *, doc_filter, filter_scope, group_agg, group_hits, mmr=None):
         """The one binding behind retrieve / retrieve_scored / dense_retrieve (base = "hrag_retrieve", "hrag_retrieve_scored"
         or "hrag_dense_retrieve"): the scope / agg / hits checks, inputs and outputs on the device, the filter words, the
         argument list from its named pieces, and the exported function that serves this combination -- base itself, or base +
         "_filtered" / "_scoped" / "_grouped".  kept (idx, score, count) and ppr (link_top_k .. ppr_tol, in the ABI's order)
-        are None / () for the dense call, which has no flags either; report: allocate residual / iters_used."""
+        are None / () for the dense call, which has no flags either; report: allocate residual / iters_used.
+        mmr: None or mmr_plan's (lambda, c): c entries are ranked and _mmr_picks keeps k of them."""
         torch = _torch()
+        k_out, k = k, (k if mmr is None else mmr[1])
         scoped = check_filter_scope(filter_scope, doc_filter)
         agg = check_group_agg(group_agg)
         hits = check_group_hits(group_hits, group_agg)
@@ -707,13 +761,63 @@ class HippoRAGEngine:
             check(getattr(self._lib, base + "_grouped")(
                 *head, k, None, None, *tail, fw.data_ptr() if fw is not None else None, fld, 1 if scoped else 0, agg,
                 out.group_idx.data_ptr(), docs[1], docs[0]))
+            if mmr is not None:
+                self._mmr_picks(out, k_out, mmr[0])
             if hits is not None:    # over the rows this call left, with its group ids and its filter
                 out.hit_idx, out.hit_score = self.last_group_hits(out.group_idx, hits, fw, fld)
-        elif fw is None:
+            return out
+        if fw is None:
             check(getattr(self._lib, base)(*head, k, *docs, *tail))
         else:
             check(getattr(self._lib, base + ("_scoped" if scoped else "_filtered"))(*head, k, *docs, *tail, fw.data_ptr(), fld))
+        if mmr is not None:
+            self._mmr_picks(out, k_out, mmr[0])
         return out
+
+    def mmr(self, cand_idx, cand_score, k: int, lam: float = 0.5, normalize: bool = True, return_sel: bool = False):
+        """MMR re-ranking (hrag_mmr; include/hrag.h, diversified retrieval) of candidates int32 [B, c] (passage positions in
+        the order a ranking returned them; -1 or an id outside [0, n_passages): an empty slot) with their scores fp32
+        [B, c] over this engine's passage embeddings: (idx int32, score fp32, value fp32), each [B, k] -- the picks in MMR
+        order, their own scores, the MMR value of each pick; -1 / 0 / 0 once the candidates run out.  normalize: relevance is
+        the min-max of the candidates' scores (else the scores as they are).  Everything stays on the device; a batch whose
+        Gram workspace would exceed MMR_WORKSPACE_CAP (or max_batch) is processed in slices.  return_sel: a fourth entry, the
+        slot of each pick in its candidate row int32 [B, k] (hrag_mmr_sel; -1 once the candidates run out)."""
+        torch = _torch()
+        ci = cand_idx.to(self.device, torch.int32).contiguous()
+        cs = cand_score.to(self.device, torch.float32).contiguous()
+        if ci.dim() != 2 or cs.shape != ci.shape:
+            raise ValueError("cand_idx / cand_score must both be [B, c]")
+        b, c = ci.shape
+        lam = check_mmr(lam, k, c)
+        idx = self._empty((b, k), torch.int32)
+        sc = self._empty((b, k), torch.float32)
+        val = self._empty((b, k), torch.float32)
+        sel = self._empty((b, k), torch.int32) if return_sel else None
+        if b == 0:
+            return (idx, sc, val, sel) if return_sel else (idx, sc, val)
+        per = int(self._lib.hrag_mmr_workspace_bytes(1, c))
+        step = max(1, min(b, self.max_batch, MMR_WORKSPACE_CAP // per))
+        need = per * step
+        ws = getattr(self, "_mmr_ws", None)
+        if ws is None or ws.numel() < need or ws.device != self.device:
+            ws = self._mmr_ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        for lo in range(0, b, step):
+            n = min(step, b - lo)
+            check(self._lib.hrag_mmr_sel(self._handle, ci[lo:].data_ptr(), cs[lo:].data_ptr(), n, c, k, lam,
+                                         1 if normalize else 0, sel[lo:].data_ptr() if return_sel else None,
+                                         idx[lo:].data_ptr(), sc[lo:].data_ptr(), val[lo:].data_ptr(), ws.data_ptr(),
+                                         ws.numel(), _stream()))
+        return (idx, sc, val, sel) if return_sel else (idx, sc, val)
+
+    def _mmr_picks(self, out: RetrieveOutput, k: int, lam: float) -> None:
+        """Replace the ranked c entries of `out` by their k MMR picks (doc_idx / doc_score / mmr_value); a grouped call's
+        group_idx follows them by the slot of each pick."""
+        torch = _torch()
+        idx, sc, val, sel = self.mmr(out.doc_idx, out.doc_score, k, lam, return_sel=True)
+        if out.group_idx is not None:
+            gi = torch.gather(out.group_idx, 1, sel.clamp_min(0).long())
+            out.group_idx = torch.where(sel >= 0, gi, torch.full_like(gi, -1))
+        out.doc_idx, out.doc_score, out.mmr_value = idx, sc, val
 
     def last_group_hits(self, group_idx, hits: int, filter_words=None, filter_ld: int = 0):
         """(hit_idx int32, hit_score fp32) [B, k, hits] for group ids int32 [B, k] over the score rows the last retrieve /
@@ -731,7 +835,8 @@ class HippoRAGEngine:
 
     def last_fused(self, member_ptr, *, weights=None, fuse: str = "rrf", rrf_c: int = 60, rrf_depth: Optional[int] = None,
                    k: int = 200, doc_filter=None, group_agg: Optional[str] = None,
-                   group_hits: Optional[int] = None) -> RetrieveOutput:
+                   group_hits: Optional[int] = None, mmr_lambda: Optional[float] = None,
+                   mmr_candidates: Optional[int] = None) -> RetrieveOutput:
         """One ranking per QUESTION from the score rows the last retrieve / retrieve_scored / grouped dense_retrieve on this
         handle left (hrag_last_fused; include/hrag.h, fused retrieval): member_ptr int [Q + 1] cuts those B = member_ptr[-1]
         rows into Q questions of consecutive member rows, weights [B] (None: all 1) weigh them, fuse = "sum" (fp64, in member
@@ -739,8 +844,11 @@ class HippoRAGEngine:
         of the fused rows under doc_filter ([n] for every question or [Q, n]; for "rrf" also the filter of the member
         rankings); with group_agg the grouped ranking instead (group_idx, group_score = doc_score, best_doc_idx = doc_idx)
         and with group_hits=m its hits.  flags / residual / iters_used are None: they belong to the member rows.
-        Afterwards last_doc_scores(Q) returns the fused rows."""
+        Afterwards last_doc_scores(Q) returns the fused rows.  mmr_lambda / mmr_candidates: as on retrieve, over the fused
+        ranking."""
         torch = _torch()
+        mmr = mmr_plan(mmr_lambda, mmr_candidates, k)
+        k_out, k = k, (k if mmr is None else mmr[1])
         agg = check_group_agg(group_agg)
         hits = check_group_hits(group_hits, group_agg)
         b = int(np.asarray(member_ptr).reshape(-1)[-1]) if np.size(member_ptr) else 0
@@ -767,20 +875,23 @@ class HippoRAGEngine:
             idx.data_ptr() if agg is not None else None, ws.data_ptr(), ws.numel(), _stream()))
         out = RetrieveOutput(idx, sc, None)
         out.group_idx = gi
+        if mmr is not None:
+            self._mmr_picks(out, k_out, mmr[0])
         if hits is not None:
-            out.hit_idx, out.hit_score = self.last_group_hits(gi, hits, fw, fld)
+            out.hit_idx, out.hit_score = self.last_group_hits(out.group_idx, hits, fw, fld)
         return out
 
     def retrieve_scored(self, pass_scores, kept_idx, kept_score, kept_count, *, link_top_k: int = 5,
                         damping: float = 0.5, passage_node_weight: float = 0.05, ppr_iters: int = 20, k: int = 200,
                         ppr_tol: float = 0.0, ppr_max_iters: int = 0, doc_filter=None,
                         filter_scope: str = "ranking", group_agg: Optional[str] = None,
-                        group_hits: Optional[int] = None) -> RetrieveOutput:
+                        group_hits: Optional[int] = None, mmr_lambda: Optional[float] = None,
+                        mmr_candidates: Optional[int] = None) -> RetrieveOutput:
         """retrieve() with the raw passage scores fp32 [B, >= Np] supplied by the caller (hrag_retrieve_scored)."""
         return self._retrieve("hrag_retrieve_scored", pass_scores, (kept_idx, kept_score, kept_count),
                               (link_top_k, damping, passage_node_weight, ppr_iters, max(ppr_max_iters, ppr_iters), ppr_tol), k,
                               True, doc_filter=doc_filter, filter_scope=filter_scope, group_agg=group_agg,
-                              group_hits=group_hits)
+                              group_hits=group_hits, mmr=mmr_plan(mmr_lambda, mmr_candidates, k))
 
     def retrieve_converged(self, q_pass, kept_idx, kept_score, kept_count, *, damping: float = 0.5,
                            ppr_iters: int = 20, ppr_tol: float = 1.5e-6, ppr_max_iters: int = 400,
@@ -832,15 +943,19 @@ class HippoRAGEngine:
         return out
 
     def dense_retrieve(self, q_pass, k: int = 200, doc_filter=None, filter_scope: str = "ranking",
-                       group_agg: Optional[str] = None, group_hits: Optional[int] = None):
+                       group_agg: Optional[str] = None, group_hits: Optional[int] = None,
+                       mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None):
         """DPR top-k; filter_scope="seeds": normalised over the allowed passages (hrag_dense_retrieve_scoped).
         group_agg="max" | "sum": (group ids, group scores, best passage of each group) over the normalised scores
-        (hrag_dense_retrieve_grouped); group_hits=m adds two entries, (hit_idx, hit_score) [B, k, m] over those scores."""
+        (hrag_dense_retrieve_grouped); group_hits=m adds two entries, (hit_idx, hit_score) [B, k, m] over those scores.
+        mmr_lambda / mmr_candidates: as on retrieve; the tuple then ends with one more entry, mmr_value [B, k]."""
         out = self._retrieve("hrag_dense_retrieve", q_pass, None, (), k, False, doc_filter=doc_filter,
-                             filter_scope=filter_scope, group_agg=group_agg, group_hits=group_hits)
+                             filter_scope=filter_scope, group_agg=group_agg, group_hits=group_hits,
+                             mmr=mmr_plan(mmr_lambda, mmr_candidates, k))
+        extra = () if out.mmr_value is None else (out.mmr_value,)
         if out.group_idx is None:
-            return out.doc_idx, out.doc_score
-        return (out.group_idx, out.doc_score, out.doc_idx) + (() if out.hit_idx is None else (out.hit_idx, out.hit_score))
+            return (out.doc_idx, out.doc_score) + extra
+        return (out.group_idx, out.doc_score, out.doc_idx) + (() if out.hit_idx is None else (out.hit_idx, out.hit_score)) + extra
 
     # ------------------------------------------------------------------ seams
     def sim_scores(self, which: str, q):
@@ -1087,6 +1202,7 @@ class CapturedPipeline:
     def __init__(self, engine: "HippoRAGEngine", batch: int, *, k_f: int = 5, k: int = 200, **retrieve_kw):
         torch = _torch()
         refuse_group_agg("CapturedPipeline", retrieve_kw)
+        refuse_mmr("CapturedPipeline", retrieve_kw)
         self.engine, self.batch = engine, int(batch)
         dev, dt = engine.device, engine.emb_dtype
         self._qf = torch.zeros((batch, engine.dim), dtype=dt, device=dev)

@@ -192,6 +192,11 @@ class RetrievalConfig:
     group_agg: str = "max"               # a group's score: "max" (its best passage's) or "sum" (of its passages' scores)
     group_hits: Optional[int] = None     # with group_by: the best m passages of each ranked group (1 .. 64) in the entry's
                                          # metadata ("group_hits"); None: the representative only
+    mmr_lambda: Optional[float] = None   # diversified retrieval (include/hrag.h): retrieve() / retrieve_dpr() / rag_qa()
+                                         # re-rank their candidates by Maximal Marginal Relevance with this lambda in [0, 1]
+                                         # (1: relevance only, 0: diversity only after the first pick); None: off
+    mmr_candidates: Optional[int] = None # how many ranked entries MMR picks from: max(this, num_to_retrieve), at most the
+                                         # passages (or groups) there are and at most 1024; None: min(retrieval_top_k, 1024)
 
 
 def identity_rerank_filter(query, candidate_items, candidate_indices, len_after_rerank=None):
@@ -346,6 +351,16 @@ def fuse_rows_host(full, member_ptr, fuse: str, weights=None, rrf_c: int = 60, r
     return out
 
 
+def mmr_pool(mmr_candidates, want: int, available: int):
+    """How many ranked entries MMR picks `want` of: max(mmr_candidates, want), at most the `available` passages (groups);
+    None: want.  A value that is no int is handed on for check_mmr / mmr_plan to refuse."""
+    if mmr_candidates is None:
+        return want
+    if isinstance(mmr_candidates, bool) or not isinstance(mmr_candidates, (int, np.integer)):
+        return mmr_candidates
+    return max(want, min(int(mmr_candidates), int(available)))
+
+
 def masked_minmax_rows(raw, allowed):
     """The dense scores of the "seeds" scope on the host: per row, min_max_normalize over the allowed entries (a zero
     range gives 1), 0 elsewhere."""
@@ -380,7 +395,8 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
                           num_to_retrieve: int, n_passages: int, timers=None, ppr_tol: float = 0.0,
                           ppr_max_iters: int = 0, ppr_base_iters_narrow: Optional[int] = None, doc_filter=None,
                           filter_scope: str = "ranking", group_agg: Optional[str] = None, group_of=None,
-                          group_hits: Optional[int] = None, keep_all_scores: bool = False):
+                          group_hits: Optional[int] = None, keep_all_scores: bool = False,
+                          mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None):
     """The body of retrieve() (HippoRAG.py:459-480), shared by the mirror class below and by
     reference_adapter.attach(): phase A on the device, the recognition-memory filter on the host (rerank_facts
     :1659-1707), phase B on the device, in batches of eng.max_batch queries.  Yields (offset of the batch, [(doc ids,
@@ -407,6 +423,10 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
     GROUPS -- doc ids are each group's best passage, doc scores the group scores, rows.group_idx the group ids.
     group_hits=m (with group_agg): rows.hit_idx / rows.hit_score [b, k, m], the best m allowed passages of every ranked
     group; the engine serves them right behind each batch's grouped call, the host form beyond max_topk.
+    mmr_lambda / mmr_candidates (include/hrag.h, diversified retrieval): each batch ranks max(mmr_candidates, want) entries
+    -- at most the passages (groups) there are; mmr_candidates None: `want`, the mirror passes its retrieval_top_k -- and MMR
+    picks `want` of them on the device (HippoRAGEngine.retrieve(mmr_lambda=)); rows.mmr_value [b, want] is the value of
+    each pick.  At most min(1024, max_topk) candidates.
     keep_all_scores: rows.all_scores is the device tensor of every passage's score of the batch and rows.repeated tells
     whether the contract ran rows again (retrieve_fused: the engine's own score rows are then not the batch's)."""
     import torch
@@ -420,6 +440,14 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
             raise ValueError("group_agg needs group_of (the passage -> group table)")
         want = max(1, min(want, int(np.max(group_of)) + 1))
     k_docs = min(want, eng.max_topk)
+    mmr = None
+    if mmr_lambda is not None or mmr_candidates is not None:
+        from .engine import MMR_MAX_CANDIDATES, mmr_plan
+        mmr = mmr_plan(mmr_lambda, mmr_pool(mmr_candidates, want, n_passages if group_agg is None else
+                                            min(n_passages, int(np.max(group_of)) + 1)), want)
+        if mmr[1] > eng.max_topk:
+            raise ValueError(f"mmr_candidates={mmr[1]} (at least num_to_retrieve) exceeds the engine's max_topk={eng.max_topk}: "
+                             f"MMR picks from one device ranking of at most min({MMR_MAX_CANDIDATES}, max_topk) entries")
     # more documents than the device top-k holds (HippoRAG.py:501-507 slices any prefix of the full ranking): the
     # scores of all passages come back and are ranked here with the library's rule (score desc, larger index first)
     beyond = k_docs < want and hasattr(eng, "last_doc_scores")
@@ -500,6 +528,8 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
             kw["group_agg"] = group_agg
         if group_hits is not None and not beyond:
             kw["group_hits"] = group_hits
+        if mmr is not None:
+            kw.update(mmr_lambda=mmr[0], mmr_candidates=mmr[1])
         if two_halves:
             bt.pending = eng.retrieve_converged_start(*args, **kw)
             o = bt.pending.out
@@ -508,6 +538,8 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
                 bt.copies += (host_copy_async(o.group_idx),)
             if "group_hits" in kw:
                 bt.copies += (host_copy_async(o.hit_idx), host_copy_async(o.hit_score))
+            if mmr is not None:
+                bt.mmr_copy = host_copy_async(o.mmr_value)
         else:                                       # an engine with the one-call form only (test doubles)
             bt.pending, bt.out = None, eng.retrieve_converged(*args, **kw)
         tick("ppr_time", t0)
@@ -553,6 +585,10 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
         rows = BatchRows()
         rows.doc_idx, rows.doc_score, rows.group_idx = d_idx, d_sc, g_idx
         rows.hit_idx, rows.hit_score = h_idx, h_sc
+        rows.mmr_value = None
+        if mmr is not None:
+            copied = bt.pending is not None and not bt.pending.repeated
+            rows.mmr_value = host_wait(bt.mmr_copy).copy() if copied else out.mmr_value.cpu().numpy()
         if keep_all_scores:
             rows.all_scores = getattr(out, "all_scores", None)
             rows.repeated = bt.pending is None or bt.pending.repeated
@@ -1142,6 +1178,36 @@ class HippoRAG:
                                      graph_seeds=(rows[i][2] if len(rows) > i else None) or []))
         return out
 
+    def _mmr(self, mmr_lambda, mmr_candidates) -> dict:
+        """The MMR arguments of a call as iter_batched_retrieve / dense_retrieve take them: the arguments, else
+        RetrievalConfig.mmr_lambda / mmr_candidates, else retrieval_top_k candidates; {} when off."""
+        cfg = self.global_config
+        lam = cfg.mmr_lambda if mmr_lambda is None else mmr_lambda
+        cand = cfg.mmr_candidates if mmr_candidates is None else mmr_candidates
+        if cand is None:
+            from .engine import MMR_MAX_CANDIDATES
+            cand = min(cfg.retrieval_top_k, MMR_MAX_CANDIDATES)
+        if lam is None:
+            if mmr_candidates is not None:
+                raise ValueError("mmr_candidates needs mmr_lambda")
+            return {}
+        return {"mmr_lambda": lam, "mmr_candidates": cand}
+
+    def _refuse_mmr(self, who: str, mmr_lambda, mmr_candidates) -> None:
+        from .engine import refuse_mmr
+        cfg = self.global_config
+        refuse_mmr(who, {"mmr_lambda": cfg.mmr_lambda if mmr_lambda is None else mmr_lambda,
+                         "mmr_candidates": mmr_candidates})
+
+    @staticmethod
+    def _mmr_metadata(solutions, values) -> None:
+        """"mmr_value" into the metadata of every returned entry (the picks are a prefix: -1 only once they run out)."""
+        if values is None:
+            return
+        for s, v in zip(solutions, values):
+            for d, x in zip(s.doc_metadata, v):
+                d["mmr_value"] = float(x)
+
     def _scope(self, filter_scope, doc_filter) -> str:
         """The doc filter's scope of a call: the argument, else RetrievalConfig.doc_filter_scope; "ranking" without a
         filter."""
@@ -1162,8 +1228,14 @@ class HippoRAG:
     # ------------------------------------------------------------------ retrieve :413-499
     def retrieve(self, queries: List[str], num_to_retrieve: Optional[int] = None,
                  gold_docs: Optional[List[List[str]]] = None, doc_filter=None, filter_scope: Optional[str] = None,
-                 group_by=None, group_agg: Optional[str] = None, group_hits: Optional[int] = None):
-        """group_by / group_agg (defaults RetrievalConfig.group_by / group_agg): rank GROUPS of passages -- source
+                 group_by=None, group_agg: Optional[str] = None, group_hits: Optional[int] = None,
+                 mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None):
+        """mmr_lambda / mmr_candidates (defaults RetrievalConfig.mmr_lambda / mmr_candidates; include/hrag.h, diversified
+        retrieval): the docs come in MMR order over the first max(mmr_candidates, num_to_retrieve) ranked entries (mmr_candidates
+        None: retrieval_top_k; never more than the passages or groups there are), doc_scores
+        are their retrieval scores and every entry's metadata carries "mmr_value"; with group_by the candidates are the
+        groups' best passages with the group scores.
+        group_by / group_agg (defaults RetrievalConfig.group_by / group_agg): rank GROUPS of passages -- source
         documents -- instead of passages (group_table): num_to_retrieve counts groups, every entry is a group's best
         passage with the group's score and {"group", "group_size"} in its metadata.
         group_hits=m (default RetrievalConfig.group_hits; with group_by): every entry's metadata also carries "group_hits",
@@ -1184,9 +1256,10 @@ class HippoRAG:
         words = self._doc_filter_words(doc_filter, len(queries))
         agg, table = self._grouping(group_by, group_agg)
         hits = self._hits(group_hits, agg)
+        mmr = self._mmr(mmr_lambda, mmr_candidates)
         self.get_query_embeddings(queries)
         results: List[QuerySolution] = []
-        self._retrieve_into(results, queries, num_to_retrieve, words, scope, agg, table, hits)
+        self._retrieve_into(results, queries, num_to_retrieve, words, scope, agg, table, hits, mmr)
         self.all_retrieval_time += time.time() - t_start
         logger.info("Total Retrieval Time %.2fs", self.all_retrieval_time)
         logger.info("Total Recognition Memory Time %.2fs", self.rerank_time)
@@ -1196,9 +1269,10 @@ class HippoRAG:
         return results
 
     def _retrieve_into(self, results, queries, num_to_retrieve, doc_filter=None, filter_scope: str = "ranking",
-                       group_agg=None, table=None, group_hits=None):
+                       group_agg=None, table=None, group_hits=None, mmr=None):
         cfg = self.global_config
         extra = {} if doc_filter is None else {"doc_filter": doc_filter, "filter_scope": filter_scope}
+        extra.update(mmr or {})
         if group_agg is not None:
             self._engine_groups(table)
             extra.update(group_agg=group_agg, group_of=table[0])
@@ -1214,15 +1288,18 @@ class HippoRAG:
                                               timers=self, **extra):
             with gc_paused():       # around the materialisation only: the filter (an LLM call in production) runs outside
                 if group_agg is not None:
-                    results.extend(self._group_solutions(queries[lo: lo + len(rows)], rows, table, num_to_retrieve))
-                    continue
-                results.extend(self._build_query_solutions(queries[lo: lo + len(rows)], rows, num_to_retrieve))
+                    sols = self._group_solutions(queries[lo: lo + len(rows)], rows, table, num_to_retrieve)
+                else:
+                    sols = self._build_query_solutions(queries[lo: lo + len(rows)], rows, num_to_retrieve)
+                self._mmr_metadata(sols, getattr(rows, "mmr_value", None))
+                results.extend(sols)
 
     # ------------------------------------------------------------------ fused retrieval
     def retrieve_fused(self, questions: List[List[str]], weights=None, fuse: str = "rrf", rrf_c: int = 60,
                        rrf_depth: Optional[int] = None, num_to_retrieve: Optional[int] = None, doc_filter=None,
                        filter_scope: Optional[str] = None, group_by=None, group_agg: Optional[str] = None,
-                       group_hits: Optional[int] = None):
+                       group_hits: Optional[int] = None, mmr_lambda: Optional[float] = None,
+                       mmr_candidates: Optional[int] = None):
         """One ranked list per QUESTION, each question given as several sub-queries -- a decomposition, paraphrases, the
         thoughts of an IRCoT chain (include/hrag.h, fused retrieval).  Every sub-query runs phase A and phase B as in
         retrieve(); the score rows of a question's sub-queries are fused ON THE DEVICE over all passages -- fuse="sum"
@@ -1233,6 +1310,7 @@ class HippoRAG:
         "max".  Returns one QuerySolution per question; its `question` is the question's first sub-query.  A question's
         sub-queries share one device batch: at most max_batch of them."""
         from .engine import check_fuse
+        self._refuse_mmr("retrieve_fused", mmr_lambda, mmr_candidates)
         t_start = time.time()
         cfg = self.global_config
         if num_to_retrieve is None:
@@ -1340,13 +1418,15 @@ class HippoRAG:
     def retrieve_ircot(self, queries: List[str], max_qa_steps: int, num_to_retrieve: Optional[int] = None,
                        gold_docs: Optional[List[List[str]]] = None, reason_fn: Optional[Callable] = None,
                        doc_filter=None, filter_scope: Optional[str] = None, group_by=None,
-                       group_agg: Optional[str] = None):
+                       group_agg: Optional[str] = None, mmr_lambda: Optional[float] = None,
+                       mmr_candidates: Optional[int] = None):
         """Iterative retrieval: alternate retrieval and one reasoning step per query, merging the document
         scores by max (:526-543).  reason_fn(query, ranked_docs, thoughts) -> str stands for
         utils/qa_utils.reason_step (the IRCoT prompt + reader LLM are outside this package).  The reference
         walks the queries one by one and retrieves with a batch of one per step; queries are independent, so
         here every step retrieves for ALL still-active queries in one batched device call -- same result per
         query, batch kernels instead of 2 * max_qa_steps single-query passes."""
+        self._refuse_mmr("retrieve_ircot", mmr_lambda, mmr_candidates)
         if max_qa_steps < 1:
             raise ValueError("max_qa_steps must be at least 1.")
         if max_qa_steps > 1 and reason_fn is None:
@@ -1436,9 +1516,11 @@ class HippoRAG:
     # ------------------------------------------------------------------ retrieve_dpr :665-732
     def retrieve_dpr(self, queries: List[str], num_to_retrieve: Optional[int] = None,
                      gold_docs: Optional[List[List[str]]] = None, doc_filter=None, filter_scope: Optional[str] = None,
-                     group_by=None, group_agg: Optional[str] = None, group_hits: Optional[int] = None):
+                     group_by=None, group_agg: Optional[str] = None, group_hits: Optional[int] = None,
+                     mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None):
         """Dense retrieval; doc_filter / filter_scope as in retrieve() ("seeds": the scores are normalised over the
-        allowed passages); group_by / group_agg / group_hits as in retrieve(), over the normalised dense scores."""
+        allowed passages); group_by / group_agg / group_hits as in retrieve(), over the normalised dense scores;
+        mmr_lambda / mmr_candidates as in retrieve(), over the dense ranking."""
         cfg = self.global_config
         if num_to_retrieve is None:
             num_to_retrieve = cfg.retrieval_top_k
@@ -1460,6 +1542,15 @@ class HippoRAG:
         beyond = k_docs < want
         from .engine import host_copy_async, host_wait
         results = []
+        mmr = self._mmr(mmr_lambda, mmr_candidates)
+        if mmr:
+            from .engine import MMR_MAX_CANDIDATES, mmr_plan
+            lam, c = mmr_plan(mmr["mmr_lambda"], mmr_pool(mmr["mmr_candidates"], want, len(self.passage_node_keys)
+                                                          if agg is None else len(table[1])), want)
+            if c > eng.max_topk:
+                raise ValueError(f"mmr_candidates={c} (at least num_to_retrieve) exceeds the engine's max_topk={eng.max_topk}: "
+                                 f"MMR picks from one device ranking of at most min({MMR_MAX_CANDIDATES}, max_topk) entries")
+            mmr = {"mmr_lambda": lam, "mmr_candidates": c}
 
         def rows_of(lo, b):                 # the packed filter rows of queries [lo, lo + b)
             return words if words.ndim == 1 else words[lo: lo + b]
@@ -1474,10 +1565,10 @@ class HippoRAG:
             if agg is not None:
                 if hits is not None:
                     extra["group_hits"] = hits
-                gi, sc, idx, *h = eng.dense_retrieve(self._q_tensor(qs, "passage"), k=k_docs, group_agg=agg, **extra)
+                gi, sc, idx, *h = eng.dense_retrieve(self._q_tensor(qs, "passage"), k=k_docs, group_agg=agg, **extra, **mmr)
                 return (qs, host_copy_async(idx), host_copy_async(sc), host_copy_async(gi)) + tuple(map(host_copy_async, h))
-            idx, sc = eng.dense_retrieve(self._q_tensor(qs, "passage"), k=k_docs, **extra)
-            return qs, host_copy_async(idx), host_copy_async(sc)
+            idx, sc, *h = eng.dense_retrieve(self._q_tensor(qs, "passage"), k=k_docs, **extra, **mmr)
+            return (qs, host_copy_async(idx), host_copy_async(sc)) + ((None,) + tuple(map(host_copy_async, h)) if h else ())
 
         # one batch ahead of the host, like retrieve(): batch i's lists are built while the device scores batch i + 1
         starts = list(range(0, len(queries), eng.max_batch))
@@ -1485,7 +1576,7 @@ class HippoRAG:
         for n in range(len(starts)):
             qs, idx_h, sc_h, *gi_h = pending
             pending = enqueue(starts[n + 1]) if n + 1 < len(starts) else None
-            gi = h_idx = h_sc = None
+            gi = h_idx = h_sc = values = None
             if beyond:
                 raw = host_wait(idx_h)[:, :len(self.passage_node_keys)]
                 if scope == "seeds":
@@ -1505,20 +1596,26 @@ class HippoRAG:
                     sc = np.take_along_axis(full, idx.astype(np.int64), axis=1)
             else:
                 idx, sc = host_wait(idx_h).copy(), host_wait(sc_h).copy()
-                gi = host_wait(gi_h[0]).copy() if gi_h else None
+                if mmr:                     # dense_retrieve's tuple ends with mmr_value
+                    values = host_wait(gi_h[-1]).copy()
+                    gi_h = gi_h[:-1]
+                gi = host_wait(gi_h[0]).copy() if gi_h and gi_h[0] is not None else None
                 if len(gi_h) == 3:
                     h_idx, h_sc = host_wait(gi_h[1]).copy(), host_wait(gi_h[2]).copy()
+            first = len(results)
             if agg is not None:
                 rows = BatchRows([(idx[i], sc[i], None) for i in range(len(qs))])
                 rows.doc_idx, rows.doc_score, rows.group_idx = idx, sc, gi
                 rows.hit_idx, rows.hit_score = h_idx, h_sc
                 results.extend(self._group_solutions(qs, rows, table, num_to_retrieve))
+                self._mmr_metadata(results[first:], values)
                 continue
             with gc_paused():
                 for i, q in enumerate(qs):
                     r = self._build_retrieval_result(q, idx[i], sc[i], num_to_retrieve)
                     results.append(QuerySolution(question=r.query, docs=r.docs, doc_scores=r.scores,
                                                  doc_metadata=r.doc_metadata))
+            self._mmr_metadata(results[first:], values)
         if gold_docs is not None:
             return results, self._recall(gold_docs, [r.docs for r in results])
         return results

@@ -68,7 +68,9 @@ extern "C" {
  *        hrag_shard_passage_scores_scoped, hrag_shard_mask_prior, hrag_shard_score_facts_all_scoped,
  *        hrag_shard_retrieve_scoped (hrag_engine_set_fact_sources then accepts a row-shard engine);
  *        later in 0.8 (detect by the symbol): fused retrieval -- hrag_fuse_rows, hrag_rrf_rows,
- *        hrag_fuse_workspace_bytes, hrag_last_fused. */
+ *        hrag_fuse_workspace_bytes, hrag_last_fused;
+ *        later in 0.8 (detect by the symbol): diversified retrieval -- hrag_gram_rows, hrag_mmr_rows,
+ *        hrag_mmr_workspace_bytes, hrag_mmr, hrag_mmr_sel. */
 #define HRAG_VERSION_MAJOR 0
 #define HRAG_VERSION_MINOR 8
 
@@ -746,6 +748,76 @@ hrag_status hrag_last_fused(hrag_engine *e, int32_t batch, const int32_t *member
                             int32_t *doc_idx_out_dev, float *doc_score_out_dev, int32_t *group_idx_out_dev,
                             float *group_score_out_dev, int32_t *best_doc_idx_out_dev, void *workspace_dev,
                             size_t workspace_bytes, hrag_stream stream);
+
+/* ---- diversified retrieval: MMR re-ranking of the candidates a ranking returned ----
+ * A ranking by score alone puts near-duplicate passages (overlapping chunk windows, the same paragraph in two sources)
+ * next to each other.  Maximal Marginal Relevance picks k of c candidates greedily, trading each candidate's relevance
+ * against its similarity to what is already picked.  One query has
+ *   candidates  cand_idx[0 .. c): passage positions; -1 or an id outside [0, n_passages) is an EMPTY slot;
+ *   scores      cand_score[0 .. c), in the order some ranking returned them;
+ *   lambda      in [0, 1], fp32;   k with 1 <= k <= c <= HRAG_MMR_MAX_CANDIDATES.
+ * Relevance: mn / mx = fminf / fmaxf over the scores of the non-empty slots, starting from +inf / -inf;
+ *   rel[i] = (s[i] - mn) / (mx - mn), one fp32 subtraction each and one fp32 division (min_max_normalize,
+ *   misc_utils.py:130-139); rel[i] = 1.0f for every slot when mx == mn; normalize == 0: rel[i] = s[i].
+ * Similarity G[i][j] for slots i < j: the score hrag_sim_gemm gives for embedding row cand_idx[i] against row cand_idx[j]
+ *   used as the QUERY -- the same v_mfma_f32_16x16x32 chain, k ascending, one fp32 accumulator.  On a split engine the
+ *   query side takes its thirds as [hi | hi | lo], read from the stored [hi | lo | hi] row.  G[j][i] = G[i][j] by
+ *   definition (bf16 / fp16 / split need no second product); G[i][i] is not used.
+ * Selection, step t = 0 .. k - 1, over the non-empty, not yet selected slots:
+ *   pen[i] = fmaxf over the selected j, in selection order, of G[i][j];   mu = 1.0f - lambda in fp32;
+ *   value[i] = (float)((double)lambda * (double)rel[i]) at t = 0,
+ *              (float)((double)lambda * (double)rel[i] - (double)mu * (double)pen[i]) afterwards (both products are exact
+ *              in fp64: one fp64 subtraction, one rounding);
+ *   the slot with the largest ranking key of `value` is selected (the rule at the top of this header: every NaN above
+ *   +inf, -0 ties +0); ties go to the SMALLER slot, the earlier place in the caller's ranking -- lambda = 1 over a
+ *   ranking's finite scores returns its first k candidates unchanged.
+ * Outputs per query, each [k]: sel_out the slots, idx_out the passage positions, score_out the candidates' own scores and
+ * value_out the value of each pick, both canonical as every ranking returns scores (the quiet NaN, -0 as +0); once the
+ * non-empty slots run out the remaining entries are -1 / -1 / 0 / 0.  No atomics: every value is one chain in a fixed
+ * order, bitwise reproducible (csrc/mmr.hip). */
+#define HRAG_MMR_MAX_CANDIDATES 1024
+
+/* The gathered Gram of each query's candidates, engine-free: emb_dev the 16-bit rows [rows, kdim] (dtype HRAG_BF16 /
+ * HRAG_FP16; kdim a multiple of 8, 16-byte aligned; split != 0: rows in the [hi | lo | hi] layout of hrag_split_f32,
+ * kdim = 3 * dim), cand_idx_dev int32 [batch, c], 1 <= c <= HRAG_MMR_MAX_CANDIDATES.  out_dev fp32 [batch, c, ld],
+ * ld >= c: element [i][j] = G[min(i, j)][max(i, j)] as defined above; an empty slot (id outside [0, rows)) gives +0.0 in
+ * its row and column; the diagonal holds the row's product with itself as the query; the columns c .. ld are not
+ * touched. */
+hrag_status hrag_gram_rows(const uint16_t *emb_dev, int64_t rows, int32_t kdim, int32_t dtype, int32_t split,
+                           const int32_t *cand_idx_dev, int32_t batch, int32_t c, float *out_dev, int64_t ld,
+                           hrag_stream stream);
+
+/* The selection alone, engine-free, over any caller-supplied similarity sim_dev fp32 [batch, c, ld]: score_dev fp32 and
+ * cand_idx_dev int32 [batch, c]; outputs [batch, k].  There is no passage count here: a NEGATIVE id is an empty slot.
+ * After slot j was selected the call reads ROW j of the matrix, pen[i] = fmaxf(pen[i], sim[j][i]): on a symmetric matrix
+ * (what hrag_gram_rows writes) that is the definition's G[i][j]. */
+hrag_status hrag_mmr_rows(const float *score_dev, const int32_t *cand_idx_dev, const float *sim_dev, int64_t ld,
+                          int32_t batch, int32_t c, int32_t k, float lambda, int32_t normalize, int32_t *sel_out_dev,
+                          int32_t *idx_out_dev, float *score_out_dev, float *value_out_dev, hrag_stream stream);
+
+/* Bytes of workspace hrag_mmr needs (16-byte aligned device memory, scratch only): the [batch, c, round_up(c, 4)] fp32
+ * Gram matrix.  Negative on a bad argument. */
+int64_t hrag_mmr_workspace_bytes(int32_t batch, int32_t c);
+
+/* The two steps over the engine's passage embeddings.  It reads only the index half, so it works on a workspace handle
+ * and after any call that produced ids and scores: hrag_retrieve*, the dense calls, the representatives and group scores
+ * of a grouped call, a fused ranking.  Bit-identical to hrag_gram_rows (ld = round_up(c, 4)) followed by hrag_mmr_rows on
+ * the same buffers whenever no id is >= n_passages (such an id is an empty slot here).  The usual one-call-per-handle and
+ * stream rules; nothing is allocated, synchronised or read back (capture safe).
+ * HRAG_EINVAL (nothing enqueued, outputs untouched): a row-shard engine (it holds a slice of the passages), an engine
+ * without passage embeddings, c outside [1, HRAG_MMR_MAX_CANDIDATES], k outside [1, c], lambda outside [0, 1] or NaN,
+ * batch outside [1, max_batch], a NULL pointer, a workspace that is too small or misaligned. */
+hrag_status hrag_mmr(hrag_engine *e, const int32_t *cand_idx_dev, const float *cand_score_dev, int32_t batch, int32_t c,
+                     int32_t k, float lambda, int32_t normalize, int32_t *idx_out_dev, float *score_out_dev,
+                     float *value_out_dev, void *workspace_dev, size_t workspace_bytes, hrag_stream stream);
+
+/* hrag_mmr that also writes the selected SLOTS: sel_out_dev int32 [batch, k] (NULL: hrag_mmr), the position of each pick in
+ * the caller's candidate row (-1 once the candidates run out) -- what a caller needs to carry anything else that came with
+ * the candidates (the group ids of a grouped ranking) along with the picks. */
+hrag_status hrag_mmr_sel(hrag_engine *e, const int32_t *cand_idx_dev, const float *cand_score_dev, int32_t batch, int32_t c,
+                         int32_t k, float lambda, int32_t normalize, int32_t *sel_out_dev, int32_t *idx_out_dev,
+                         float *score_out_dev, float *value_out_dev, void *workspace_dev, size_t workspace_bytes,
+                         hrag_stream stream);
 
 /* ---- lower-level seams (used by the per-method adapters and by the parity tests) ---- */
 
