@@ -11,6 +11,7 @@ LIB_PATH = os.path.join(_HERE, "libhrag.so")
 
 HRAG_OK, HRAG_EINVAL, HRAG_ENOMEM, HRAG_EHIP, HRAG_EBUSY, HRAG_ECAPACITY = range(6)
 SEED_STRIDE = 32
+LEX_TILE, LEX_MAX_QUERY_TERMS = 2048, 256     # HRAG_LEX_TILE / HRAG_LEX_MAX_QUERY_TERMS of include/hrag.h
 HRAG_VERSION = 8      # HRAG_VERSION_MAJOR * 1000 + HRAG_VERSION_MINOR of include/hrag.h
 FLAG_DPR_FALLBACK, FLAG_ZERO_MASS, FLAG_ZERO_PHRASE, FLAG_FP8_SATURATED, FLAG_NOT_CONVERGED = 1, 2, 4, 8, 16
 # the convergence contract's error bound (include/hrag.h): error <= max(PPR_ERR_K * residual, floor of the state type);
@@ -148,6 +149,10 @@ SIGNATURES = {
     "hrag_mmr_workspace_bytes": (C.c_int64, [_I32, _I32]),
     "hrag_mmr": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _F32, _I32, _P, _P, _P, _P, C.c_size_t, _P]),
     "hrag_mmr_sel": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _F32, _I32, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "hrag_lex_create": (C.c_int, [_I64, _I64, _P, _P, _P, C.POINTER(_P)]),
+    "hrag_lex_destroy": (C.c_int, [_P]),
+    "hrag_lex_scores": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _I64, _P, _P, _P]),
+    "hrag_lex_blend_rows": (C.c_int, [_P, _I64, _P, _I64, _I32, _I64, _P, _P, _P, _P, _F32, _P, _I64, _P]),
     "hrag_ppr_sweeps": (C.c_int, [_P, _I32, _I32, _F32, _I32, _P]),
     "hrag_ppr_layout": (C.c_int, [_P, _I32, C.POINTER(_I32), C.POINTER(_I32)]),
     "hrag_row_minmax": (C.c_int, [_P, _I32, _I64, _I64, _P, _P, _P]),

@@ -18,6 +18,7 @@ from . import _lib
 from ._lib import (EmbedDesc, FactDesc, GraphDesc, Opts, ShardLayout, Timings, check, FLAG_DPR_FALLBACK,
                    FLAG_FP8_SATURATED, FLAG_ZERO_MASS, FLAG_ZERO_PHRASE, SEED_STRIDE)
 from .graph import CSRGraph
+from .lexical import invert_postings
 
 
 def _torch():
@@ -60,6 +61,8 @@ GROUP_HITS_MAX = 64                    # HRAG_GROUP_HITS_MAX
 FUSE_MODES = {"sum": 0, "max": 1, "rrf": 2}     # HRAG_FUSE_SUM / HRAG_FUSE_MAX / HRAG_FUSE_RRF
 MMR_MAX_CANDIDATES = 1024              # HRAG_MMR_MAX_CANDIDATES
 MMR_WORKSPACE_CAP = 256 << 20          # bytes of Gram workspace one hrag_mmr call may take: larger batches go in slices
+LEX_TILE = _lib.LEX_TILE                               # HRAG_LEX_TILE
+LEX_MAX_QUERY_TERMS = _lib.LEX_MAX_QUERY_TERMS         # HRAG_LEX_MAX_QUERY_TERMS
 
 
 def check_group_agg(group_agg) -> Optional[int]:
@@ -160,6 +163,124 @@ def refuse_mmr(who: str, kw: dict) -> None:
         if kw.get(name) is not None:
             raise ValueError(f"{who} does not serve {name}: MMR reads the passage embeddings of one unsharded engine after a "
                              "plain ranking -- use HippoRAGEngine.retrieve(mmr_lambda=...) or HippoRAGEngine.mmr")
+
+
+def _host_array(a, name: str) -> np.ndarray:
+    if isinstance(a, np.ndarray):
+        return a
+    if hasattr(a, "detach") and hasattr(a, "cpu"):      # a torch tensor (a device tensor is read back: pass host arrays)
+        return a.detach().cpu().numpy()
+    raise ValueError(f"lexical: {name} must be a numpy array or a torch tensor, not {type(a).__name__}")
+
+
+def check_lexical_weight(lexical_weight) -> float:
+    """lexical_weight as the library takes it: a real number in [0, 1] (not NaN, not a bool)."""
+    if isinstance(lexical_weight, bool) or not isinstance(lexical_weight, (int, float, np.integer, np.floating)):
+        raise ValueError(f"lexical_weight={lexical_weight!r}: a number in [0, 1] expected")
+    w = float(lexical_weight)
+    if not 0.0 <= w <= 1.0:             # (False for NaN)
+        raise ValueError(f"lexical_weight={w}: outside [0, 1]")
+    return w
+
+
+def check_lexical(lexical, lexical_weight, batch: Optional[int]):
+    """The sparse queries of a lexical call (include/hrag.h, lexical retrieval) as the library takes them: lexical =
+    (q_ptr int32 [batch + 1], q_term int32 [nnz], q_weight fp32 [nnz]), the terms of query b at q_ptr[b] .. q_ptr[b + 1].
+    q_ptr runs from 0 to nnz without decreasing; the dtypes are exactly int32 / int32 / fp32 (a silent cast would hide a
+    caller's float64 weights or int64 hashes); no query lists more than LEX_MAX_QUERY_TERMS terms -- the device would
+    ignore the rest, so this RAISES instead of truncating; lexical_weight a number in [0, 1].  batch None: whatever
+    q_ptr says.  Returns (q_ptr, q_term, q_weight, weight) as contiguous host arrays and a float."""
+    if not isinstance(lexical, (tuple, list)) or len(lexical) != 3:
+        raise ValueError("lexical: a (q_ptr, q_term, q_weight) triple expected")
+    weight = check_lexical_weight(lexical_weight)
+    qp, qt, qw = (_host_array(a, n) for a, n in zip(lexical, ("q_ptr", "q_term", "q_weight")))
+    for a, name, dt in ((qp, "q_ptr", np.int32), (qt, "q_term", np.int32), (qw, "q_weight", np.float32)):
+        if a.dtype != dt:
+            raise ValueError(f"lexical: {name} has dtype {a.dtype}, {np.dtype(dt).name} expected")
+        if a.ndim != 1:
+            raise ValueError(f"lexical: {name} must be one-dimensional")
+    if qp.shape[0] < 2 or (batch is not None and qp.shape[0] != batch + 1):
+        raise ValueError(f"lexical: q_ptr has {qp.shape[0]} entries, batch + 1 = "
+                         f"{'at least 2' if batch is None else batch + 1} expected")
+    if qt.shape[0] != qw.shape[0]:
+        raise ValueError(f"lexical: q_term has {qt.shape[0]} entries and q_weight {qw.shape[0]}")
+    if qp[0] != 0 or qp[-1] != qt.shape[0]:
+        raise ValueError(f"lexical: q_ptr must run from 0 to the {qt.shape[0]} listed terms (it runs from {qp[0]} to {qp[-1]})")
+    lens = np.diff(qp.astype(np.int64))
+    if (lens < 0).any():
+        raise ValueError("lexical: q_ptr must not decrease")
+    if (lens > LEX_MAX_QUERY_TERMS).any():
+        raise ValueError(f"lexical: query {int(np.argmax(lens))} lists {int(lens.max())} terms, at most "
+                         f"LEX_MAX_QUERY_TERMS={LEX_MAX_QUERY_TERMS} are scored (merge repeated terms or drop the rarest)")
+    return np.ascontiguousarray(qp), np.ascontiguousarray(qt), np.ascontiguousarray(qw), weight
+
+
+def refuse_lexical(who: str, kw: dict) -> None:
+    """The callers that do not serve lexical retrieval name the argument they refuse."""
+    if kw.get("lexical") is not None:
+        raise NotImplementedError(f"{who} does not serve lexical: the lexical score rows cover every passage of one "
+                                  "unsharded engine and are blended before the call's own min-max -- use "
+                                  "HippoRAGEngine.retrieve(lexical=...)")
+    if kw.get("lexical_weight") not in (None, 0, 0.0):
+        raise NotImplementedError(f"{who} does not serve lexical_weight: use HippoRAGEngine.retrieve(lexical=..., "
+                                  "lexical_weight=...)")
+
+
+class LexicalIndex:
+    """A sparse passage index on the device (hrag_lex_create; include/hrag.h, lexical retrieval): per term, the passages
+    that hold it and a weight each.  Independent of any engine -- HippoRAGEngine.set_lexical_index takes it by reference,
+    so several engines and their workspaces over the same passages share one.  The library scores whatever weights it is
+    given (hipporag_amd.lexical.bm25_weights makes BM25 ones)."""
+
+    def __init__(self, n_passages: int, n_terms: int, term_ptr, post_doc, post_w, device: Optional[int] = None):
+        torch = _torch()
+        if not torch.cuda.is_available():
+            raise RuntimeError("LexicalIndex needs an MI355X-class GPU: no HIP device is visible (there is no CPU fallback)")
+        self._lib = _lib.load()
+        self._handle = C.c_void_p(0)
+        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+        tp = np.ascontiguousarray(term_ptr, dtype=np.int64)
+        pd = np.ascontiguousarray(post_doc, dtype=np.int32)
+        pw = np.ascontiguousarray(post_w, dtype=np.float32)
+        if tp.ndim != 1 or tp.shape[0] != int(n_terms) + 1:
+            raise ValueError(f"term_ptr: {int(n_terms) + 1} entries expected")
+        if pd.ndim != 1 or pd.shape != pw.shape or (tp.size and int(tp[-1]) != pd.shape[0]):
+            raise ValueError("post_doc / post_w: one entry per posting, term_ptr[-1] of them, expected")
+        with torch.cuda.device(self.device):
+            check(self._lib.hrag_lex_create(int(n_passages), int(n_terms), tp.ctypes.data, pd.ctypes.data if pd.size else None,
+                                            pw.ctypes.data if pw.size else None, C.byref(self._handle)))
+        self.n_passages, self.n_terms, self.nnz = int(n_passages), int(n_terms), int(pd.shape[0])
+
+    @classmethod
+    def from_postings(cls, n_passages: int, term_ptr, post_doc, post_w, device: Optional[int] = None) -> "LexicalIndex":
+        """From the inverted form itself: the posting list of term t is post_doc[term_ptr[t] : term_ptr[t + 1]]."""
+        return cls(n_passages, len(term_ptr) - 1, term_ptr, post_doc, post_w, device)
+
+    @classmethod
+    def from_csr(cls, row_ptr, term, weight, n_terms: Optional[int] = None, device: Optional[int] = None) -> "LexicalIndex":
+        """From passage-major rows (invert_postings, on the host); a term repeated within a passage is rejected.
+        n_terms None: the largest term id + 1."""
+        n = len(row_ptr) - 1
+        if n_terms is None:
+            n_terms = int(np.max(term)) + 1 if np.size(term) else 0
+        return cls(n, n_terms, *invert_postings(n, n_terms, row_ptr, term, weight), device)
+
+    def close(self):
+        if getattr(self, "_handle", None) and self._handle.value:
+            check(self._lib.hrag_lex_destroy(self._handle))
+            self._handle = C.c_void_p(0)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 def group_table_csr(group_of, n_groups: int):
@@ -696,7 +817,8 @@ class HippoRAGEngine:
                  k: int = 200, ppr_tol: float = 0.0, ppr_max_iters: int = 0,
                  want_residual: bool = True, doc_filter=None, filter_scope: str = "ranking",
                  group_agg: Optional[str] = None, group_hits: Optional[int] = None,
-                 mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None) -> RetrieveOutput:
+                 mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None,
+                 lexical=None, lexical_weight: float = 0.5) -> RetrieveOutput:
         """Phase B: seeds + passage prior + PPR + ranking (DPR ranking where kept_count == 0).
         ppr_tol / ppr_max_iters: the convergence contract of include/hrag.h (0 = exactly ppr_iters sweeps);
         the output carries the per-query residual and the sweeps that ran.
@@ -712,7 +834,18 @@ class HippoRAGEngine:
         c = max(mmr_candidates, k) <= min(max_topk, 1024) entries (mmr_candidates None: k) and returns the k MMR picks among
         them in doc_idx / doc_score (their own scores, MMR order) and mmr_value; relevance is the min-max of the candidates'
         scores.  With group_agg the candidates are the groups' best passages with the group scores, and group_idx / the
-        hits follow the picks.  None: the call and its outputs are exactly the plain ones."""
+        hits follow the picks.  None: the call and its outputs are exactly the plain ones.
+        lexical=(q_ptr, q_term, q_weight) (check_lexical; after set_lexical_index; include/hrag.h, lexical retrieval): the
+        passage scores are the dense ones (hrag_sim_scores) blended with the lexical rows of these sparse queries at
+        lexical_weight in [0, 1] (hrag_row_minmax, hrag_lex_scores, hrag_lex_blend_rows), handed to hrag_retrieve_scored*:
+        the doc filter (scope "ranking"), group_agg, group_hits, mmr_* and a following last_fused work as they do there.  A
+        query whose terms match nothing keeps its dense row bit for bit.  None: the call is exactly the plain one."""
+        if lexical is not None:
+            rows = self._lexical_blend(None, q_pass, lexical, lexical_weight, filter_scope, doc_filter)
+            return self._retrieve("hrag_retrieve_scored", rows, (kept_idx, kept_score, kept_count),
+                                  (link_top_k, damping, passage_node_weight, ppr_iters, max(ppr_max_iters, ppr_iters), ppr_tol),
+                                  k, want_residual or ppr_tol > 0, doc_filter=doc_filter, filter_scope=filter_scope,
+                                  group_agg=group_agg, group_hits=group_hits, mmr=mmr_plan(mmr_lambda, mmr_candidates, k))
         return self._retrieve("hrag_retrieve", q_pass, (kept_idx, kept_score, kept_count),
                               (link_top_k, damping, passage_node_weight, ppr_iters, max(ppr_max_iters, ppr_iters), ppr_tol), k,
                               want_residual or ppr_tol > 0, doc_filter=doc_filter, filter_scope=filter_scope,
@@ -773,6 +906,108 @@ class HippoRAGEngine:
         if mmr is not None:
             self._mmr_picks(out, k_out, mmr[0])
         return out
+
+    # ------------------------------------------------------------------ lexical retrieval
+    def set_lexical_index(self, ix: Optional["LexicalIndex"]):
+        """The LexicalIndex the lexical= calls of this engine and of its workspaces score against (None: none).  Held by
+        reference on the Python side only: the library's engine does not know it, and closing it is the caller's."""
+        root = getattr(self, "_parent", None) or self
+        if ix is not None:
+            if root.n_rows != root.num_vertices or root.passage_rows != root.n_passages:
+                raise NotImplementedError("set_lexical_index on a row-shard engine: lexical retrieval is served by the "
+                                          "unsharded engine only")
+            if ix.n_passages != root.n_passages:
+                raise ValueError(f"the lexical index covers {ix.n_passages} passages, the engine {root.n_passages}")
+            if ix.device != root.device:
+                raise ValueError(f"the lexical index lives on {ix.device}, the engine on {root.device}")
+        root._lexical_index = ix
+
+    def _lex_index(self) -> "LexicalIndex":
+        ix = getattr(getattr(self, "_parent", None) or self, "_lexical_index", None)
+        if ix is None or not ix._handle.value:
+            raise ValueError("lexical: no lexical index on this engine (set_lexical_index)")
+        return ix
+
+    def _lex_rows(self, qp, qt, qw):
+        """(rows fp32 [B, n_passages], mn [B], mx [B]) of checked host CSR queries (hrag_lex_scores)."""
+        torch = _torch()
+        ix = self._lex_index()
+        b, nnz = qp.shape[0] - 1, qt.shape[0]
+        d_p = torch.from_numpy(qp).to(self.device)
+        d_t = torch.from_numpy(qt).to(self.device)
+        d_w = torch.from_numpy(qw).to(self.device)
+        rows = self._empty((b, ix.n_passages), torch.float32)
+        mn, mx = self._empty((b,), torch.float32), self._empty((b,), torch.float32)
+        check(self._lib.hrag_lex_scores(ix._handle, d_p.data_ptr(), d_t.data_ptr() if nnz else None,
+                                        d_w.data_ptr() if nnz else None, nnz, b, rows.data_ptr(), rows.stride(0),
+                                        mn.data_ptr(), mx.data_ptr(), _stream()))
+        return rows, mn, mx
+
+    def lexical_scores(self, q_ptr, q_term, q_weight, want_minmax: bool = False):
+        """The lexical score rows fp32 [B, n_passages] of sparse queries (check_lexical's triple) against the engine's
+        lexical index; want_minmax: (rows, mn [B], mx [B]), the row min / max as hrag_row_minmax gives them."""
+        qp, qt, qw, _ = check_lexical((q_ptr, q_term, q_weight), 0.0, None)
+        rows, mn, mx = self._lex_rows(qp, qt, qw)
+        return (rows, mn, mx) if want_minmax else rows
+
+    def _lexical_blend(self, dense_rows, q_pass, lexical, lexical_weight, filter_scope: str = "ranking", doc_filter=None):
+        """The blended passage score rows fp32 [B, n_passages] of a lexical= call: dense_rows (the caller's, left as they
+        are) or, when None, hrag_sim_scores of q_pass (blended in place)."""
+        torch = _torch()
+        if check_filter_scope(filter_scope, doc_filter):
+            raise NotImplementedError('filter_scope="seeds" is not served with lexical: the blend\'s two min-maxes would '
+                                      'have to run over the allowed passages -- use filter_scope="ranking"')
+        ix = self._lex_index()
+        n = ix.n_passages
+        if dense_rows is None:
+            q = self._q(q_pass)
+            b = q.shape[0]
+        else:
+            src = dense_rows.to(self.device, torch.float32)
+            if src.dim() != 2 or src.shape[1] < n:
+                raise ValueError(f"pass_scores must be [B, >= {n}]")
+            if src.stride(-1) != 1:
+                src = src.contiguous()
+            b = src.shape[0]
+        qp, qt, qw, alpha = check_lexical(lexical, lexical_weight, b)      # before anything is enqueued
+        if dense_rows is None:
+            src = out = self.sim_scores("passages", q)
+        else:
+            out = self._empty((b, n), torch.float32)
+        lex, mn_l, mx_l = self._lex_rows(qp, qt, qw)
+        mn_d, mx_d = self._empty((b,), torch.float32), self._empty((b,), torch.float32)
+        check(self._lib.hrag_row_minmax(src.data_ptr(), b, n, src.stride(0), mn_d.data_ptr(), mx_d.data_ptr(), _stream()))
+        check(self._lib.hrag_lex_blend_rows(src.data_ptr(), src.stride(0), lex.data_ptr(), lex.stride(0), b, n,
+                                            mn_d.data_ptr(), mx_d.data_ptr(), mn_l.data_ptr(), mx_l.data_ptr(), alpha,
+                                            out.data_ptr(), out.stride(0), _stream()))
+        return out
+
+    def _rank_rows(self, rows, k: int, normalize: bool, doc_filter=None):
+        """(idx int32, score fp32) [B, k]: the library ranking of score rows over the engine's passages
+        (hrag_topk_rows_ws, or hrag_topk_rows_masked under a doc filter); normalize: min-max normalised scores."""
+        torch = _torch()
+        b, n = rows.shape[0], self.n_passages
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+            raise ValueError(f"k={k!r}: an int >= 1 expected")
+        idx, val = self._empty((b, k), torch.int32), self._empty((b, k), torch.float32)
+        need = int(self._lib.hrag_topk_rows_workspace_bytes(b, n, k))
+        ws = _topk_workspace(self.device, _stream(), need).data_ptr() if need > 0 else None
+        if doc_filter is None:
+            check(self._lib.hrag_topk_rows_ws(rows.data_ptr(), b, n, rows.stride(0), k, 0, 1 if normalize else 0,
+                                              idx.data_ptr(), val.data_ptr(), None, None, ws, max(need, 0), _stream()))
+        else:
+            fw, fld = doc_filter_words(doc_filter, n, b, self.device)
+            check(self._lib.hrag_topk_rows_masked(rows.data_ptr(), b, n, rows.stride(0), k, 0, 1 if normalize else 0,
+                                                  fw.data_ptr(), fld, 0, idx.data_ptr(), val.data_ptr(), None, None, ws,
+                                                  max(need, 0), _stream()))
+        return idx, val
+
+    def lexical_retrieve(self, lexical, k: int = 200, doc_filter=None):
+        """The pure lexical ranking: (idx int32, score fp32) [B, k] of the lexical score rows as they are (no
+        normalisation, no dense side), under doc_filter; -1 / 0 beyond the passages there are (or are allowed)."""
+        qp, qt, qw, _ = check_lexical(lexical, 0.0, None)
+        rows, _, _ = self._lex_rows(qp, qt, qw)
+        return self._rank_rows(rows, k, False, doc_filter)
 
     def mmr(self, cand_idx, cand_score, k: int, lam: float = 0.5, normalize: bool = True, return_sel: bool = False):
         """MMR re-ranking (hrag_mmr; include/hrag.h, diversified retrieval) of candidates int32 [B, c] (passage positions in
@@ -886,8 +1121,11 @@ class HippoRAGEngine:
                         ppr_tol: float = 0.0, ppr_max_iters: int = 0, doc_filter=None,
                         filter_scope: str = "ranking", group_agg: Optional[str] = None,
                         group_hits: Optional[int] = None, mmr_lambda: Optional[float] = None,
-                        mmr_candidates: Optional[int] = None) -> RetrieveOutput:
-        """retrieve() with the raw passage scores fp32 [B, >= Np] supplied by the caller (hrag_retrieve_scored)."""
+                        mmr_candidates: Optional[int] = None, lexical=None, lexical_weight: float = 0.5) -> RetrieveOutput:
+        """retrieve() with the raw passage scores fp32 [B, >= Np] supplied by the caller (hrag_retrieve_scored).
+        lexical / lexical_weight: as on retrieve(), blended into the caller's rows (which are left as they are)."""
+        if lexical is not None:
+            pass_scores = self._lexical_blend(pass_scores, None, lexical, lexical_weight, filter_scope, doc_filter)
         return self._retrieve("hrag_retrieve_scored", pass_scores, (kept_idx, kept_score, kept_count),
                               (link_top_k, damping, passage_node_weight, ppr_iters, max(ppr_max_iters, ppr_iters), ppr_tol), k,
                               True, doc_filter=doc_filter, filter_scope=filter_scope, group_agg=group_agg,
@@ -918,6 +1156,11 @@ class HippoRAGEngine:
         kept_idx, kept_score, kept_count = (t.to(self.device) for t in (kept_idx, kept_score, kept_count))
         doc_filter = kw.pop("doc_filter", None)
         check_filter_scope(kw.get("filter_scope", "ranking"), doc_filter)   # (filter_scope travels in kw to every run)
+        lexical, lexical_weight = kw.pop("lexical", None), kw.pop("lexical_weight", 0.5)
+        # lexical: the blended rows are formed ONCE; every run, the repeats of finish() included, is retrieve_scored on its
+        # rows of them (a repeat never re-encodes or re-slices the sparse queries)
+        blended = None if lexical is None else self._lexical_blend(None, q, lexical, lexical_weight,
+                                                                   kw.get("filter_scope", "ranking"), doc_filter)
         fw, fld = (None, 0) if doc_filter is None else doc_filter_words(doc_filter, self.n_passages, q.shape[0],
                                                                         self.device)
 
@@ -925,8 +1168,13 @@ class HippoRAGEngine:
             sel = slice(None) if rows is None else rows
             if fw is not None:    # the repeats of finish() rerun rows of the batch: each keeps its own filter row
                 kw["doc_filter"] = fw if fld == 0 else fw[sel]
-            o = self.retrieve(q[sel], kept_idx[sel], kept_score[sel], kept_count[sel], damping=damping,
-                              ppr_iters=iters, ppr_tol=ppr_tol, ppr_max_iters=max(max_iters, iters), **kw)
+            if blended is not None:
+                o = self.retrieve_scored(blended[sel], kept_idx[sel], kept_score[sel], kept_count[sel], damping=damping,
+                                         ppr_iters=iters, ppr_tol=ppr_tol, ppr_max_iters=max(max_iters, iters),
+                                         **{n: v for n, v in kw.items() if n != "want_residual"})
+            else:
+                o = self.retrieve(q[sel], kept_idx[sel], kept_score[sel], kept_count[sel], damping=damping,
+                                  ppr_iters=iters, ppr_tol=ppr_tol, ppr_max_iters=max(max_iters, iters), **kw)
             if want_all_scores:     # every passage's score (callers that want more than max_topk documents)
                 o.all_scores = self.last_doc_scores(o.doc_idx.shape[0])
             return o
@@ -944,11 +1192,26 @@ class HippoRAGEngine:
 
     def dense_retrieve(self, q_pass, k: int = 200, doc_filter=None, filter_scope: str = "ranking",
                        group_agg: Optional[str] = None, group_hits: Optional[int] = None,
-                       mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None):
+                       mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None,
+                       lexical=None, lexical_weight: float = 0.5):
         """DPR top-k; filter_scope="seeds": normalised over the allowed passages (hrag_dense_retrieve_scoped).
         group_agg="max" | "sum": (group ids, group scores, best passage of each group) over the normalised scores
         (hrag_dense_retrieve_grouped); group_hits=m adds two entries, (hit_idx, hit_score) [B, k, m] over those scores.
-        mmr_lambda / mmr_candidates: as on retrieve; the tuple then ends with one more entry, mmr_value [B, k]."""
+        mmr_lambda / mmr_candidates: as on retrieve; the tuple then ends with one more entry, mmr_value [B, k].
+        lexical / lexical_weight (as on retrieve): (idx, score) of the blended rows, ranked by the normalising top-k
+        (hrag_topk_rows_ws, hrag_topk_rows_masked under a doc_filter); not with group_agg, group_hits, mmr_* or
+        filter_scope="seeds"."""
+        if lexical is not None:
+            for name, v in (("group_agg", group_agg), ("group_hits", group_hits), ("mmr_lambda", mmr_lambda),
+                            ("mmr_candidates", mmr_candidates)):
+                if v is not None:
+                    raise ValueError(f"dense_retrieve(lexical=) does not serve {name}: it ranks the blended rows and keeps "
+                                     "no score rows on the handle -- use retrieve(lexical=...) or rank lexical_scores yourself")
+            if filter_scope == "seeds":
+                raise ValueError('dense_retrieve(lexical=) does not serve filter_scope="seeds": the blend\'s min-maxes run '
+                                 "over every passage")
+            rows = self._lexical_blend(None, q_pass, lexical, lexical_weight, filter_scope, doc_filter)
+            return self._rank_rows(rows, k, True, doc_filter)
         out = self._retrieve("hrag_dense_retrieve", q_pass, None, (), k, False, doc_filter=doc_filter,
                              filter_scope=filter_scope, group_agg=group_agg, group_hits=group_hits,
                              mmr=mmr_plan(mmr_lambda, mmr_candidates, k))
@@ -1203,6 +1466,7 @@ class CapturedPipeline:
         torch = _torch()
         refuse_group_agg("CapturedPipeline", retrieve_kw)
         refuse_mmr("CapturedPipeline", retrieve_kw)
+        refuse_lexical("CapturedPipeline", retrieve_kw)
         self.engine, self.batch = engine, int(batch)
         dev, dt = engine.device, engine.emb_dtype
         self._qf = torch.zeros((batch, engine.dim), dtype=dt, device=dev)

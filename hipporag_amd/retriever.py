@@ -197,6 +197,11 @@ class RetrievalConfig:
                                          # (1: relevance only, 0: diversity only after the first pick); None: off
     mmr_candidates: Optional[int] = None # how many ranked entries MMR picks from: max(this, num_to_retrieve), at most the
                                          # passages (or groups) there are and at most 1024; None: min(retrieval_top_k, 1024)
+    lexical_weight: float = 0.0          # lexical retrieval (include/hrag.h): the weight in [0, 1] of the BM25 scores of the
+                                         # query strings in the passage scores of retrieve() / retrieve_dpr() / rag_qa() /
+                                         # retrieve_ircot(); 0: nothing is built and nothing changes
+    lexical_tokenize_fn: Optional[Callable] = None   # str -> list of tokens, for passages and queries alike; None:
+                                         # lexical.default_tokenize (lower-case, \w+)
 
 
 def identity_rerank_filter(query, candidate_items, candidate_indices, len_after_rerank=None):
@@ -396,7 +401,8 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
                           ppr_max_iters: int = 0, ppr_base_iters_narrow: Optional[int] = None, doc_filter=None,
                           filter_scope: str = "ranking", group_agg: Optional[str] = None, group_of=None,
                           group_hits: Optional[int] = None, keep_all_scores: bool = False,
-                          mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None):
+                          mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None,
+                          lexical_encode: Optional[Callable] = None, lexical_weight: float = 0.0):
     """The body of retrieve() (HippoRAG.py:459-480), shared by the mirror class below and by
     reference_adapter.attach(): phase A on the device, the recognition-memory filter on the host (rerank_facts
     :1659-1707), phase B on the device, in batches of eng.max_batch queries.  Yields (offset of the batch, [(doc ids,
@@ -427,6 +433,9 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
     -- at most the passages (groups) there are; mmr_candidates None: `want`, the mirror passes its retrieval_top_k -- and MMR
     picks `want` of them on the device (HippoRAGEngine.retrieve(mmr_lambda=)); rows.mmr_value [b, want] is the value of
     each pick.  At most min(1024, max_topk) candidates.
+    lexical_encode / lexical_weight (include/hrag.h, lexical retrieval): with a weight above 0 every batch's query strings
+    are encoded (lexical_encode(strings) -> the CSR triple of engine.check_lexical) and phase B gets lexical= /
+    lexical_weight=; with 0 its arguments are exactly the plain ones.
     keep_all_scores: rows.all_scores is the device tensor of every passage's score of the batch and rows.repeated tells
     whether the contract ran rows again (retrieve_fused: the engine's own score rows are then not the batch's)."""
     import torch
@@ -457,6 +466,9 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
     use_facts = len(facts) > 0 and k_f > 0
     from .engine import check_filter_scope
     scoped = doc_filter is not None and check_filter_scope(filter_scope, doc_filter)
+    if scoped and lexical_encode is not None and lexical_weight > 0:
+        raise NotImplementedError('filter_scope="seeds" is not served with lexical_weight > 0: the blend\'s min-maxes run over '
+                                  'every passage -- use filter_scope="ranking"')
     if scoped and use_facts and not getattr(eng, "has_fact_sources", False):
         raise ValueError('filter_scope="seeds" needs the fact -> passage table on the engine (set_fact_sources)')
     two_halves = hasattr(eng, "retrieve_converged_start")
@@ -530,6 +542,8 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
             kw["group_hits"] = group_hits
         if mmr is not None:
             kw.update(mmr_lambda=mmr[0], mmr_candidates=mmr[1])
+        if lexical_encode is not None and lexical_weight > 0:
+            kw.update(lexical=lexical_encode(qs), lexical_weight=lexical_weight)
         if two_halves:
             bt.pending = eng.retrieve_converged_start(*args, **kw)
             o = bt.pending.out
@@ -652,6 +666,7 @@ class HippoRAG:
         self._graph = None                                 # graph.IncrementalGraph (the igraph object)
         self._pass_emb = self._fact_emb = None             # fp32 rows in store order
         self._arrays = None
+        self.lexical_model = self.lexical_index = None     # lexical retrieval (lexical_weight > 0): built with the engine
 
     # ------------------------------------------------------------------ index side
     def index_from_openie(self, docs: Sequence, chunk_triples: Sequence[Sequence[Sequence[str]]],
@@ -908,6 +923,7 @@ class HippoRAG:
             pe = compose("passages", self.passage_node_keys, a["passage_emb"], held["passages"])
             if has_facts and held["facts"]:
                 fe = compose("facts", self.fact_node_keys, a["fact_emb"], held["facts"])
+        self._drop_lexical()
         if old is not None:
             # the gathered matrices no longer depend on the old engine: free its index before the new one is built
             # (peak device memory = one index + the embedding matrices, not two indexes)
@@ -940,7 +956,54 @@ class HippoRAG:
         self.engine = engine
         self._engine_rows = {"passages": list(self.passage_node_keys), "facts": list(self.fact_node_keys) if has_facts else []}
         self.passage_node_idxs = a["passage_vertex"].tolist()
+        if self.global_config.lexical_weight > 0:
+            self._build_lexical()
         self.ready_to_retrieve = True
+
+    # ------------------------------------------------------------------ lexical retrieval
+    def _drop_lexical(self):
+        ix = getattr(self, "lexical_index", None)
+        if ix is not None:
+            ix.close()
+        self.lexical_model = self.lexical_index = None
+
+    def _build_lexical(self):
+        """The BM25 model of the passages the mirror holds (lexical.LexicalModel: vocabulary, idf, weights) and its device
+        index on the engine.  prepare_retrieval_objects rebuilds it after index() / delete(): idf and the average length
+        move with the corpus.  An engine without set_lexical_index (a test double) gets the model only."""
+        from .lexical import LexicalModel
+        self._drop_lexical()
+        self.lexical_model = LexicalModel(self.passage_texts, self.global_config.lexical_tokenize_fn)
+        if hasattr(self.engine, "set_lexical_index"):
+            from .engine import LexicalIndex
+            self.lexical_index = LexicalIndex.from_postings(len(self.passage_texts), *self.lexical_model.postings(),
+                                                            device=self.engine.device.index)
+            self.engine.set_lexical_index(self.lexical_index)
+
+    def _lexical(self, lexical_weight) -> dict:
+        """The lexical arguments of a call as iter_batched_retrieve takes them: the argument, else
+        RetrievalConfig.lexical_weight; {} at weight 0.  Builds the index on first use when the config did not ask for it."""
+        from .engine import check_lexical_weight
+        w = check_lexical_weight(self.global_config.lexical_weight if lexical_weight is None else lexical_weight)
+        if w == 0:
+            return {}
+        if getattr(self, "lexical_model", None) is None:
+            self._build_lexical()
+        return {"lexical_encode": self.lexical_model.encode_queries, "lexical_weight": w}
+
+    def _refuse_lexical(self, who: str, lexical_weight=None) -> None:
+        w = self.global_config.lexical_weight if lexical_weight is None else lexical_weight
+        if w not in (None, 0, 0.0):
+            raise ValueError(f"{who} does not serve lexical_weight={w}: it fuses the score rows of plain member calls -- use "
+                             "retrieve(lexical_weight=...)")
+
+    @staticmethod
+    def _lexical_metadata(solutions, lex: dict) -> None:
+        """"lexical_weight" into the metadata of every returned entry of a lexical call."""
+        if lex:
+            for s in solutions:
+                for d in s.doc_metadata or []:
+                    d["lexical_weight"] = lex["lexical_weight"]
 
     def fact_source_table(self):
         """The fact -> source-passage table of the scoped doc filter as a CSR in self.facts order: (row_ptr int64
@@ -1229,8 +1292,13 @@ class HippoRAG:
     def retrieve(self, queries: List[str], num_to_retrieve: Optional[int] = None,
                  gold_docs: Optional[List[List[str]]] = None, doc_filter=None, filter_scope: Optional[str] = None,
                  group_by=None, group_agg: Optional[str] = None, group_hits: Optional[int] = None,
-                 mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None):
-        """mmr_lambda / mmr_candidates (defaults RetrievalConfig.mmr_lambda / mmr_candidates; include/hrag.h, diversified
+                 mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None,
+                 lexical_weight: Optional[float] = None):
+        """lexical_weight (default RetrievalConfig.lexical_weight; include/hrag.h, lexical retrieval): above 0, the passage
+        scores that feed the passage prior and the DPR fallback are the dense ones blended at this weight with the BM25
+        scores of the query strings against the passages (hipporag_amd.lexical); every entry's metadata then carries
+        "lexical_weight".  Everything below composes with it except filter_scope="seeds".
+        mmr_lambda / mmr_candidates (defaults RetrievalConfig.mmr_lambda / mmr_candidates; include/hrag.h, diversified
         retrieval): the docs come in MMR order over the first max(mmr_candidates, num_to_retrieve) ranked entries (mmr_candidates
         None: retrieval_top_k; never more than the passages or groups there are), doc_scores
         are their retrieval scores and every entry's metadata carries "mmr_value"; with group_by the candidates are the
@@ -1257,9 +1325,10 @@ class HippoRAG:
         agg, table = self._grouping(group_by, group_agg)
         hits = self._hits(group_hits, agg)
         mmr = self._mmr(mmr_lambda, mmr_candidates)
+        lex = self._lexical(lexical_weight)
         self.get_query_embeddings(queries)
         results: List[QuerySolution] = []
-        self._retrieve_into(results, queries, num_to_retrieve, words, scope, agg, table, hits, mmr)
+        self._retrieve_into(results, queries, num_to_retrieve, words, scope, agg, table, hits, mmr, lex)
         self.all_retrieval_time += time.time() - t_start
         logger.info("Total Retrieval Time %.2fs", self.all_retrieval_time)
         logger.info("Total Recognition Memory Time %.2fs", self.rerank_time)
@@ -1269,10 +1338,11 @@ class HippoRAG:
         return results
 
     def _retrieve_into(self, results, queries, num_to_retrieve, doc_filter=None, filter_scope: str = "ranking",
-                       group_agg=None, table=None, group_hits=None, mmr=None):
+                       group_agg=None, table=None, group_hits=None, mmr=None, lex=None):
         cfg = self.global_config
         extra = {} if doc_filter is None else {"doc_filter": doc_filter, "filter_scope": filter_scope}
         extra.update(mmr or {})
+        extra.update(lex or {})
         if group_agg is not None:
             self._engine_groups(table)
             extra.update(group_agg=group_agg, group_of=table[0])
@@ -1292,6 +1362,7 @@ class HippoRAG:
                 else:
                     sols = self._build_query_solutions(queries[lo: lo + len(rows)], rows, num_to_retrieve)
                 self._mmr_metadata(sols, getattr(rows, "mmr_value", None))
+                self._lexical_metadata(sols, lex)
                 results.extend(sols)
 
     # ------------------------------------------------------------------ fused retrieval
@@ -1311,6 +1382,7 @@ class HippoRAG:
         sub-queries share one device batch: at most max_batch of them."""
         from .engine import check_fuse
         self._refuse_mmr("retrieve_fused", mmr_lambda, mmr_candidates)
+        self._refuse_lexical("retrieve_fused")
         t_start = time.time()
         cfg = self.global_config
         if num_to_retrieve is None:
@@ -1419,13 +1491,14 @@ class HippoRAG:
                        gold_docs: Optional[List[List[str]]] = None, reason_fn: Optional[Callable] = None,
                        doc_filter=None, filter_scope: Optional[str] = None, group_by=None,
                        group_agg: Optional[str] = None, mmr_lambda: Optional[float] = None,
-                       mmr_candidates: Optional[int] = None):
+                       mmr_candidates: Optional[int] = None, lexical_weight: Optional[float] = None):
         """Iterative retrieval: alternate retrieval and one reasoning step per query, merging the document
         scores by max (:526-543).  reason_fn(query, ranked_docs, thoughts) -> str stands for
         utils/qa_utils.reason_step (the IRCoT prompt + reader LLM are outside this package).  The reference
         walks the queries one by one and retrieves with a batch of one per step; queries are independent, so
         here every step retrieves for ALL still-active queries in one batched device call -- same result per
-        query, batch kernels instead of 2 * max_qa_steps single-query passes."""
+        query, batch kernels instead of 2 * max_qa_steps single-query passes.  lexical_weight (default
+        RetrievalConfig.lexical_weight): every step's retrieve() takes it, the thoughts being the query strings."""
         self._refuse_mmr("retrieve_ircot", mmr_lambda, mmr_candidates)
         if max_qa_steps < 1:
             raise ValueError("max_qa_steps must be at least 1.")
@@ -1434,7 +1507,8 @@ class HippoRAG:
         if num_to_retrieve is None:
             num_to_retrieve = self.global_config.retrieval_top_k
         first = self.retrieve(list(queries), num_to_retrieve=num_to_retrieve, doc_filter=doc_filter,
-                              filter_scope=filter_scope, group_by=group_by, group_agg=group_agg)
+                              filter_scope=filter_scope, group_by=group_by, group_agg=group_agg,
+                              lexical_weight=lexical_weight)
         merged = [dict(zip(r.docs, r.doc_scores.tolist())) for r in first]
         meta = [dict(zip(r.docs, r.doc_metadata or [])) for r in first]
         thoughts: List[List[str]] = [[] for _ in queries]
@@ -1455,7 +1529,8 @@ class HippoRAG:
                 break
             for i, r in zip(step_i, self.retrieve(step_q, num_to_retrieve=num_to_retrieve,
                                                   doc_filter=self._filter_rows(doc_filter, step_i),
-                                                  filter_scope=filter_scope, group_by=group_by, group_agg=group_agg)):
+                                                  filter_scope=filter_scope, group_by=group_by, group_agg=group_agg,
+                                                  lexical_weight=lexical_weight)):
                 for doc, score in zip(r.docs, r.doc_scores.tolist()):
                     merged[i][doc] = max(merged[i].get(doc, float("-inf")), score)
                 meta[i].update(dict(zip(r.docs, r.doc_metadata or [])))
@@ -1517,10 +1592,14 @@ class HippoRAG:
     def retrieve_dpr(self, queries: List[str], num_to_retrieve: Optional[int] = None,
                      gold_docs: Optional[List[List[str]]] = None, doc_filter=None, filter_scope: Optional[str] = None,
                      group_by=None, group_agg: Optional[str] = None, group_hits: Optional[int] = None,
-                     mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None):
+                     mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None,
+                     lexical_weight: Optional[float] = None):
         """Dense retrieval; doc_filter / filter_scope as in retrieve() ("seeds": the scores are normalised over the
         allowed passages); group_by / group_agg / group_hits as in retrieve(), over the normalised dense scores;
-        mmr_lambda / mmr_candidates as in retrieve(), over the dense ranking."""
+        mmr_lambda / mmr_candidates as in retrieve(), over the dense ranking.
+        lexical_weight (default RetrievalConfig.lexical_weight) above 0: the ranking of the dense scores blended with the
+        BM25 scores of the query strings (HippoRAGEngine.dense_retrieve(lexical=)); then not with group_by, mmr_lambda,
+        filter_scope="seeds" or more documents than the engine's max_topk (ValueError naming lexical_weight)."""
         cfg = self.global_config
         if num_to_retrieve is None:
             num_to_retrieve = cfg.retrieval_top_k
@@ -1551,6 +1630,13 @@ class HippoRAG:
                 raise ValueError(f"mmr_candidates={c} (at least num_to_retrieve) exceeds the engine's max_topk={eng.max_topk}: "
                                  f"MMR picks from one device ranking of at most min({MMR_MAX_CANDIDATES}, max_topk) entries")
             mmr = {"mmr_lambda": lam, "mmr_candidates": c}
+        lex = self._lexical(lexical_weight)
+        if lex:
+            for name, on in (("group_by", agg is not None), ("mmr_lambda", bool(mmr)), ('filter_scope="seeds"', scope == "seeds"),
+                             (f"num_to_retrieve above max_topk={eng.max_topk}", beyond)):
+                if on:
+                    raise ValueError(f"retrieve_dpr does not serve lexical_weight={lex['lexical_weight']} with {name}: the "
+                                     "blended rows are ranked once on the device -- use retrieve(lexical_weight=...)")
 
         def rows_of(lo, b):                 # the packed filter rows of queries [lo, lo + b)
             return words if words.ndim == 1 else words[lo: lo + b]
@@ -1567,6 +1653,8 @@ class HippoRAG:
                     extra["group_hits"] = hits
                 gi, sc, idx, *h = eng.dense_retrieve(self._q_tensor(qs, "passage"), k=k_docs, group_agg=agg, **extra, **mmr)
                 return (qs, host_copy_async(idx), host_copy_async(sc), host_copy_async(gi)) + tuple(map(host_copy_async, h))
+            if lex:
+                extra.update(lexical=lex["lexical_encode"](qs), lexical_weight=lex["lexical_weight"])
             idx, sc, *h = eng.dense_retrieve(self._q_tensor(qs, "passage"), k=k_docs, **extra, **mmr)
             return (qs, host_copy_async(idx), host_copy_async(sc)) + ((None,) + tuple(map(host_copy_async, h)) if h else ())
 
@@ -1616,18 +1704,21 @@ class HippoRAG:
                     results.append(QuerySolution(question=r.query, docs=r.docs, doc_scores=r.scores,
                                                  doc_metadata=r.doc_metadata))
             self._mmr_metadata(results[first:], values)
+            self._lexical_metadata(results[first:], lex)
         if gold_docs is not None:
             return results, self._recall(gold_docs, [r.docs for r in results])
         return results
 
     # ------------------------------------------------------------------ rag_qa :591-663
     def rag_qa(self, queries, gold_docs: Optional[List[List[str]]] = None,
-               gold_answers: Optional[List[List[str]]] = None, doc_filter=None, filter_scope: Optional[str] = None):
+               gold_answers: Optional[List[List[str]]] = None, doc_filter=None, filter_scope: Optional[str] = None,
+               lexical_weight: Optional[float] = None):
         if self.qa_fn is None:
             raise NotImplementedError("rag_qa needs a qa_fn (the reader LLM is outside this package)")
         retrieval_metrics = None
         if not isinstance(queries[0], QuerySolution):
-            out = self.retrieve(queries=queries, gold_docs=gold_docs, doc_filter=doc_filter, filter_scope=filter_scope)
+            out = self.retrieve(queries=queries, gold_docs=gold_docs, doc_filter=doc_filter, filter_scope=filter_scope,
+                                lexical_weight=lexical_weight)
             queries, retrieval_metrics = out if gold_docs is not None else (out, None)
         solutions, messages, metadata = self.qa_fn(queries)
         if gold_answers is not None:

@@ -70,7 +70,9 @@ extern "C" {
  *        later in 0.8 (detect by the symbol): fused retrieval -- hrag_fuse_rows, hrag_rrf_rows,
  *        hrag_fuse_workspace_bytes, hrag_last_fused;
  *        later in 0.8 (detect by the symbol): diversified retrieval -- hrag_gram_rows, hrag_mmr_rows,
- *        hrag_mmr_workspace_bytes, hrag_mmr, hrag_mmr_sel. */
+ *        hrag_mmr_workspace_bytes, hrag_mmr, hrag_mmr_sel;
+ *        later in 0.8 (detect by the symbol): lexical retrieval -- hrag_lex_create, hrag_lex_destroy, hrag_lex_scores,
+ *        hrag_lex_blend_rows. */
 #define HRAG_VERSION_MAJOR 0
 #define HRAG_VERSION_MINOR 8
 
@@ -818,6 +820,74 @@ hrag_status hrag_mmr_sel(hrag_engine *e, const int32_t *cand_idx_dev, const floa
                          int32_t k, float lambda, int32_t normalize, int32_t *sel_out_dev, int32_t *idx_out_dev,
                          float *score_out_dev, float *value_out_dev, void *workspace_dev, size_t workspace_bytes,
                          hrag_stream stream);
+
+/* ---- lexical retrieval: sparse-vector (BM25, learned term weights) scores blended into the dense scores ----
+ * Every score above starts from the cosine of dense embeddings, which smears the rare surface forms a multi-hop question
+ * turns on -- a name, a product code, a year.  An exact term match does not.  A LEXICAL INDEX holds, for each of n_terms
+ * terms, the passages that contain it with a weight each (the posting list of the term); a sparse query is a list of
+ * (term, weight) pairs.  The library knows nothing about BM25: it scores whatever weights it is given (negative ones
+ * included: learned sparse models produce them).  For query b and passage p the score is the fp64 chain
+ *
+ *   acc = +0.0
+ *   for j in q_ptr[b] .. q_ptr[b+1] - 1, in list order:
+ *       if passage p is in the posting list of q_term[j]:
+ *           acc += (double)q_weight[j] * (double)post_w[that entry]
+ *
+ * rounded once to fp32.  The product of two fp32 values is exact in fp64.  A passage that no query term lists scores
+ * +0.0.  A term id outside [0, n_terms) contributes nothing.  A term repeated within a query contributes once per
+ * occurrence, in list order.  At most HRAG_LEX_MAX_QUERY_TERMS terms of a query are read: a device-side q_ptr cannot be
+ * checked on the host, so the terms of a longer list beyond the cap are IGNORED (a caller that must not lose terms checks
+ * the lengths itself, as the Python binding does); whatever q_ptr holds, only q_term / q_weight [0, q_nnz) are read and
+ * nothing outside the output rows is written.  A NaN or inf q_weight propagates by IEEE rules; a NaN result is the quiet
+ * NaN 0x7fc00000, as in hrag_fuse_rows.  No atomics, no read-modify-write of global memory: every value is one chain in a
+ * fixed order and every column is written exactly once, bitwise reproducible (csrc/lex.hip: one workgroup per query and
+ * tile of HRAG_LEX_TILE consecutive passages, the tile's fp64 accumulators in LDS).
+ *
+ * THE BLEND of a dense row d and a lexical row l with a weight alpha in [0, 1], per row:
+ *   alpha == 0, or the lexical row has no range (mx_l == mn_l, or it holds no number -- a query none of whose terms match
+ *   is the common case): the output row is the dense row BIT FOR BIT;
+ *   otherwise nd = (d - mn_d) / (mx_d - mn_d) and nl = (l - mn_l) / (mx_l - mn_l), one fp32 subtraction and one fp32
+ *   division each, a zero range giving 1.0f (min_max_normalize, misc_utils.py:130-139: the min-max of every kernel here),
+ *   and out = (float)((double)(1.0f - alpha) * (double)nd + (double)alpha * (double)nl): two exact products, one fp64
+ *   add, one rounding; a NaN result is the quiet NaN.
+ * The blended rows are raw passage scores for hrag_retrieve_scored* (or for a ranking), and hrag_retrieve_scored min-max
+ * normalises its rows AGAIN when it forms the passage prior and the DPR fallback.  That composition -- minmax(blend of
+ * the two min-maxes) -- IS the definition of the lexical prior; it is not an approximation of some other formula.
+ * Everything hrag_retrieve_scored* serves (the doc filter in the "ranking" scope, grouping, group hits) and everything
+ * behind it (hrag_last_fused, hrag_mmr) therefore composes with no further entry point.  Rank-level blending (RRF of the
+ * dense and the lexical ranking) is not a separate mode: hrag_rrf_rows serves a caller who ranks both rows themself. */
+#define HRAG_LEX_TILE 2048               /* passages per workgroup tile of hrag_lex_scores (tests pick their sizes by it) */
+#define HRAG_LEX_MAX_QUERY_TERMS 256     /* terms of one query that hrag_lex_scores reads */
+
+typedef struct hrag_lex hrag_lex; /* opaque; independent of any engine: engines and workspaces over the same passages share one */
+
+/* The index from HOST arrays in inverted form: the posting list of term t is post_doc[term_ptr[t] : term_ptr[t + 1]]
+ * (passage positions) with the weights post_w at the same places; term_ptr int64 [n_terms + 1].  Validated on the host,
+ * then copied to the current device (the arrays may be freed right after).  HRAG_EINVAL, and nothing is allocated, unless
+ * term_ptr[0] == 0 and term_ptr is non-decreasing, every passage position lies in [0, n_passages) and the positions of a
+ * list are strictly ascending, and every weight is finite; 1 <= n_passages < 2^31, 0 <= n_terms < 2^31. */
+hrag_status hrag_lex_create(int64_t n_passages, int64_t n_terms, const int64_t *term_ptr, const int32_t *post_doc,
+                            const float *post_w, hrag_lex **out);
+hrag_status hrag_lex_destroy(hrag_lex *lex);
+
+/* The score rows of `batch` sparse queries in device CSR form -- q_ptr_dev int32 [batch + 1], q_term_dev int32 and
+ * q_weight_dev fp32 [q_nnz] -- by the chain above: out_dev fp32 [batch, ld], ld >= n_passages, every one of the
+ * n_passages columns written, the columns n_passages .. ld not touched.  min_out_dev / max_out_dev fp32 [batch] (both or
+ * both NULL): the row min / max of the result exactly as hrag_row_minmax gives them (fminf / fmaxf, NaN skipped).
+ * Enqueues on `stream`; nothing is allocated, synchronised or read back.  Any number of calls may read one index at the
+ * same time. */
+hrag_status hrag_lex_scores(const hrag_lex *lex, const int32_t *q_ptr_dev, const int32_t *q_term_dev,
+                            const float *q_weight_dev, int64_t q_nnz, int32_t batch, float *out_dev, int64_t ld,
+                            float *min_out_dev, float *max_out_dev, hrag_stream stream);
+
+/* The blend above, engine-free: dense_dev fp32 [batch, ld_d] and lex_dev fp32 [batch, ld_l] with n valid columns, the
+ * per-row mn_d / mx_d / mn_l / mx_l fp32 [batch] on the device (as hrag_row_minmax and hrag_lex_scores write them), out_dev
+ * fp32 [batch, ld_o]; out_dev may BE dense_dev (then ld_o == ld_d).  The columns n .. ld_o are not touched.  Enqueues on
+ * `stream`; nothing is allocated, synchronised or read back.  HRAG_EINVAL: alpha outside [0, 1] or not finite, a NULL
+ * pointer, batch outside [1, 65535], a row stride below n. */
+hrag_status hrag_lex_blend_rows(const float *dense_dev, int64_t ld_d, const float *lex_dev, int64_t ld_l, int32_t batch,
+                                int64_t n, const float *mn_d_dev, const float *mx_d_dev, const float *mn_l_dev,
+                                const float *mx_l_dev, float alpha, float *out_dev, int64_t ld_o, hrag_stream stream);
 
 /* ---- lower-level seams (used by the per-method adapters and by the parity tests) ---- */
 
