@@ -12,6 +12,11 @@ LIB_PATH = os.path.join(_HERE, "libhrag.so")
 HRAG_OK, HRAG_EINVAL, HRAG_ENOMEM, HRAG_EHIP, HRAG_EBUSY, HRAG_ECAPACITY = range(6)
 SEED_STRIDE = 32
 LEX_TILE, LEX_MAX_QUERY_TERMS = 2048, 256     # HRAG_LEX_TILE / HRAG_LEX_MAX_QUERY_TERMS of include/hrag.h
+# HRAG_PAY_* of include/hrag.h (payload filters): tile, caps, column types, clause roles and kinds (c_op = role | kind << 8)
+PAY_TILE, PAY_MAX_CLAUSES, PAY_MAX_COLS = 2048, 64, 256
+PAY_I64, PAY_F64 = 0, 1
+PAY_MUST, PAY_MUST_NOT, PAY_SHOULD = 0, 1, 2
+PAY_RANGE, PAY_IN, PAY_PRESENT = 0, 1, 2
 HRAG_VERSION = 8      # HRAG_VERSION_MAJOR * 1000 + HRAG_VERSION_MINOR of include/hrag.h
 FLAG_DPR_FALLBACK, FLAG_ZERO_MASS, FLAG_ZERO_PHRASE, FLAG_FP8_SATURATED, FLAG_NOT_CONVERGED = 1, 2, 4, 8, 16
 # the convergence contract's error bound (include/hrag.h): error <= max(PPR_ERR_K * residual, floor of the state type);
@@ -153,6 +158,10 @@ SIGNATURES = {
     "hrag_lex_destroy": (C.c_int, [_P]),
     "hrag_lex_scores": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, _I64, _P, _P, _P]),
     "hrag_lex_blend_rows": (C.c_int, [_P, _I64, _P, _I64, _I32, _I64, _P, _P, _P, _P, _F32, _P, _I64, _P]),
+    "hrag_payload_create": (C.c_int, [_I64, _I32, _P, _P, _P, C.POINTER(_P)]),
+    "hrag_payload_destroy": (C.c_int, [_P]),
+    "hrag_payload_filter": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I32, _P, _I64, _P, _I64, _P]),
+    "hrag_bitset_count_rows": (C.c_int, [_P, _I64, _I64, _I32, _P, _P]),
     "hrag_ppr_sweeps": (C.c_int, [_P, _I32, _I32, _F32, _I32, _P]),
     "hrag_ppr_layout": (C.c_int, [_P, _I32, C.POINTER(_I32), C.POINTER(_I32)]),
     "hrag_row_minmax": (C.c_int, [_P, _I32, _I64, _I64, _P, _P, _P]),

@@ -19,6 +19,7 @@ from ._lib import (EmbedDesc, FactDesc, GraphDesc, Opts, ShardLayout, Timings, c
                    FLAG_FP8_SATURATED, FLAG_ZERO_MASS, FLAG_ZERO_PHRASE, SEED_STRIDE)
 from .graph import CSRGraph
 from .lexical import invert_postings
+from .payload import PayloadFilter, PayloadIndex, compile_filters     # noqa: F401  (re-exported: the payload filters)
 
 
 def _torch():
@@ -706,6 +707,7 @@ class HippoRAGEngine:
         w._workspaces = []
         w._parent = root
         w._fuse_ws = w._fuse_host = w._mmr_ws = None         # last_fused / mmr: scratch buffers of its own
+        w._pay_words = None                                  # ... and the words of a PayloadFilter doc filter
         with _torch().cuda.device(root.device):
             check(root._lib.hrag_workspace_create(root._handle, C.byref(w._handle)))
         if not hasattr(root, "_workspaces"):
@@ -807,7 +809,7 @@ class HippoRAGEngine:
             check(self._lib.hrag_score_facts(self._handle, q.data_ptr(), b, k, idx.data_ptr(), sc.data_ptr(),
                                              _stream()))
         else:
-            fw, fld = doc_filter_words(scope_filter, self.n_passages, b, self.device)
+            fw, fld = self._filter_words(scope_filter, b, "scope_filter")
             check(self._lib.hrag_score_facts_scoped(self._handle, q.data_ptr(), b, k, idx.data_ptr(), sc.data_ptr(),
                                                     _stream(), fw.data_ptr(), fld))
         return idx, sc
@@ -887,7 +889,7 @@ class HippoRAGEngine:
                 out.residual, out.iters_used = self._empty((b,), torch.float32), self._empty((b,), torch.int32)
             tail = (out.flags.data_ptr(), out.residual.data_ptr() if report else None,
                     out.iters_used.data_ptr() if report else None, _stream())
-        fw, fld = (None, 0) if doc_filter is None else doc_filter_words(doc_filter, self.n_passages, b, self.device)
+        fw, fld = (None, 0) if doc_filter is None else self._filter_words(doc_filter, b)
         docs = (out.doc_idx.data_ptr(), out.doc_score.data_ptr())
         if agg is not None:     # the ungrouped ranking is left out; its two tensors carry the group scores / representatives
             out.group_idx = self._empty((b, k), torch.int32)
@@ -906,6 +908,41 @@ class HippoRAGEngine:
         if mmr is not None:
             self._mmr_picks(out, k_out, mmr[0])
         return out
+
+    # ------------------------------------------------------------------ payload filters
+    def set_payload_index(self, ix: Optional["PayloadIndex"]):
+        """The PayloadIndex that doc_filter=PayloadFilter / scope_filter=PayloadFilter calls of this engine and of its
+        workspaces evaluate against (None: none; include/hrag.h, payload filters).  Held by reference on the Python side
+        only: the library's engine does not know it, and closing it is the caller's."""
+        root = getattr(self, "_parent", None) or self
+        if ix is not None:
+            if ix.n_passages != root.n_passages:
+                raise ValueError(f"the payload index covers {ix.n_passages} passages, the engine {root.n_passages}")
+            if ix.device != root.device:
+                raise ValueError(f"the payload index lives on {ix.device}, the engine on {root.device}")
+        root._payload_index = ix
+
+    def _filter_words(self, doc_filter, batch: int, name: str = "doc_filter", own: bool = False):
+        """(int32 device words, filter_ld_words) of a doc filter: doc_filter_words for a tensor; a PayloadFilter
+        (payload.compile_filters) is evaluated on the device (hrag_payload_filter) into this handle's [max_batch, W] scratch,
+        allocated on first use -- own: into a tensor of its own, for a caller that reads the words after later calls."""
+        if not isinstance(doc_filter, PayloadFilter):
+            return doc_filter_words(doc_filter, self.n_passages, batch, self.device)
+        ix = getattr(getattr(self, "_parent", None) or self, "_payload_index", None)
+        if ix is None or not ix._handle.value:
+            raise ValueError(f"{name}: a PayloadFilter needs a payload index on this engine (set_payload_index)")
+        if doc_filter.n_passages != self.n_passages:
+            raise ValueError(f"{name}: the PayloadFilter was compiled for {doc_filter.n_passages} passages, the engine ranks "
+                             f"{self.n_passages}")
+        if not doc_filter.broadcast and doc_filter.batch != batch:
+            raise ValueError(f"{name}: the PayloadFilter holds {doc_filter.batch} queries, the call {batch}")
+        out = None
+        if not own and doc_filter.batch <= self.max_batch:
+            out = getattr(self, "_pay_words", None)
+            if out is None:
+                out = self._pay_words = self._empty((self.max_batch, ix.words), _torch().int32)
+        words = ix.evaluate(doc_filter, out=out)
+        return words, (0 if doc_filter.broadcast else words.stride(0))
 
     # ------------------------------------------------------------------ lexical retrieval
     def set_lexical_index(self, ix: Optional["LexicalIndex"]):
@@ -996,7 +1033,7 @@ class HippoRAGEngine:
             check(self._lib.hrag_topk_rows_ws(rows.data_ptr(), b, n, rows.stride(0), k, 0, 1 if normalize else 0,
                                               idx.data_ptr(), val.data_ptr(), None, None, ws, max(need, 0), _stream()))
         else:
-            fw, fld = doc_filter_words(doc_filter, n, b, self.device)
+            fw, fld = self._filter_words(doc_filter, b)
             check(self._lib.hrag_topk_rows_masked(rows.data_ptr(), b, n, rows.stride(0), k, 0, 1 if normalize else 0,
                                                   fw.data_ptr(), fld, 0, idx.data_ptr(), val.data_ptr(), None, None, ws,
                                                   max(need, 0), _stream()))
@@ -1091,7 +1128,7 @@ class HippoRAGEngine:
         mode, mp, w, c, depth = check_fuse(fuse, member_ptr, b, weights, rrf_c,
                                            min(k, dmax) if rrf_depth is None else rrf_depth, dmax)
         nq = mp.shape[0] - 1
-        fw, fld = (None, 0) if doc_filter is None else doc_filter_words(doc_filter, self.n_passages, nq, self.device)
+        fw, fld = (None, 0) if doc_filter is None else self._filter_words(doc_filter, nq)
         need = int(self._lib.hrag_fuse_workspace_bytes(b, self.n_passages, mode, depth, 1 if fld else 0))
         if need < 0:
             raise ValueError(f"hrag_fuse_workspace_bytes rejects batch={b}, mode={fuse!r}, depth={depth}")
@@ -1161,8 +1198,8 @@ class HippoRAGEngine:
         # rows of them (a repeat never re-encodes or re-slices the sparse queries)
         blended = None if lexical is None else self._lexical_blend(None, q, lexical, lexical_weight,
                                                                    kw.get("filter_scope", "ranking"), doc_filter)
-        fw, fld = (None, 0) if doc_filter is None else doc_filter_words(doc_filter, self.n_passages, q.shape[0],
-                                                                        self.device)
+        # (a PayloadFilter is evaluated ONCE, into words of its own: the repeats of finish() read them after later calls)
+        fw, fld = (None, 0) if doc_filter is None else self._filter_words(doc_filter, q.shape[0], own=True)
 
         def run(rows=None, iters=ppr_iters, max_iters=ppr_max_iters):
             sel = slice(None) if rows is None else rows

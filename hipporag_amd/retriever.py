@@ -202,6 +202,10 @@ class RetrievalConfig:
                                          # retrieve_ircot(); 0: nothing is built and nothing changes
     lexical_tokenize_fn: Optional[Callable] = None   # str -> list of tokens, for passages and queries alike; None:
                                          # lexical.default_tokenize (lower-case, \w+)
+    payload_index: bool = False          # payload filters (include/hrag.h): the chunk metadata (source_id included) as typed
+                                         # columns on the device; metadata dict filters are then evaluated there and may use
+                                         # $gt / $gte / $lt / $lte / $exists / $not / $any (payload.compile_filters); False:
+                                         # the host bitsets, equality only
 
 
 def identity_rerank_filter(query, candidate_items, candidate_indices, len_after_rerank=None):
@@ -667,6 +671,7 @@ class HippoRAG:
         self._pass_emb = self._fact_emb = None             # fp32 rows in store order
         self._arrays = None
         self.lexical_model = self.lexical_index = None     # lexical retrieval (lexical_weight > 0): built with the engine
+        self.payload_index = None                          # payload filters (payload_index=True): built with the engine
 
     # ------------------------------------------------------------------ index side
     def index_from_openie(self, docs: Sequence, chunk_triples: Sequence[Sequence[Sequence[str]]],
@@ -924,6 +929,7 @@ class HippoRAG:
             if has_facts and held["facts"]:
                 fe = compose("facts", self.fact_node_keys, a["fact_emb"], held["facts"])
         self._drop_lexical()
+        self._drop_payload()
         if old is not None:
             # the gathered matrices no longer depend on the old engine: free its index before the new one is built
             # (peak device memory = one index + the embedding matrices, not two indexes)
@@ -958,7 +964,42 @@ class HippoRAG:
         self.passage_node_idxs = a["passage_vertex"].tolist()
         if self.global_config.lexical_weight > 0:
             self._build_lexical()
+        if self.global_config.payload_index:
+            self._build_payload()
         self.ready_to_retrieve = True
+
+    # ------------------------------------------------------------------ payload filters
+    def _drop_payload(self):
+        ix = getattr(self, "payload_index", None)
+        if ix is not None:
+            ix.close()
+        self.payload_index = None
+
+    def payload_columns(self) -> dict:
+        """The chunk metadata (source_id included) as columns over the passages, key -> one value (or None) per passage in
+        passage_node_keys order: every key payload.encode_columns accepts.  A key whose values it rejects (str mixed with
+        numbers, an unhashable value) is left out and stays with the host path."""
+        from .payload import _encode_column
+        meta = self.chunk_metadata
+        rows = [meta.get(k, {}) for k in self.passage_node_keys]
+        cols = {}
+        for key in dict.fromkeys(k for m in rows for k in m):
+            col = [m.get(key) for m in rows]
+            try:
+                _encode_column(key, col, len(rows))
+            except ValueError:
+                continue
+            cols[key] = col
+        return cols
+
+    def _build_payload(self):
+        """The payload index of the passages the mirror holds, on the engine's device.  prepare_retrieval_objects rebuilds
+        it after index() / delete(), where the lexical model is rebuilt."""
+        from .payload import PayloadIndex
+        self._drop_payload()
+        if self.passage_node_keys:
+            self.payload_index = PayloadIndex.from_columns(self.payload_columns(), len(self.passage_node_keys),
+                                                           device=self.engine.device.index)
 
     # ------------------------------------------------------------------ lexical retrieval
     def _drop_lexical(self):
@@ -1117,6 +1158,7 @@ class HippoRAG:
         if isinstance(f, dict):
             words = np.full((n + 31) // 32, 0xFFFFFFFF, np.uint32)
             for key, values in f.items():               # keys: AND; the values of one key: OR
+                self._refuse_operators(key, values)
                 alts = values if isinstance(values, (list, tuple, set, frozenset)) else [values]
                 any_of = np.zeros_like(words)
                 for v in alts:
@@ -1131,14 +1173,54 @@ class HippoRAG:
             return pack_mask(f)
         raise TypeError(f"doc_filter of type {type(f).__name__}: a metadata dict, a bool numpy array, or a list of those")
 
+    @staticmethod
+    def _refuse_operators(key, values) -> None:
+        """The host path matches equality only: a $ key or $ operator raises instead of silently matching nothing."""
+        if (isinstance(key, str) and key.startswith("$")) or (
+                isinstance(values, dict) and any(isinstance(k, str) and k.startswith("$") for k in values)):
+            raise ValueError(f"doc_filter: {key!r}: the $ operators need RetrievalConfig.payload_index=True and a key its "
+                             "columns hold (payload_columns); the host path matches equality only")
+
+    def _payload_filter_words(self, filters: list, broadcast: bool) -> np.ndarray:
+        """The words of dict / bool-array / None filters with the dicts evaluated on the device (one hrag_payload_filter
+        call, one copy back): per query, the keys the payload index holds -- and $not / $any -- go into the clause program;
+        the other keys (equality only) and a bool array go through the host path into the base row."""
+        import torch
+        ix = self.payload_index
+        n = len(self.passage_node_keys)
+        progs, base, any_base = [], np.full((len(filters), (n + 31) // 32), 0xFFFFFFFF, np.uint32), False
+        for i, f in enumerate(filters):
+            if not isinstance(f, dict):
+                base[i] = self._filter_words(f)            # a bool array (or the TypeError of anything else)
+                progs.append(None)
+                any_base = True
+                continue
+            host = {k: v for k, v in f.items() if not (isinstance(k, str) and k.startswith("$")) and k not in ix.names}
+            if host:
+                base[i] = self._filter_words(host)          # (a $ operator on such a key raises there)
+                any_base = True
+            progs.append({k: v for k, v in f.items() if k not in host})
+        from .payload import compile_filters
+        pf = compile_filters(ix, progs[0] if broadcast else progs)
+        and_with = None
+        if any_base:
+            and_with = torch.from_numpy((base[0] if broadcast else base).view(np.int32)).to(ix.device)
+        words = ix.evaluate(pf, and_with=and_with)
+        return np.ascontiguousarray(words.cpu().numpy()).view(np.uint32)
+
     def _doc_filter_words(self, doc_filter, n_queries: int) -> Optional[np.ndarray]:
         """doc_filter as the engine takes it: None, packed [W] (one filter for the batch, sent as one broadcast row) or
-        [n_queries, W] (a list: one filter per query)."""
+        [n_queries, W] (a list: one filter per query).  With RetrievalConfig.payload_index the metadata dicts are evaluated
+        on the device (_payload_filter_words)."""
         if doc_filter is None:
             return None
+        if isinstance(doc_filter, list) and len(doc_filter) != n_queries:
+            raise ValueError(f"doc_filter list of {len(doc_filter)} entries for {n_queries} queries")
+        if getattr(self, "payload_index", None) is not None:
+            per = doc_filter if isinstance(doc_filter, list) else [doc_filter]
+            if per and any(isinstance(f, dict) for f in per):
+                return self._payload_filter_words(per, not isinstance(doc_filter, list))
         if isinstance(doc_filter, list):
-            if len(doc_filter) != n_queries:
-                raise ValueError(f"doc_filter list of {len(doc_filter)} entries for {n_queries} queries")
             w = (len(self.passage_node_keys) + 31) // 32
             return (np.stack([self._filter_words(f) for f in doc_filter]) if doc_filter
                     else np.zeros((0, w), np.uint32))

@@ -72,7 +72,9 @@ extern "C" {
  *        later in 0.8 (detect by the symbol): diversified retrieval -- hrag_gram_rows, hrag_mmr_rows,
  *        hrag_mmr_workspace_bytes, hrag_mmr, hrag_mmr_sel;
  *        later in 0.8 (detect by the symbol): lexical retrieval -- hrag_lex_create, hrag_lex_destroy, hrag_lex_scores,
- *        hrag_lex_blend_rows. */
+ *        hrag_lex_blend_rows;
+ *        later in 0.8 (detect by the symbol): payload filters -- hrag_payload_create, hrag_payload_destroy,
+ *        hrag_payload_filter, hrag_bitset_count_rows. */
 #define HRAG_VERSION_MAJOR 0
 #define HRAG_VERSION_MINOR 8
 
@@ -888,6 +890,88 @@ hrag_status hrag_lex_scores(const hrag_lex *lex, const int32_t *q_ptr_dev, const
 hrag_status hrag_lex_blend_rows(const float *dense_dev, int64_t ld_d, const float *lex_dev, int64_t ld_l, int32_t batch,
                                 int64_t n, const float *mn_d_dev, const float *mx_d_dev, const float *mn_l_dev,
                                 const float *mx_l_dev, float alpha, float *out_dev, int64_t ld_o, hrag_stream stream);
+
+/* ---- payload filters: metadata conditions evaluated on the device into a doc filter ----
+ * Every filtered entry point above takes the doc filter as a finished bitset.  A PAYLOAD INDEX holds typed per-passage
+ * columns on the device, and hrag_payload_filter evaluates a small per-query clause program over them straight into the
+ * packed words of that bitset (bit p & 31 of word p >> 5): its output is an ordinary doc filter, so everything that takes
+ * one composes with no further entry point.
+ *
+ * A column is HRAG_PAY_I64 (int64: integers, bools, the dictionary codes of keyword strings) or HRAG_PAY_F64 (IEEE
+ * doubles; NaN and +-inf are legal values), 8 bytes per passage, with an optional presence bitset in the doc filter's
+ * format (NULL: every passage has a value).
+ *
+ * Query b owns the clauses f_ptr[b] .. f_ptr[b + 1] (int32).  Clause j names a column c_col[j], an operation
+ * c_op[j] = role | kind << 8, two 8-byte bounds c_lo[j] / c_hi[j] and the slice c_set_ptr[j] .. c_set_ptr[j + 1] of
+ * set_vals.  For passage p and the value x of the clause's column there:
+ *   HRAG_PAY_RANGE    lo <= x && x <= hi in the column's type: signed int64 compares on an I64 column; double compares on
+ *                     an F64 column, the bounds being the doubles' bit patterns.  A NaN value is in no range.
+ *   HRAG_PAY_IN       x equals one of the slice's values.  The slice is sorted ascending in the column's order and matched
+ *                     by binary search, with equality in the column's type: -0.0 matches 0.0, NaN matches nothing.
+ *   HRAG_PAY_PRESENT  the passage has a value.
+ *   hit(j, p) = present(column, p) && test.  A missing value hits nothing, so HRAG_PAY_MUST_NOT of it lets the passage
+ *   through.
+ *   allowed(b, p) = base(b, p) && every MUST clause hits && no MUST_NOT clause hits && (no SHOULD clause || some SHOULD
+ *   clause hits).
+ * base is and_words_dev: [batch, ld_a] words, or one row for the batch when ld_a == 0, or all ones when NULL.  A query
+ * with no clauses gives its base row.  The bits at positions >= n_passages of the last word are 0; the words
+ * ceil(n_passages / 32) .. ld_o of a row are not touched.  out_words_dev must not overlap and_words_dev.
+ *
+ * The clause arrays live on the device and cannot be checked on the host, so the definition covers bad input:
+ *   - whatever f_ptr / c_set_ptr hold, only the clauses [0, n_clauses) and the values [0, set_nnz) are ever read: both
+ *     ends of a range are clamped (a descending pair is empty), as hrag_lex_scores clamps q_ptr;
+ *   - at most HRAG_PAY_MAX_CLAUSES clauses of a query are read, the rest are IGNORED (a caller that must not lose clauses
+ *     checks the lengths itself, as the Python binding does);
+ *   - a column id outside [0, n_cols), an unknown kind or role (or any bit above the two bytes of c_op), or lo > hi (a NaN
+ *     bound included) makes a clause that hits nothing; a clause with an unknown role counts as a MUST, so its query allows
+ *     nothing.
+ * No atomics, no read-modify-write of global memory; every output word is written exactly once (csrc/payload.hip: one
+ * workgroup per query and tile of HRAG_PAY_TILE consecutive passages, the verdicts packed by the 64-bit wave ballot).
+ *
+ * OUT OF SCOPE: term clauses over the lexical index ("the passage contains term t"; the kind byte leaves room for one),
+ * multi-valued fields (tag lists), nested boolean groups, keyword ranges and prefix matches, evaluation inside the row-shard,
+ * hybrid or captured forms (they take the finished words), and a doc filter that stays on the device through the mirror. */
+#define HRAG_PAY_TILE 2048               /* passages per workgroup tile of hrag_payload_filter (tests pick their sizes by it) */
+#define HRAG_PAY_MAX_CLAUSES 64          /* clauses of one query that hrag_payload_filter reads */
+#define HRAG_PAY_MAX_COLS 256            /* columns of one payload index */
+#define HRAG_PAY_I64 0                   /* column types */
+#define HRAG_PAY_F64 1
+#define HRAG_PAY_MUST 0                  /* clause roles: the low byte of c_op */
+#define HRAG_PAY_MUST_NOT 1
+#define HRAG_PAY_SHOULD 2
+#define HRAG_PAY_RANGE 0                 /* clause kinds: the second byte of c_op */
+#define HRAG_PAY_IN 1
+#define HRAG_PAY_PRESENT 2
+
+typedef struct hrag_payload hrag_payload; /* opaque; independent of any engine: engines and workspaces over the same passages share one */
+
+/* The index from HOST arrays: col_type int32 [n_cols]; col_values[c] the 8-byte values [n_passages] of column c;
+ * col_present[c] packed uint32 [ceil(n_passages / 32)], or NULL (as may be col_present itself) for "every passage has a
+ * value".  Validated on the host, then copied to the current device (the arrays may be freed right after).  HRAG_EINVAL, and
+ * nothing is allocated, unless 1 <= n_passages < 2^31, 0 <= n_cols <= HRAG_PAY_MAX_COLS, every type is known and every
+ * value pointer is not NULL. */
+hrag_status hrag_payload_create(int64_t n_passages, int32_t n_cols, const int32_t *col_type, const void *const *col_values,
+                                const uint32_t *const *col_present, hrag_payload **out);
+hrag_status hrag_payload_destroy(hrag_payload *pay);
+
+/* The doc filter rows of `batch` clause programs by the definition above: f_ptr_dev int32 [batch + 1]; c_col_dev / c_op_dev
+ * int32, c_lo_dev / c_hi_dev int64 [n_clauses]; c_set_ptr_dev int32 [n_clauses + 1]; set_vals_dev int64 [set_nnz] (the
+ * clause arrays may be NULL when n_clauses == 0, set_vals_dev when set_nnz == 0); out_words_dev uint32 [batch, ld_o].
+ * Enqueues on `stream`; nothing is allocated, synchronised or read back.  Any number of calls may read one index at the
+ * same time.  HRAG_EINVAL: a NULL handle or output, batch outside [1, 65535], ld_o < ceil(n_passages / 32), ld_a neither 0
+ * nor >= ceil(n_passages / 32), a negative count. */
+hrag_status hrag_payload_filter(const hrag_payload *pay, const int32_t *f_ptr_dev, const int32_t *c_col_dev,
+                                const int32_t *c_op_dev, const int64_t *c_lo_dev, const int64_t *c_hi_dev,
+                                const int32_t *c_set_ptr_dev, const int64_t *set_vals_dev, int64_t n_clauses, int64_t set_nnz,
+                                int32_t batch, const uint32_t *and_words_dev, int64_t ld_a, uint32_t *out_words_dev,
+                                int64_t ld_o, hrag_stream stream);
+
+/* How many passages a doc filter leaves: count_out_dev int32 [batch], the number of set bits among the first n of each row
+ * of words_dev uint32 [batch, ld] (ld >= ceil(n / 32), or 0: one row, counted for every entry).  Engine-free and for ANY doc
+ * filter -- the count call of the vector stores, what a caller needs to size k.  One workgroup per row, no atomics.
+ * Enqueues on `stream`. */
+hrag_status hrag_bitset_count_rows(const uint32_t *words_dev, int64_t ld, int64_t n, int32_t batch, int32_t *count_out_dev,
+                                   hrag_stream stream);
 
 /* ---- lower-level seams (used by the per-method adapters and by the parity tests) ---- */
 
