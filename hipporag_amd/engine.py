@@ -843,11 +843,13 @@ class HippoRAGEngine:
         the doc filter (scope "ranking"), group_agg, group_hits, mmr_* and a following last_fused work as they do there.  A
         query whose terms match nothing keeps its dense row bit for bit.  None: the call is exactly the plain one."""
         if lexical is not None:
+            mmr = mmr_plan(mmr_lambda, mmr_candidates, k)     # (refused before the blend is enqueued)
+            self._check_mmr_fits(mmr)
             rows = self._lexical_blend(None, q_pass, lexical, lexical_weight, filter_scope, doc_filter)
             return self._retrieve("hrag_retrieve_scored", rows, (kept_idx, kept_score, kept_count),
                                   (link_top_k, damping, passage_node_weight, ppr_iters, max(ppr_max_iters, ppr_iters), ppr_tol),
                                   k, want_residual or ppr_tol > 0, doc_filter=doc_filter, filter_scope=filter_scope,
-                                  group_agg=group_agg, group_hits=group_hits, mmr=mmr_plan(mmr_lambda, mmr_candidates, k))
+                                  group_agg=group_agg, group_hits=group_hits, mmr=mmr)
         return self._retrieve("hrag_retrieve", q_pass, (kept_idx, kept_score, kept_count),
                               (link_top_k, damping, passage_node_weight, ppr_iters, max(ppr_max_iters, ppr_iters), ppr_tol), k,
                               want_residual or ppr_tol > 0, doc_filter=doc_filter, filter_scope=filter_scope,
@@ -862,6 +864,7 @@ class HippoRAGEngine:
         mmr: None or mmr_plan's (lambda, c): c entries are ranked and _mmr_picks keeps k of them."""
         torch = _torch()
         k_out, k = k, (k if mmr is None else mmr[1])
+        self._check_mmr_fits(mmr)
         scoped = check_filter_scope(filter_scope, doc_filter)
         agg = check_group_agg(group_agg)
         hits = check_group_hits(group_hits, group_agg)
@@ -1081,6 +1084,12 @@ class HippoRAGEngine:
                                          ws.numel(), _stream()))
         return (idx, sc, val, sel) if return_sel else (idx, sc, val)
 
+    def _check_mmr_fits(self, mmr) -> None:
+        """The c entries an MMR call ranks must fit the engine: c <= max_topk (mmr_plan holds c to MMR_MAX_CANDIDATES)."""
+        if mmr is not None and mmr[1] > self.max_topk:
+            raise ValueError(f"mmr_candidates: the call would rank c = max(mmr_candidates, k) = {mmr[1]} entries, the engine "
+                             f"ranks at most max_topk={self.max_topk}")
+
     def _mmr_picks(self, out: RetrieveOutput, k: int, lam: float) -> None:
         """Replace the ranked c entries of `out` by their k MMR picks (doc_idx / doc_score / mmr_value); a grouped call's
         group_idx follows them by the slot of each pick."""
@@ -1121,6 +1130,7 @@ class HippoRAGEngine:
         torch = _torch()
         mmr = mmr_plan(mmr_lambda, mmr_candidates, k)
         k_out, k = k, (k if mmr is None else mmr[1])
+        self._check_mmr_fits(mmr)
         agg = check_group_agg(group_agg)
         hits = check_group_hits(group_hits, group_agg)
         b = int(np.asarray(member_ptr).reshape(-1)[-1]) if np.size(member_ptr) else 0
@@ -1161,12 +1171,14 @@ class HippoRAGEngine:
                         mmr_candidates: Optional[int] = None, lexical=None, lexical_weight: float = 0.5) -> RetrieveOutput:
         """retrieve() with the raw passage scores fp32 [B, >= Np] supplied by the caller (hrag_retrieve_scored).
         lexical / lexical_weight: as on retrieve(), blended into the caller's rows (which are left as they are)."""
+        mmr = mmr_plan(mmr_lambda, mmr_candidates, k)
         if lexical is not None:
+            self._check_mmr_fits(mmr)                         # (refused before the blend is enqueued)
             pass_scores = self._lexical_blend(pass_scores, None, lexical, lexical_weight, filter_scope, doc_filter)
         return self._retrieve("hrag_retrieve_scored", pass_scores, (kept_idx, kept_score, kept_count),
                               (link_top_k, damping, passage_node_weight, ppr_iters, max(ppr_max_iters, ppr_iters), ppr_tol), k,
                               True, doc_filter=doc_filter, filter_scope=filter_scope, group_agg=group_agg,
-                              group_hits=group_hits, mmr=mmr_plan(mmr_lambda, mmr_candidates, k))
+                              group_hits=group_hits, mmr=mmr)
 
     def retrieve_converged(self, q_pass, kept_idx, kept_score, kept_count, *, damping: float = 0.5,
                            ppr_iters: int = 20, ppr_tol: float = 1.5e-6, ppr_max_iters: int = 400,
@@ -1189,6 +1201,7 @@ class HippoRAGEngine:
                                  want_all_scores: bool = False, **kw) -> "PendingRetrieve":
         """Enqueue the batch and the copy of its flag words to (pinned) host memory; nothing waits.  .finish() waits for
         the flags -- not for whatever was enqueued behind them -- and does the host half of the contract."""
+        self._check_mmr_fits(mmr_plan(kw.get("mmr_lambda"), kw.get("mmr_candidates"), kw.get("k", 200)))   # before any work
         q = self._q(q_pass)
         kept_idx, kept_score, kept_count = (t.to(self.device) for t in (kept_idx, kept_score, kept_count))
         doc_filter = kw.pop("doc_filter", None)

@@ -366,8 +366,10 @@ def test_mmr_composes_with_filter_groups_fusion_and_dense(case):
     w = _want_from_plain(pass_dev, dim, di, ds, k, 0.7, n_p)
     assert np.array_equal(_np(gi), w[1]) and same_bits(_np(gs), w[2]) and same_bits(_np(gv), w[3])
     # more candidates than the engine ranks, and the python-side checks
-    with pytest.raises(Exception):
+    with pytest.raises(ValueError, match="mmr_candidates"):       # (named on the host, before anything is enqueued)
         eng.retrieve(qp, idx, sc, cnt, k=k, mmr_lambda=0.5, mmr_candidates=eng.max_topk + 1)
+    with pytest.raises(ValueError, match="mmr_candidates"):
+        eng.last_fused(mp, fuse="sum", k=k, mmr_lambda=0.5, mmr_candidates=eng.max_topk + 1)
     for kw in (dict(mmr_lambda=1.5), dict(mmr_lambda=float("nan")), dict(mmr_candidates=20), dict(mmr_lambda=0.5, mmr_candidates=2000)):
         with pytest.raises(ValueError):
             eng.retrieve(qp, idx, sc, cnt, k=k, **kw)
