@@ -17,6 +17,13 @@ PAY_TILE, PAY_MAX_CLAUSES, PAY_MAX_COLS = 2048, 64, 256
 PAY_I64, PAY_F64 = 0, 1
 PAY_MUST, PAY_MUST_NOT, PAY_SHOULD = 0, 1, 2
 PAY_RANGE, PAY_IN, PAY_PRESENT = 0, 1, 2
+# HRAG_BOOST_* (boosted retrieval): t_op = kind | mode << 8 | sub << 16 | BOOST_HAS_MISSING
+BOOST_MAX_TERMS = 32
+BOOST_CONST, BOOST_FIELD, BOOST_DECAY = 0, 1, 2
+BOOST_MUL, BOOST_ADD = 0, 1
+BOOST_NONE, BOOST_SQRT = 0, 1
+BOOST_LINEAR, BOOST_EXP, BOOST_GAUSS = 0, 1, 2
+BOOST_HAS_MISSING = 1 << 24
 HRAG_VERSION = 8      # HRAG_VERSION_MAJOR * 1000 + HRAG_VERSION_MINOR of include/hrag.h
 FLAG_DPR_FALLBACK, FLAG_ZERO_MASS, FLAG_ZERO_PHRASE, FLAG_FP8_SATURATED, FLAG_NOT_CONVERGED = 1, 2, 4, 8, 16
 # the convergence contract's error bound (include/hrag.h): error <= max(PPR_ERR_K * residual, floor of the state type);
@@ -99,6 +106,13 @@ FP8_UNAVAILABLE = {1: "hrag_graph_desc.col_sum was not given", 2: "V + 1 > 2^24 
 _P = C.c_void_p
 _I32, _I64, _F32 = C.c_int32, C.c_int64, C.c_float
 
+
+class BoostProgramDesc(C.Structure):
+    """hrag_boost_program: the device arrays of a boost program (include/hrag.h, boosted retrieval)."""
+    _fields_ = [(n, _P) for n in ("t_ptr", "t_op", "t_col", "t_num", "t_cl_ptr", "c_col", "c_op", "c_lo", "c_hi",
+                                  "c_set_ptr", "set_vals")] + [("n_terms", _I64), ("n_clauses", _I64), ("set_nnz", _I64)]
+
+
 # name -> (restype, argtypes); every symbol include/hrag.h declares
 SIGNATURES = {
     "hrag_last_error": (C.c_char_p, []),
@@ -162,6 +176,9 @@ SIGNATURES = {
     "hrag_payload_destroy": (C.c_int, [_P]),
     "hrag_payload_filter": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I32, _P, _I64, _P, _I64, _P]),
     "hrag_bitset_count_rows": (C.c_int, [_P, _I64, _I64, _I32, _P, _P]),
+    "hrag_boost_rows": (C.c_int, [_P, _P, _I64, _I32, _P, _P, C.POINTER(BoostProgramDesc), _I32, _P]),
+    "hrag_last_boosted": (C.c_int, [_P, _P, _I32, C.POINTER(BoostProgramDesc), _I32, _I32, _P, _I64, _I32, _P, _P, _P, _P,
+                                    _P, _P]),
     "hrag_ppr_sweeps": (C.c_int, [_P, _I32, _I32, _F32, _I32, _P]),
     "hrag_ppr_layout": (C.c_int, [_P, _I32, C.POINTER(_I32), C.POINTER(_I32)]),
     "hrag_row_minmax": (C.c_int, [_P, _I32, _I64, _I64, _P, _P, _P]),

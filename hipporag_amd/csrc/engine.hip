@@ -2062,6 +2062,43 @@ hrag_status hrag_last_fused(hrag_engine *e, int32_t batch, const int32_t *member
     return HRAG_OK;
 }
 
+// ---- boosted retrieval (include/hrag.h): the rows a call left, boosted in place (boost.hip), then the usual ranking
+hrag_status hrag_last_boosted(hrag_engine *e, const hrag_payload *pay, int32_t batch, const hrag_boost_program *program,
+                              int32_t broadcast, int32_t k, const uint32_t *filter_dev, int64_t filter_ld_words,
+                              int32_t group_agg, int32_t *doc_idx_out, float *doc_score_out, int32_t *group_idx_out,
+                              float *group_score_out, int32_t *best_doc_idx_out, hrag_stream stream) {
+    HRAG_TRY(check_batch(e, batch));
+    HRAG_REQUIRE(e->p_rows == e->n_passages && e->n_rows == e->V,
+                 "hrag_last_boosted on a row-shard engine: its score rows are slices of the passages (boosted retrieval is "
+                 "served by the unsharded engine only)");
+    HRAG_REQUIRE(pay != nullptr, "the payload index is NULL");
+    HRAG_REQUIRE(pay->n_passages == e->n_passages, "the payload index covers %lld passages, the engine %lld",
+                 (long long)pay->n_passages, (long long)e->n_passages);
+    HRAG_REQUIRE(program != nullptr, "the boost program is NULL");
+    TopkMask fm;
+    const TopkMask *mask = nullptr;
+    HRAG_TRY(doc_filter(e, filter_dev, filter_ld_words, fm, &mask));
+    HRAG_REQUIRE((doc_idx_out != nullptr) == (doc_score_out != nullptr), "doc_idx_out / doc_score_out: both or neither");
+    const GroupOut g{group_agg, group_idx_out, group_score_out, best_doc_idx_out};
+    const GroupOut *grp = group_agg >= 0 ? &g : nullptr;
+    if (grp) HRAG_TRY(check_grouped(e, grp));
+    if (doc_idx_out || grp) HRAG_REQUIRE(k >= 1 && k <= e->max_topk, "k=%d outside [1, max_topk=%d]", k, e->max_topk);
+    hipStream_t s = (hipStream_t)stream;
+    HRAG_ENGINE_CALL(e, stream);   // (rows_batch is read inside the call: another thread's retrieve cannot be rewriting it)
+    HRAG_REQUIRE(e->d_doc && e->rows_batch >= 1,
+                 "no score rows on this handle: hrag_last_boosted follows a retrieve, a scored or a grouped dense call or a "
+                 "fusion (the ungrouped dense calls do not write the rows)");
+    HRAG_REQUIRE(batch <= e->rows_batch, "batch=%d exceeds the %d queries of the call that wrote the score rows", batch,
+                 e->rows_batch);
+    e->rows_batch = 0;             // the rows are being rewritten; set again when the boost is enqueued
+    HRAG_TRY(launch_boost_rows(pay, e->d_doc, e->ld_p, batch, nullptr, nullptr, program, broadcast, s));
+    e->rows_batch = batch;
+    if (doc_idx_out)
+        HRAG_TRY(rank_rows(e, e->d_doc, batch, e->n_passages, k, 0, kNormNone, doc_idx_out, doc_score_out, s, mask));
+    if (grp) HRAG_TRY(rank_groups(e, e->d_doc, batch, k, mask, grp, s));
+    return HRAG_OK;
+}
+
 hrag_status hrag_ppr(hrag_engine *e, const float *reset, int32_t batch, float damping, int32_t iters,
                      float *x_out, int32_t *flags_out, hrag_stream stream) {
     HRAG_TRY(check_batch(e, batch));

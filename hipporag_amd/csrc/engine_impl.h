@@ -119,6 +119,29 @@ struct Ppr8Session {
 
 using namespace hrag;
 
+// a payload index (include/hrag.h, payload filters): typed per-passage columns on the device, read by payload.hip (the
+// doc filter words) and boost.hip (boosted retrieval) through the clause code of payload_clause.h
+namespace hrag {
+struct PayCol {
+    const int64_t *values;      // [n_passages] int64, or the bit patterns of doubles
+    const uint32_t *present;    // [ceil(n / 32)] or nullptr: every passage has a value
+    int32_t type, pad;
+};
+}  // namespace hrag
+
+struct hrag_payload {
+    int64_t n_passages = 0;
+    int32_t n_cols = 0;
+    std::vector<void *> owned;          // every device allocation of the handle
+    hrag::PayCol *d_cols = nullptr;     // [n_cols]
+};
+
+namespace hrag {
+// hrag_boost_rows without the export's casts (boost.hip); hrag_last_boosted (engine.hip) boosts the handle's rows with it
+hrag_status launch_boost_rows(const hrag_payload *pay, float *rows, int64_t ld, int32_t batch, const float *mn,
+                              const float *mx, const hrag_boost_program *g, int32_t broadcast, hipStream_t s);
+}  // namespace hrag
+
 // host-side entry flag of an engine handle; copying a handle (hrag_workspace_create) starts from "not in a call"
 struct CallFlag {
     std::atomic<int> v{0};

@@ -5,32 +5,16 @@
 // payload_filter_kernel: one 256-thread workgroup per (query, tile of HRAG_PAY_TILE consecutive passages).  The query's
 // clause records -- at most HRAG_PAY_MAX_CLAUSES, with the column pointers they name already resolved from the handle's
 // device table -- are staged once in LDS (3.5 KB).  A clause that is ill-formed is staged as DEAD (it hits nothing).  The
-// clause loop is uniform over the workgroup; thread t evaluates the passages tile0 + 256 u + t, u = 0 .. 7: coalesced 8-byte
-// column reads, a presence word shared by 32 lanes.  The verdicts of a wavefront are packed by the 64-bit wave ballot --
+// staging and the evaluation of a clause are payload_clause.h's: boost.hip evaluates the same clauses with the same code.
+// The clause loop is uniform over the workgroup; thread t evaluates the passages tile0 + 256 u + t, u = 0 .. 7: coalesced
+// 8-byte column reads, a presence word shared by 32 lanes.  The verdicts of a wavefront are packed by the 64-bit wave ballot --
 // lanes past n_passages stay in it with a false predicate, which is what zeroes the tail bits -- into 64 words in LDS, and
 // the first 64 threads store the tile's words, the words below W only.  No atomics, no global read-modify-write, every
 // output word written exactly once; the words W .. ld_o of a row are not touched.
 //
 // bitset_count_kernel: one workgroup per row, the popcounts of its words (the last one cut to n bits) summed per thread,
 // per wavefront, then over the four wavefronts in LDS.  No atomics.
-#include "engine_impl.h"
-
-namespace hrag {
-namespace {
-struct PayCol {
-    const int64_t *values;      // [n_passages] int64, or the bit patterns of doubles
-    const uint32_t *present;    // [ceil(n / 32)] or nullptr: every passage has a value
-    int32_t type, pad;
-};
-}  // namespace
-}  // namespace hrag
-
-struct hrag_payload {
-    int64_t n_passages = 0;
-    int32_t n_cols = 0;
-    std::vector<void *> owned;          // every device allocation of the handle
-    hrag::PayCol *d_cols = nullptr;     // [n_cols]
-};
+#include "payload_clause.h"
 
 namespace hrag {
 namespace {
@@ -41,31 +25,6 @@ constexpr int kPayTileWords = HRAG_PAY_TILE / 32;
 static_assert(kPayPer * kPayThreads == HRAG_PAY_TILE && kPayPer == 8, "a thread keeps its verdicts in 8-bit masks");
 static_assert(kPayTileWords == 64 && kPayTileWords <= kPayThreads, "the first 64 threads store the tile's words");
 static_assert(HRAG_PAY_MAX_CLAUSES <= kPayThreads, "thread j stages clause j");
-
-enum : int32_t { kDead = -1 };      // staged kind of an ill-formed clause
-
-struct PayClause {
-    const int64_t *values;
-    const uint32_t *present;
-    int64_t lo, hi;
-    int32_t kind, role, f64, set_beg, set_len, pad;
-};
-
-__device__ __forceinline__ double as_f64(int64_t v) { return __longlong_as_double(v); }
-
-// x equals one of the ascending values set[0 .. len): binary search, equality in the column's type
-template <bool F64>
-__device__ __forceinline__ bool in_set(const int64_t *__restrict__ set, int32_t len, int64_t x) {
-    int32_t lo = 0, hi = len;
-    while (lo < hi) {
-        const int32_t mid = lo + ((hi - lo) >> 1);
-        const int64_t v = set[mid];
-        const bool less = F64 ? as_f64(v) < as_f64(x) : v < x;
-        if (less) lo = mid + 1; else hi = mid;
-    }
-    if (lo >= len) return false;
-    return F64 ? as_f64(set[lo]) == as_f64(x) : set[lo] == x;
-}
 
 __global__ __launch_bounds__(kPayThreads) void payload_filter_kernel(
     const PayCol *__restrict__ cols, int32_t n_cols, int64_t n, const int32_t *__restrict__ f_ptr,
@@ -87,36 +46,7 @@ __global__ __launch_bounds__(kPayThreads) void payload_filter_kernel(
         beg = beg < 0 ? 0 : beg > n_clauses ? n_clauses : beg;
         end = end < beg ? beg : end > n_clauses ? n_clauses : end;
         nc = (int32_t)(end - beg < HRAG_PAY_MAX_CLAUSES ? end - beg : HRAG_PAY_MAX_CLAUSES);
-        if (tid < nc) {
-            const int64_t j = beg + tid;
-            const int32_t col = c_col[j], op = c_op[j];
-            PayClause c;
-            c.values = nullptr;
-            c.present = nullptr;
-            c.lo = c_lo[j];
-            c.hi = c_hi[j];
-            c.kind = (op >> 8) & 0xff;
-            c.role = op & 0xff;
-            c.f64 = 0;
-            c.pad = 0;
-            // the set slice: only set_vals [0, set_nnz) is read
-            int64_t sb = c_set_ptr[j], se = c_set_ptr[j + 1];
-            sb = sb < 0 ? 0 : sb > set_nnz ? set_nnz : sb;
-            se = se < sb ? sb : se > set_nnz ? set_nnz : se;
-            c.set_beg = (int32_t)sb;
-            c.set_len = (int32_t)(se - sb);
-            bool ok = (op >> 16) == 0 && col >= 0 && col < n_cols && c.kind <= HRAG_PAY_PRESENT && c.role <= HRAG_PAY_SHOULD;
-            if (c.role > HRAG_PAY_SHOULD || (op >> 16) != 0) c.role = HRAG_PAY_MUST;     // an unknown role: a MUST that hits nothing
-            if (ok) {
-                const PayCol pc = cols[col];
-                c.values = pc.values;
-                c.present = pc.present;
-                c.f64 = pc.type == HRAG_PAY_F64;
-                if (c.kind == HRAG_PAY_RANGE) ok = c.f64 ? as_f64(c.lo) <= as_f64(c.hi) : c.lo <= c.hi;   // (false for a NaN bound)
-            }
-            if (!ok) c.kind = kDead;
-            s_cl[tid] = c;
-        }
+        if (tid < nc) s_cl[tid] = stage_clause(cols, n_cols, c_col, c_op, c_lo, c_hi, c_set_ptr, set_nnz, beg + tid);
     }
     __syncthreads();
 
@@ -124,34 +54,7 @@ __global__ __launch_bounds__(kPayThreads) void payload_filter_kernel(
     uint32_t inb = 0;
 #pragma unroll
     for (int u = 0; u < kPayPer; ++u) inb |= (uint32_t)(tile0 + kPayThreads * u + tid < n) << u;
-    uint32_t pass = inb, should = 0;
-    bool has_should = false;
-
-    for (int32_t j = 0; j < nc; ++j) {       // uniform over the workgroup: every value below comes from LDS
-        const PayClause c = s_cl[j];
-        uint32_t hit = 0;
-        if (c.kind != kDead) {
-#pragma unroll
-            for (int u = 0; u < kPayPer; ++u) {
-                if (!((inb >> u) & 1u)) continue;
-                const int64_t p = tile0 + kPayThreads * u + tid;
-                bool h = c.present ? ((c.present[p >> 5] >> (p & 31)) & 1u) != 0 : true;
-                if (h && c.kind != HRAG_PAY_PRESENT) {
-                    const int64_t x = c.values[p];
-                    if (c.kind == HRAG_PAY_RANGE)
-                        h = c.f64 ? (as_f64(c.lo) <= as_f64(x) && as_f64(x) <= as_f64(c.hi)) : (c.lo <= x && x <= c.hi);
-                    else
-                        h = c.f64 ? in_set<true>(set_vals + c.set_beg, c.set_len, x)
-                                  : in_set<false>(set_vals + c.set_beg, c.set_len, x);
-                }
-                hit |= (uint32_t)h << u;
-            }
-        }
-        if (c.role == HRAG_PAY_MUST) pass &= hit;
-        else if (c.role == HRAG_PAY_MUST_NOT) pass &= ~hit;
-        else { has_should = true; should |= hit; }
-    }
-    if (has_should) pass &= should;
+    uint32_t pass = clauses_pass(s_cl, nc, set_vals, tile0, tid, inb);
 
     if (and_words) {
         const uint32_t *row = and_words + (size_t)b * ld_a;      // ld_a 0: one row for the batch

@@ -20,6 +20,8 @@ from ._lib import (EmbedDesc, FactDesc, GraphDesc, Opts, ShardLayout, Timings, c
 from .graph import CSRGraph
 from .lexical import invert_postings
 from .payload import PayloadFilter, PayloadIndex, compile_filters     # noqa: F401  (re-exported: the payload filters)
+from .boost import BoostProgram, check_program, compile_boosts        # noqa: F401  (re-exported: boosted retrieval)
+from .boost import boost_rows as _boost_rows
 
 
 def _torch():
@@ -305,6 +307,13 @@ def refuse_group_agg(who: str, kw: dict) -> None:
         raise NotImplementedError(f"{who} does not serve fuse (one ranking per question from several member queries): the "
                                   "fusion works on the score rows of one unsharded handle -- use HippoRAGEngine.retrieve + "
                                   "last_fused")
+
+
+def refuse_boost(who: str, kw: dict) -> None:
+    """The callers that do not serve boosted retrieval name the argument they refuse."""
+    if kw.get("boost") is not None:
+        raise NotImplementedError(f"{who} does not serve boost: the boost rewrites the score rows of one unsharded handle and "
+                                  "ranks them again -- use HippoRAGEngine.retrieve(boost=...)")
 
 
 def check_filter_scope(filter_scope: str, doc_filter) -> bool:
@@ -820,7 +829,7 @@ class HippoRAGEngine:
                  want_residual: bool = True, doc_filter=None, filter_scope: str = "ranking",
                  group_agg: Optional[str] = None, group_hits: Optional[int] = None,
                  mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None,
-                 lexical=None, lexical_weight: float = 0.5) -> RetrieveOutput:
+                 lexical=None, lexical_weight: float = 0.5, boost=None) -> RetrieveOutput:
         """Phase B: seeds + passage prior + PPR + ranking (DPR ranking where kept_count == 0).
         ppr_tol / ppr_max_iters: the convergence contract of include/hrag.h (0 = exactly ppr_iters sweeps);
         the output carries the per-query residual and the sweeps that ran.
@@ -841,7 +850,12 @@ class HippoRAGEngine:
         passage scores are the dense ones (hrag_sim_scores) blended with the lexical rows of these sparse queries at
         lexical_weight in [0, 1] (hrag_row_minmax, hrag_lex_scores, hrag_lex_blend_rows), handed to hrag_retrieve_scored*:
         the doc filter (scope "ranking"), group_agg, group_hits, mmr_* and a following last_fused work as they do there.  A
-        query whose terms match nothing keeps its dense row bit for bit.  None: the call is exactly the plain one."""
+        query whose terms match nothing keeps its dense row bit for bit.  None: the call is exactly the plain one.
+        boost= a BoostProgram or the grammar of compile_boosts (after set_payload_index; include/hrag.h, boosted retrieval):
+        the call runs as it does without it, then hrag_last_boosted rewrites the score rows it left as s * M + A and ranks
+        them again with the call's k, doc filter, group_agg, group_hits and mmr_*: every ranking output is that of the
+        boosted rows, flags / residual / iters_used stay the call's, and last_doc_scores / last_fused afterwards read the
+        boosted rows.  The first ranking is computed and discarded.  None: the call is exactly the plain one."""
         if lexical is not None:
             mmr = mmr_plan(mmr_lambda, mmr_candidates, k)     # (refused before the blend is enqueued)
             self._check_mmr_fits(mmr)
@@ -849,19 +863,22 @@ class HippoRAGEngine:
             return self._retrieve("hrag_retrieve_scored", rows, (kept_idx, kept_score, kept_count),
                                   (link_top_k, damping, passage_node_weight, ppr_iters, max(ppr_max_iters, ppr_iters), ppr_tol),
                                   k, want_residual or ppr_tol > 0, doc_filter=doc_filter, filter_scope=filter_scope,
-                                  group_agg=group_agg, group_hits=group_hits, mmr=mmr)
+                                  group_agg=group_agg, group_hits=group_hits, mmr=mmr, boost=boost)
         return self._retrieve("hrag_retrieve", q_pass, (kept_idx, kept_score, kept_count),
                               (link_top_k, damping, passage_node_weight, ppr_iters, max(ppr_max_iters, ppr_iters), ppr_tol), k,
                               want_residual or ppr_tol > 0, doc_filter=doc_filter, filter_scope=filter_scope,
-                              group_agg=group_agg, group_hits=group_hits, mmr=mmr_plan(mmr_lambda, mmr_candidates, k))
+                              group_agg=group_agg, group_hits=group_hits, mmr=mmr_plan(mmr_lambda, mmr_candidates, k),
+                              boost=boost)
 
-    def _retrieve(self, base, source, kept, ppr, k, report, *, doc_filter, filter_scope, group_agg, group_hits, mmr=None):
+    def _retrieve(self, base, source, kept, ppr, k, report, *, doc_filter, filter_scope, group_agg, group_hits, mmr=None,
+                  boost=None):
         """The one binding behind retrieve / retrieve_scored / dense_retrieve (base = "hrag_retrieve", "hrag_retrieve_scored"
         or "hrag_dense_retrieve"): the scope / agg / hits checks, inputs and outputs on the device, the filter words, the
         argument list from its named pieces, and the exported function that serves this combination -- base itself, or base +
         "_filtered" / "_scoped" / "_grouped".  kept (idx, score, count) and ppr (link_top_k .. ppr_tol, in the ABI's order)
         are None / () for the dense call, which has no flags either; report: allocate residual / iters_used.
-        mmr: None or mmr_plan's (lambda, c): c entries are ranked and _mmr_picks keeps k of them."""
+        mmr: None or mmr_plan's (lambda, c): c entries are ranked and _mmr_picks keeps k of them.
+        boost: None, or the rows the call left are boosted and ranked again (_last_boosted) before MMR and the hits."""
         torch = _torch()
         k_out, k = k, (k if mmr is None else mmr[1])
         self._check_mmr_fits(mmr)
@@ -877,6 +894,7 @@ class HippoRAGEngine:
             src = self._q(source)
             head = (self._handle, src.data_ptr(), src.shape[0])
         b = src.shape[0]
+        prog = None if boost is None else self._boost_program(boost, b)      # (refused before anything is enqueued)
         out = RetrieveOutput(self._empty((b, k), torch.int32), self._empty((b, k), torch.float32), None)
         tail = (_stream(),)
         if kept is not None:
@@ -899,17 +917,71 @@ class HippoRAGEngine:
             check(getattr(self._lib, base + "_grouped")(
                 *head, k, None, None, *tail, fw.data_ptr() if fw is not None else None, fld, 1 if scoped else 0, agg,
                 out.group_idx.data_ptr(), docs[1], docs[0]))
-            if mmr is not None:
-                self._mmr_picks(out, k_out, mmr[0])
-            if hits is not None:    # over the rows this call left, with its group ids and its filter
-                out.hit_idx, out.hit_score = self.last_group_hits(out.group_idx, hits, fw, fld)
-            return out
-        if fw is None:
+        elif fw is None:
             check(getattr(self._lib, base)(*head, k, *docs, *tail))
         else:
             check(getattr(self._lib, base + ("_scoped" if scoped else "_filtered"))(*head, k, *docs, *tail, fw.data_ptr(), fld))
+        if prog is not None:
+            self._last_boosted(out, prog, b, k, fw, fld, agg)
         if mmr is not None:
             self._mmr_picks(out, k_out, mmr[0])
+        if hits is not None:    # over the rows this call left, with its group ids and its filter
+            out.hit_idx, out.hit_score = self.last_group_hits(out.group_idx, hits, fw, fld)
+        return out
+
+    # ------------------------------------------------------------------ boosted retrieval
+    def _payload_ix(self, name: str) -> "PayloadIndex":
+        ix = getattr(getattr(self, "_parent", None) or self, "_payload_index", None)
+        if ix is None or not ix._handle.value:
+            raise ValueError(f"{name} needs a payload index on this engine (set_payload_index)")
+        return ix
+
+    def _boost_program(self, boost, batch: int) -> "BoostProgram":
+        """boost= of a call as a BoostProgram that fits the engine's payload index and the call's batch."""
+        if self.n_rows != self.num_vertices or self.passage_rows != self.n_passages:
+            raise NotImplementedError("boost on a row-shard engine: its score rows are slices of the passages (boosted "
+                                      "retrieval is served by the unsharded engine only)")
+        return check_program(self._payload_ix("boost"), boost, batch)
+
+    def boost_rows(self, rows, program, mn=None, mx=None):
+        """Any device score rows fp32 [B, >= n_passages] boosted IN PLACE by a BoostProgram (or compile_boosts' grammar) over
+        the engine's payload index (hrag_boost_rows); mn / mx fp32 [B]: the min-max of an entry is read instead of it."""
+        return _boost_rows(self._payload_ix("boost_rows"), rows, program, mn, mx)
+
+    def _last_boosted(self, out: RetrieveOutput, prog, b: int, k: int, fw, fld: int, agg) -> None:
+        """hrag_last_boosted over the rows the last call left: the ranking fields of `out` are written again."""
+        torch = _torch()
+        ix = self._payload_ix("boost")
+        if agg is not None and out.group_idx is None:
+            out.group_idx = self._empty((b, k), torch.int32)
+        check(self._lib.hrag_last_boosted(
+            self._handle, ix._handle, b, C.byref(prog.desc(self.device)), 1 if prog.broadcast else 0, k,
+            fw.data_ptr() if fw is not None else None, fld, -1 if agg is None else agg,
+            None if agg is not None else out.doc_idx.data_ptr(), None if agg is not None else out.doc_score.data_ptr(),
+            out.group_idx.data_ptr() if agg is not None else None, out.doc_score.data_ptr() if agg is not None else None,
+            out.doc_idx.data_ptr() if agg is not None else None, _stream()))
+
+    def last_boosted(self, boost, batch: int, *, k: int = 200, doc_filter=None, group_agg: Optional[str] = None,
+                     group_hits: Optional[int] = None, mmr_lambda: Optional[float] = None,
+                     mmr_candidates: Optional[int] = None) -> RetrieveOutput:
+        """The boosted ranking over the first `batch` score rows the last retrieve / retrieve_scored / grouped
+        dense_retrieve / last_fused on this handle left (hrag_last_boosted): the rows are boosted in place -- calling it
+        twice boosts twice -- and ranked under doc_filter, with group_agg / group_hits / mmr_* as on retrieve.  flags /
+        residual / iters_used are None: they belong to the call that wrote the rows."""
+        torch = _torch()
+        mmr = mmr_plan(mmr_lambda, mmr_candidates, k)
+        k_out, k = k, (k if mmr is None else mmr[1])
+        self._check_mmr_fits(mmr)
+        agg = check_group_agg(group_agg)
+        hits = check_group_hits(group_hits, group_agg)
+        prog = self._boost_program(boost, batch)
+        fw, fld = (None, 0) if doc_filter is None else self._filter_words(doc_filter, batch)
+        out = RetrieveOutput(self._empty((batch, k), torch.int32), self._empty((batch, k), torch.float32), None)
+        self._last_boosted(out, prog, batch, k, fw, fld, agg)
+        if mmr is not None:
+            self._mmr_picks(out, k_out, mmr[0])
+        if hits is not None:
+            out.hit_idx, out.hit_score = self.last_group_hits(out.group_idx, hits, fw, fld)
         return out
 
     # ------------------------------------------------------------------ payload filters
@@ -1117,7 +1189,7 @@ class HippoRAGEngine:
     def last_fused(self, member_ptr, *, weights=None, fuse: str = "rrf", rrf_c: int = 60, rrf_depth: Optional[int] = None,
                    k: int = 200, doc_filter=None, group_agg: Optional[str] = None,
                    group_hits: Optional[int] = None, mmr_lambda: Optional[float] = None,
-                   mmr_candidates: Optional[int] = None) -> RetrieveOutput:
+                   mmr_candidates: Optional[int] = None, boost=None) -> RetrieveOutput:
         """One ranking per QUESTION from the score rows the last retrieve / retrieve_scored / grouped dense_retrieve on this
         handle left (hrag_last_fused; include/hrag.h, fused retrieval): member_ptr int [Q + 1] cuts those B = member_ptr[-1]
         rows into Q questions of consecutive member rows, weights [B] (None: all 1) weigh them, fuse = "sum" (fp64, in member
@@ -1126,7 +1198,9 @@ class HippoRAGEngine:
         rankings); with group_agg the grouped ranking instead (group_idx, group_score = doc_score, best_doc_idx = doc_idx)
         and with group_hits=m its hits.  flags / residual / iters_used are None: they belong to the member rows.
         Afterwards last_doc_scores(Q) returns the fused rows.  mmr_lambda / mmr_candidates: as on retrieve, over the fused
-        ranking."""
+        ranking.  boost= (one list for the questions, or one per question): the fused rows are boosted (hrag_last_boosted)
+        and the ranking, the groups, the hits and MMR are those of the boosted fused rows; the fusion itself then ranks
+        nothing.  (After a retrieve(boost=) the member rows are boosted already: last_fused fuses boosted rows.)"""
         torch = _torch()
         mmr = mmr_plan(mmr_lambda, mmr_candidates, k)
         k_out, k = k, (k if mmr is None else mmr[1])
@@ -1138,6 +1212,7 @@ class HippoRAGEngine:
         mode, mp, w, c, depth = check_fuse(fuse, member_ptr, b, weights, rrf_c,
                                            min(k, dmax) if rrf_depth is None else rrf_depth, dmax)
         nq = mp.shape[0] - 1
+        prog = None if boost is None else self._boost_program(boost, nq)
         fw, fld = (None, 0) if doc_filter is None else self._filter_words(doc_filter, nq)
         need = int(self._lib.hrag_fuse_workspace_bytes(b, self.n_passages, mode, depth, 1 if fld else 0))
         if need < 0:
@@ -1151,12 +1226,16 @@ class HippoRAGEngine:
         self._fuse_host = (getattr(self, "_fuse_host", None) or [])[-1:] + [(mp, w)]   # alive until the stream copied them
         check(self._lib.hrag_last_fused(
             self._handle, b, mp.ctypes.data, nq, w.ctypes.data if w is not None else None, mode, c, depth, k,
-            fw.data_ptr() if fw is not None else None, fld, -1 if agg is None else agg,
-            None if agg is not None else idx.data_ptr(), None if agg is not None else sc.data_ptr(),
-            gi.data_ptr() if agg is not None else None, sc.data_ptr() if agg is not None else None,
-            idx.data_ptr() if agg is not None else None, ws.data_ptr(), ws.numel(), _stream()))
+            fw.data_ptr() if fw is not None else None, fld, -1 if agg is None or prog is not None else agg,
+            None if agg is not None or prog is not None else idx.data_ptr(),
+            None if agg is not None or prog is not None else sc.data_ptr(),
+            gi.data_ptr() if agg is not None and prog is None else None,
+            sc.data_ptr() if agg is not None and prog is None else None,
+            idx.data_ptr() if agg is not None and prog is None else None, ws.data_ptr(), ws.numel(), _stream()))
         out = RetrieveOutput(idx, sc, None)
         out.group_idx = gi
+        if prog is not None:        # (the fusion above ranked nothing: the boosted fused rows are ranked here)
+            self._last_boosted(out, prog, nq, k, fw, fld, agg)
         if mmr is not None:
             self._mmr_picks(out, k_out, mmr[0])
         if hits is not None:
@@ -1168,9 +1247,11 @@ class HippoRAGEngine:
                         ppr_tol: float = 0.0, ppr_max_iters: int = 0, doc_filter=None,
                         filter_scope: str = "ranking", group_agg: Optional[str] = None,
                         group_hits: Optional[int] = None, mmr_lambda: Optional[float] = None,
-                        mmr_candidates: Optional[int] = None, lexical=None, lexical_weight: float = 0.5) -> RetrieveOutput:
+                        mmr_candidates: Optional[int] = None, lexical=None, lexical_weight: float = 0.5,
+                        boost=None) -> RetrieveOutput:
         """retrieve() with the raw passage scores fp32 [B, >= Np] supplied by the caller (hrag_retrieve_scored).
-        lexical / lexical_weight: as on retrieve(), blended into the caller's rows (which are left as they are)."""
+        lexical / lexical_weight: as on retrieve(), blended into the caller's rows (which are left as they are).
+        boost: as on retrieve()."""
         mmr = mmr_plan(mmr_lambda, mmr_candidates, k)
         if lexical is not None:
             self._check_mmr_fits(mmr)                         # (refused before the blend is enqueued)
@@ -1178,7 +1259,7 @@ class HippoRAGEngine:
         return self._retrieve("hrag_retrieve_scored", pass_scores, (kept_idx, kept_score, kept_count),
                               (link_top_k, damping, passage_node_weight, ppr_iters, max(ppr_max_iters, ppr_iters), ppr_tol), k,
                               True, doc_filter=doc_filter, filter_scope=filter_scope, group_agg=group_agg,
-                              group_hits=group_hits, mmr=mmr)
+                              group_hits=group_hits, mmr=mmr, boost=boost)
 
     def retrieve_converged(self, q_pass, kept_idx, kept_score, kept_count, *, damping: float = 0.5,
                            ppr_iters: int = 20, ppr_tol: float = 1.5e-6, ppr_max_iters: int = 400,
@@ -1207,6 +1288,9 @@ class HippoRAGEngine:
         doc_filter = kw.pop("doc_filter", None)
         check_filter_scope(kw.get("filter_scope", "ranking"), doc_filter)   # (filter_scope travels in kw to every run)
         lexical, lexical_weight = kw.pop("lexical", None), kw.pop("lexical_weight", 0.5)
+        # boost: compiled ONCE; every run boosts its own rows by its own program rows (BoostProgram.select)
+        boost = kw.pop("boost", None)
+        prog = None if boost is None else self._boost_program(boost, q.shape[0])
         # lexical: the blended rows are formed ONCE; every run, the repeats of finish() included, is retrieve_scored on its
         # rows of them (a repeat never re-encodes or re-slices the sparse queries)
         blended = None if lexical is None else self._lexical_blend(None, q, lexical, lexical_weight,
@@ -1218,6 +1302,8 @@ class HippoRAGEngine:
             sel = slice(None) if rows is None else rows
             if fw is not None:    # the repeats of finish() rerun rows of the batch: each keeps its own filter row
                 kw["doc_filter"] = fw if fld == 0 else fw[sel]
+            if prog is not None:
+                kw["boost"] = prog if rows is None else prog.select(rows.cpu().numpy())
             if blended is not None:
                 o = self.retrieve_scored(blended[sel], kept_idx[sel], kept_score[sel], kept_count[sel], damping=damping,
                                          ppr_iters=iters, ppr_tol=ppr_tol, ppr_max_iters=max(max_iters, iters),
@@ -1243,14 +1329,35 @@ class HippoRAGEngine:
     def dense_retrieve(self, q_pass, k: int = 200, doc_filter=None, filter_scope: str = "ranking",
                        group_agg: Optional[str] = None, group_hits: Optional[int] = None,
                        mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None,
-                       lexical=None, lexical_weight: float = 0.5):
+                       lexical=None, lexical_weight: float = 0.5, boost=None):
         """DPR top-k; filter_scope="seeds": normalised over the allowed passages (hrag_dense_retrieve_scoped).
         group_agg="max" | "sum": (group ids, group scores, best passage of each group) over the normalised scores
         (hrag_dense_retrieve_grouped); group_hits=m adds two entries, (hit_idx, hit_score) [B, k, m] over those scores.
         mmr_lambda / mmr_candidates: as on retrieve; the tuple then ends with one more entry, mmr_value [B, k].
         lexical / lexical_weight (as on retrieve): (idx, score) of the blended rows, ranked by the normalising top-k
         (hrag_topk_rows_ws, hrag_topk_rows_masked under a doc_filter); not with group_agg, group_hits, mmr_* or
-        filter_scope="seeds"."""
+        filter_scope="seeds".
+        boost= (as on retrieve): (idx, score) of the boosted min-max scores -- hrag_sim_scores, hrag_row_minmax,
+        hrag_boost_rows with the row min / max, then the plain top-k (under a doc_filter of scope "ranking"); a program
+        without any term is the plain call, and in a per-query program a query without terms keeps its raw scores (its
+        ranking is the plain one).  Not with group_agg, group_hits, mmr_*, lexical or filter_scope="seeds"."""
+        if boost is not None:
+            for name, v in (("group_agg", group_agg), ("group_hits", group_hits), ("mmr_lambda", mmr_lambda),
+                            ("mmr_candidates", mmr_candidates), ("lexical", lexical)):
+                if v is not None:
+                    raise ValueError(f"dense_retrieve(boost=) does not serve {name}: it ranks the boosted rows and keeps no "
+                                     "score rows on the handle -- use retrieve(boost=...) or boost_rows yourself")
+            if filter_scope == "seeds":
+                raise ValueError('dense_retrieve(boost=) does not serve filter_scope="seeds": the min-max it boosts runs '
+                                 "over every passage")
+            check_filter_scope(filter_scope, doc_filter)
+            q = self._q(q_pass)
+            prog = self._boost_program(boost, q.shape[0])
+            if prog.n_terms:
+                rows = self.sim_scores("passages", q)
+                mn, mx = row_minmax(rows, self.n_passages)
+                self.boost_rows(rows, prog, mn, mx)
+                return self._rank_rows(rows, k, False, doc_filter)
         if lexical is not None:
             for name, v in (("group_agg", group_agg), ("group_hits", group_hits), ("mmr_lambda", mmr_lambda),
                             ("mmr_candidates", mmr_candidates)):
@@ -1480,8 +1587,9 @@ class HippoRAGEngine:
         check(self._lib.hrag_shard_ppr_gate(self._handle, step, C.byref(o), _stream()))
         return bool(o.value)
 
-    def shard_finish(self, mn, mx, flags, k: int, want_residual: bool = False, doc_filter=None):
+    def shard_finish(self, mn, mx, flags, k: int, want_residual: bool = False, doc_filter=None, boost=None):
         """doc_filter: the GLOBAL filter ([B, n_passages of the whole index] or packed); the shard reads its slice."""
+        refuse_boost("shard_finish", {"boost": boost})
         torch = _torch()
         b = mn.shape[0]
         idx = self._empty((b, k), torch.int32)
@@ -1517,6 +1625,7 @@ class CapturedPipeline:
         refuse_group_agg("CapturedPipeline", retrieve_kw)
         refuse_mmr("CapturedPipeline", retrieve_kw)
         refuse_lexical("CapturedPipeline", retrieve_kw)
+        refuse_boost("CapturedPipeline", retrieve_kw)
         self.engine, self.batch = engine, int(batch)
         dev, dt = engine.device, engine.emb_dtype
         self._qf = torch.zeros((batch, engine.dim), dtype=dt, device=dev)

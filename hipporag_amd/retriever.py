@@ -206,6 +206,9 @@ class RetrievalConfig:
                                          # columns on the device; metadata dict filters are then evaluated there and may use
                                          # $gt / $gte / $lt / $lte / $exists / $not / $any (payload.compile_filters); False:
                                          # the host bitsets, equality only
+    boost: Optional[list] = None         # boosted retrieval (include/hrag.h): the default boost of every retrieve call, one list
+                                         # of items in the grammar of boost.compile_boosts over the chunk-metadata columns
+                                         # (needs payload_index=True); None: no boost
 
 
 def identity_rerank_filter(query, candidate_items, candidate_indices, len_after_rerank=None):
@@ -406,7 +409,7 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
                           filter_scope: str = "ranking", group_agg: Optional[str] = None, group_of=None,
                           group_hits: Optional[int] = None, keep_all_scores: bool = False,
                           mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None,
-                          lexical_encode: Optional[Callable] = None, lexical_weight: float = 0.0):
+                          lexical_encode: Optional[Callable] = None, lexical_weight: float = 0.0, boost=None):
     """The body of retrieve() (HippoRAG.py:459-480), shared by the mirror class below and by
     reference_adapter.attach(): phase A on the device, the recognition-memory filter on the host (rerank_facts
     :1659-1707), phase B on the device, in batches of eng.max_batch queries.  Yields (offset of the batch, [(doc ids,
@@ -440,6 +443,8 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
     lexical_encode / lexical_weight (include/hrag.h, lexical retrieval): with a weight above 0 every batch's query strings
     are encoded (lexical_encode(strings) -> the CSR triple of engine.check_lexical) and phase B gets lexical= /
     lexical_weight=; with 0 its arguments are exactly the plain ones.
+    boost (include/hrag.h, boosted retrieval): a BoostProgram over all the queries (or a broadcast one); every batch's
+    phase B gets boost= with its own rows of it, so every ranking output -- and all_scores -- is that of the boosted rows.
     keep_all_scores: rows.all_scores is the device tensor of every passage's score of the batch and rows.repeated tells
     whether the contract ran rows again (retrieve_fused: the engine's own score rows are then not the batch's)."""
     import torch
@@ -548,6 +553,8 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
             kw.update(mmr_lambda=mmr[0], mmr_candidates=mmr[1])
         if lexical_encode is not None and lexical_weight > 0:
             kw.update(lexical=lexical_encode(qs), lexical_weight=lexical_weight)
+        if boost is not None:
+            kw["boost"] = boost.select(range(bt.lo, bt.lo + b))
         if two_halves:
             bt.pending = eng.retrieve_converged_start(*args, **kw)
             o = bt.pending.out
@@ -972,6 +979,8 @@ class HippoRAG:
     def _drop_payload(self):
         ix = getattr(self, "payload_index", None)
         if ix is not None:
+            if getattr(getattr(self, "engine", None), "_payload_index", None) is ix:
+                self.engine.set_payload_index(None)
             ix.close()
         self.payload_index = None
 
@@ -1000,6 +1009,8 @@ class HippoRAG:
         if self.passage_node_keys:
             self.payload_index = PayloadIndex.from_columns(self.payload_columns(), len(self.passage_node_keys),
                                                            device=self.engine.device.index)
+            if hasattr(self.engine, "set_payload_index"):      # (boost= evaluates over it inside the engine's calls)
+                self.engine.set_payload_index(self.payload_index)
 
     # ------------------------------------------------------------------ lexical retrieval
     def _drop_lexical(self):
@@ -1037,6 +1048,28 @@ class HippoRAG:
         if w not in (None, 0, 0.0):
             raise ValueError(f"{who} does not serve lexical_weight={w}: it fuses the score rows of plain member calls -- use "
                              "retrieve(lexical_weight=...)")
+
+    def _boost(self, boost, n_queries: int, who: str = "retrieve"):
+        """None, or the BoostProgram of a call's boost= (default RetrievalConfig.boost): one list of items for every query
+        or one list per query, compiled against the payload index (which _ensure_ready has built)."""
+        b = self.global_config.boost if boost is None else boost
+        if b is None:
+            return None
+        ix = getattr(self, "payload_index", None)
+        if ix is None:
+            raise ValueError(f"{who}: boost needs RetrievalConfig.payload_index=True (the boost terms read the chunk metadata "
+                             "as typed columns on the device)")
+        from .boost import check_program
+        prog = check_program(ix, b, n_queries)
+        return prog
+
+    @staticmethod
+    def _boost_metadata(solutions, prog) -> None:
+        """"boosted": True into the metadata of every returned entry of a boosted call."""
+        if prog is not None:
+            for s in solutions:
+                for d in s.doc_metadata or []:
+                    d["boosted"] = True
 
     @staticmethod
     def _lexical_metadata(solutions, lex: dict) -> None:
@@ -1375,8 +1408,12 @@ class HippoRAG:
                  gold_docs: Optional[List[List[str]]] = None, doc_filter=None, filter_scope: Optional[str] = None,
                  group_by=None, group_agg: Optional[str] = None, group_hits: Optional[int] = None,
                  mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None,
-                 lexical_weight: Optional[float] = None):
-        """lexical_weight (default RetrievalConfig.lexical_weight; include/hrag.h, lexical retrieval): above 0, the passage
+                 lexical_weight: Optional[float] = None, boost=None):
+        """boost (default RetrievalConfig.boost; include/hrag.h, boosted retrieval; needs payload_index=True): one list of
+        boost items (boost.compile_boosts) for every query, or one list per query, or a BoostProgram: the scores become
+        s * M + A over the chunk-metadata columns before they are ranked -- a recency decay, a trusted source, a penalty --
+        and everything below ranks the boosted scores; every entry's metadata then carries "boosted": True.
+        lexical_weight (default RetrievalConfig.lexical_weight; include/hrag.h, lexical retrieval): above 0, the passage
         scores that feed the passage prior and the DPR fallback are the dense ones blended at this weight with the BM25
         scores of the query strings against the passages (hipporag_amd.lexical); every entry's metadata then carries
         "lexical_weight".  Everything below composes with it except filter_scope="seeds".
@@ -1408,9 +1445,10 @@ class HippoRAG:
         hits = self._hits(group_hits, agg)
         mmr = self._mmr(mmr_lambda, mmr_candidates)
         lex = self._lexical(lexical_weight)
+        prog = self._boost(boost, len(queries))
         self.get_query_embeddings(queries)
         results: List[QuerySolution] = []
-        self._retrieve_into(results, queries, num_to_retrieve, words, scope, agg, table, hits, mmr, lex)
+        self._retrieve_into(results, queries, num_to_retrieve, words, scope, agg, table, hits, mmr, lex, prog)
         self.all_retrieval_time += time.time() - t_start
         logger.info("Total Retrieval Time %.2fs", self.all_retrieval_time)
         logger.info("Total Recognition Memory Time %.2fs", self.rerank_time)
@@ -1420,11 +1458,13 @@ class HippoRAG:
         return results
 
     def _retrieve_into(self, results, queries, num_to_retrieve, doc_filter=None, filter_scope: str = "ranking",
-                       group_agg=None, table=None, group_hits=None, mmr=None, lex=None):
+                       group_agg=None, table=None, group_hits=None, mmr=None, lex=None, boost=None):
         cfg = self.global_config
         extra = {} if doc_filter is None else {"doc_filter": doc_filter, "filter_scope": filter_scope}
         extra.update(mmr or {})
         extra.update(lex or {})
+        if boost is not None:
+            extra["boost"] = boost
         if group_agg is not None:
             self._engine_groups(table)
             extra.update(group_agg=group_agg, group_of=table[0])
@@ -1445,6 +1485,7 @@ class HippoRAG:
                     sols = self._build_query_solutions(queries[lo: lo + len(rows)], rows, num_to_retrieve)
                 self._mmr_metadata(sols, getattr(rows, "mmr_value", None))
                 self._lexical_metadata(sols, lex)
+                self._boost_metadata(sols, boost)
                 results.extend(sols)
 
     # ------------------------------------------------------------------ fused retrieval
@@ -1452,7 +1493,7 @@ class HippoRAG:
                        rrf_depth: Optional[int] = None, num_to_retrieve: Optional[int] = None, doc_filter=None,
                        filter_scope: Optional[str] = None, group_by=None, group_agg: Optional[str] = None,
                        group_hits: Optional[int] = None, mmr_lambda: Optional[float] = None,
-                       mmr_candidates: Optional[int] = None):
+                       mmr_candidates: Optional[int] = None, boost=None):
         """One ranked list per QUESTION, each question given as several sub-queries -- a decomposition, paraphrases, the
         thoughts of an IRCoT chain (include/hrag.h, fused retrieval).  Every sub-query runs phase A and phase B as in
         retrieve(); the score rows of a question's sub-queries are fused ON THE DEVICE over all passages -- fuse="sum"
@@ -1465,6 +1506,9 @@ class HippoRAG:
         from .engine import check_fuse
         self._refuse_mmr("retrieve_fused", mmr_lambda, mmr_candidates)
         self._refuse_lexical("retrieve_fused")
+        if boost is not None or self.global_config.boost is not None:
+            raise ValueError("retrieve_fused does not serve boost: it fuses the score rows of plain member calls -- use "
+                             "retrieve(boost=...), or HippoRAGEngine.last_fused(boost=...)")
         t_start = time.time()
         cfg = self.global_config
         if num_to_retrieve is None:
@@ -1573,14 +1617,15 @@ class HippoRAG:
                        gold_docs: Optional[List[List[str]]] = None, reason_fn: Optional[Callable] = None,
                        doc_filter=None, filter_scope: Optional[str] = None, group_by=None,
                        group_agg: Optional[str] = None, mmr_lambda: Optional[float] = None,
-                       mmr_candidates: Optional[int] = None, lexical_weight: Optional[float] = None):
+                       mmr_candidates: Optional[int] = None, lexical_weight: Optional[float] = None, boost=None):
         """Iterative retrieval: alternate retrieval and one reasoning step per query, merging the document
         scores by max (:526-543).  reason_fn(query, ranked_docs, thoughts) -> str stands for
         utils/qa_utils.reason_step (the IRCoT prompt + reader LLM are outside this package).  The reference
         walks the queries one by one and retrieves with a batch of one per step; queries are independent, so
         here every step retrieves for ALL still-active queries in one batched device call -- same result per
         query, batch kernels instead of 2 * max_qa_steps single-query passes.  lexical_weight (default
-        RetrievalConfig.lexical_weight): every step's retrieve() takes it, the thoughts being the query strings."""
+        RetrievalConfig.lexical_weight): every step's retrieve() takes it, the thoughts being the query strings.  boost
+        (default RetrievalConfig.boost): every step's retrieve() takes it, a per-query one cut to the step's queries."""
         self._refuse_mmr("retrieve_ircot", mmr_lambda, mmr_candidates)
         if max_qa_steps < 1:
             raise ValueError("max_qa_steps must be at least 1.")
@@ -1588,9 +1633,11 @@ class HippoRAG:
             raise ValueError("retrieve_ircot with max_qa_steps > 1 needs a reason_fn (the reader LLM is outside this package)")
         if num_to_retrieve is None:
             num_to_retrieve = self.global_config.retrieval_top_k
+        self._ensure_ready()
+        prog = self._boost(boost, len(queries), "retrieve_ircot")
         first = self.retrieve(list(queries), num_to_retrieve=num_to_retrieve, doc_filter=doc_filter,
                               filter_scope=filter_scope, group_by=group_by, group_agg=group_agg,
-                              lexical_weight=lexical_weight)
+                              lexical_weight=lexical_weight, boost=prog)
         merged = [dict(zip(r.docs, r.doc_scores.tolist())) for r in first]
         meta = [dict(zip(r.docs, r.doc_metadata or [])) for r in first]
         thoughts: List[List[str]] = [[] for _ in queries]
@@ -1612,7 +1659,8 @@ class HippoRAG:
             for i, r in zip(step_i, self.retrieve(step_q, num_to_retrieve=num_to_retrieve,
                                                   doc_filter=self._filter_rows(doc_filter, step_i),
                                                   filter_scope=filter_scope, group_by=group_by, group_agg=group_agg,
-                                                  lexical_weight=lexical_weight)):
+                                                  lexical_weight=lexical_weight,
+                                                  boost=None if prog is None else prog.select(step_i))):
                 for doc, score in zip(r.docs, r.doc_scores.tolist()):
                     merged[i][doc] = max(merged[i].get(doc, float("-inf")), score)
                 meta[i].update(dict(zip(r.docs, r.doc_metadata or [])))
@@ -1675,13 +1723,16 @@ class HippoRAG:
                      gold_docs: Optional[List[List[str]]] = None, doc_filter=None, filter_scope: Optional[str] = None,
                      group_by=None, group_agg: Optional[str] = None, group_hits: Optional[int] = None,
                      mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None,
-                     lexical_weight: Optional[float] = None):
+                     lexical_weight: Optional[float] = None, boost=None):
         """Dense retrieval; doc_filter / filter_scope as in retrieve() ("seeds": the scores are normalised over the
         allowed passages); group_by / group_agg / group_hits as in retrieve(), over the normalised dense scores;
         mmr_lambda / mmr_candidates as in retrieve(), over the dense ranking.
         lexical_weight (default RetrievalConfig.lexical_weight) above 0: the ranking of the dense scores blended with the
         BM25 scores of the query strings (HippoRAGEngine.dense_retrieve(lexical=)); then not with group_by, mmr_lambda,
-        filter_scope="seeds" or more documents than the engine's max_topk (ValueError naming lexical_weight)."""
+        filter_scope="seeds" or more documents than the engine's max_topk (ValueError naming lexical_weight).
+        boost (default RetrievalConfig.boost): the ranking of the boosted min-max scores
+        (HippoRAGEngine.dense_retrieve(boost=)); then not with group_by, mmr_lambda, lexical_weight, filter_scope="seeds" or
+        more documents than the engine's max_topk (ValueError naming boost)."""
         cfg = self.global_config
         if num_to_retrieve is None:
             num_to_retrieve = cfg.retrieval_top_k
@@ -1720,6 +1771,15 @@ class HippoRAG:
                     raise ValueError(f"retrieve_dpr does not serve lexical_weight={lex['lexical_weight']} with {name}: the "
                                      "blended rows are ranked once on the device -- use retrieve(lexical_weight=...)")
 
+        prog = self._boost(boost, len(queries), "retrieve_dpr")
+        if prog is not None:
+            for name, on in (("group_by", agg is not None), ("mmr_lambda", bool(mmr)), ("lexical_weight", bool(lex)),
+                             ('filter_scope="seeds"', scope == "seeds"),
+                             (f"num_to_retrieve above max_topk={eng.max_topk}", beyond)):
+                if on:
+                    raise ValueError(f"retrieve_dpr does not serve boost with {name}: the boosted rows are ranked once on the "
+                                     "device -- use retrieve(boost=...)")
+
         def rows_of(lo, b):                 # the packed filter rows of queries [lo, lo + b)
             return words if words.ndim == 1 else words[lo: lo + b]
 
@@ -1737,6 +1797,8 @@ class HippoRAG:
                 return (qs, host_copy_async(idx), host_copy_async(sc), host_copy_async(gi)) + tuple(map(host_copy_async, h))
             if lex:
                 extra.update(lexical=lex["lexical_encode"](qs), lexical_weight=lex["lexical_weight"])
+            if prog is not None:
+                extra["boost"] = prog.select(range(lo, lo + len(qs)))
             idx, sc, *h = eng.dense_retrieve(self._q_tensor(qs, "passage"), k=k_docs, **extra, **mmr)
             return (qs, host_copy_async(idx), host_copy_async(sc)) + ((None,) + tuple(map(host_copy_async, h)) if h else ())
 
@@ -1787,6 +1849,7 @@ class HippoRAG:
                                                  doc_metadata=r.doc_metadata))
             self._mmr_metadata(results[first:], values)
             self._lexical_metadata(results[first:], lex)
+            self._boost_metadata(results[first:], prog)
         if gold_docs is not None:
             return results, self._recall(gold_docs, [r.docs for r in results])
         return results
@@ -1794,13 +1857,13 @@ class HippoRAG:
     # ------------------------------------------------------------------ rag_qa :591-663
     def rag_qa(self, queries, gold_docs: Optional[List[List[str]]] = None,
                gold_answers: Optional[List[List[str]]] = None, doc_filter=None, filter_scope: Optional[str] = None,
-               lexical_weight: Optional[float] = None):
+               lexical_weight: Optional[float] = None, boost=None):
         if self.qa_fn is None:
             raise NotImplementedError("rag_qa needs a qa_fn (the reader LLM is outside this package)")
         retrieval_metrics = None
         if not isinstance(queries[0], QuerySolution):
             out = self.retrieve(queries=queries, gold_docs=gold_docs, doc_filter=doc_filter, filter_scope=filter_scope,
-                                lexical_weight=lexical_weight)
+                                lexical_weight=lexical_weight, boost=boost)
             queries, retrieval_metrics = out if gold_docs is not None else (out, None)
         solutions, messages, metadata = self.qa_fn(queries)
         if gold_answers is not None:

@@ -74,7 +74,8 @@ extern "C" {
  *        later in 0.8 (detect by the symbol): lexical retrieval -- hrag_lex_create, hrag_lex_destroy, hrag_lex_scores,
  *        hrag_lex_blend_rows;
  *        later in 0.8 (detect by the symbol): payload filters -- hrag_payload_create, hrag_payload_destroy,
- *        hrag_payload_filter, hrag_bitset_count_rows. */
+ *        hrag_payload_filter, hrag_bitset_count_rows;
+ *        later in 0.8 (detect by the symbol): boosted retrieval -- hrag_boost_rows, hrag_last_boosted. */
 #define HRAG_VERSION_MAJOR 0
 #define HRAG_VERSION_MINOR 8
 
@@ -972,6 +973,115 @@ hrag_status hrag_payload_filter(const hrag_payload *pay, const int32_t *f_ptr_de
  * Enqueues on `stream`. */
 hrag_status hrag_bitset_count_rows(const uint32_t *words_dev, int64_t ld, int64_t n, int32_t batch, int32_t *count_out_dev,
                                    hrag_stream stream);
+
+/* ---- boosted retrieval: payload-driven score boosts and decay functions on the device ----
+ * A payload condition above can only EXCLUDE a passage.  A boost PROGRAM prefers instead: it rewrites score rows in place
+ * as s * M + A, M and A built per passage from a small per-query list of TERMS over the columns of a payload index -- a
+ * constant under a condition (trust these sources 1.5x, halve the drafts), a column value (a little score per citation),
+ * a decay function of a column (prefer the last 90 days without hiding older material).
+ *
+ * Query b owns the terms t_ptr[b] .. t_ptr[b + 1] (int32); with broadcast != 0 every query owns t_ptr[0] .. t_ptr[1], as
+ * ld_a = 0 gives one row of filter words to a batch.  At most HRAG_BOOST_MAX_TERMS terms of a query are read.  Term j holds
+ *   t_op[j]       kind | mode << 8 | sub << 16 | has_missing << 24: kind HRAG_BOOST_CONST / _FIELD / _DECAY, mode
+ *                 HRAG_BOOST_MUL / _ADD, sub the modifier of a FIELD (HRAG_BOOST_NONE / _SQRT) or the shape of a DECAY
+ *                 (HRAG_BOOST_LINEAR / _EXP / _GAUSS), 0 for a CONST;
+ *   t_col[j]      the column of a FIELD or DECAY (a CONST ignores it);
+ *   t_num[5 j ..] five doubles: the weight w; three parameters -- a DECAY's origin, offset and c, unused otherwise --; the
+ *                 value `missing` (read when has_missing);
+ *   t_cl_ptr[j] .. t_cl_ptr[j + 1]   its CONDITION: a slice of clauses in the payload-filter encoding above (column,
+ *                 op = role | kind << 8, lo, hi, set slice; RANGE / IN / PRESENT x MUST / MUST_NOT / SHOULD, the same rule,
+ *                 without base words), evaluated by the device code of hrag_payload_filter itself.  An empty slice is true.
+ *                 All terms of one query together use at most HRAG_PAY_MAX_CLAUSES clauses: they fill that cap in term
+ *                 order, a term keeping the first clauses of its slice that still fit (the slice of an ill-formed term
+ *                 counts like any other).
+ *
+ * For passage p with the row entry s (fp32) start with M = 1.0, A = 0.0 (fp64).  For each term in list order:
+ *   1. hit = the term's condition at p.
+ *   2. the value v: CONST 1.0.  FIELD: x, the column value as a double (an I64 value converted round-to-nearest-even);
+ *      v = x (NONE) or the IEEE sqrt(x) (SQRT; NaN below 0).  DECAY: d = pos(fabs(x - origin) - offset), then
+ *      LINEAR v = pos((c - d) / c), EXP v = exp_dec(c * d), GAUSS v = exp_dec(c * (d * d)); pos(y) = y > 0 ? y : +0.0 is
+ *      fmax(0, y).  The HOST computes c once in fp64 from the usual scale and decay: scale / (1 - decay) for LINEAR,
+ *      ln(decay) / scale for EXP, ln(decay) / scale^2 for GAUSS.  A value that is absent, or NaN on an F64 column, is
+ *      MISSING for FIELD and DECAY: v = missing when the term carries one (as it is: no modifier, no decay), else
+ *      hit = false.
+ *   3. if hit: t = w * v, then M = M * t (MUL) or A = A + t (ADD).
+ * Every product, quotient, difference and sum is rounded on its own in fp64; no fused multiply-add anywhere.
+ *   out = (float)(((double)s * M) + A): two fp64 roundings and one to fp32, a NaN stored as the quiet NaN 0x7fc00000 (as
+ *   hrag_lex_scores stores one).
+ * The row of a query with NO terms is not touched: it stays bit for bit, -0.0 and NaN payloads included (a query whose
+ * terms hit nothing is rewritten with M = 1, A = 0).  The columns n_passages .. ld of a row are never touched.  No atomics;
+ * every element is read and written by one thread, which is why the operation is in place.
+ *
+ * With mn_dev / mx_dev (fp32 [batch], hrag_row_minmax of the rows) the kernel reads the min-max of the entry instead of s:
+ * mx - mn == 0 ? 1 : (s - mn) / (mx - mn) in fp32, the library's rule (hrag_lex_blend_rows) -- what a dense ranking needs.
+ *
+ * exp_dec(x), x <= 0, is the library's own exponential, so that the definition is a sequence of rounded fp64 operations
+ * a host can restate bit for bit: NaN gives NaN; x > 0 is taken as 0; x < -708 gives 0.0; else k = rint(x * LOG2E),
+ * r = (x - k * LN2_HI) - k * LN2_LO with LOG2E = 0x1.71547652b82fep+0, LN2_HI = 0x1.62e42fee00000p-1,
+ * LN2_LO = 0x1.a39ef35793c76p-33; p by Horner from c13 down to c0, c_i = fp64(1 / i!), each step p = p * r + c_i as two
+ * rounded operations; the result is ldexp(p, k).  Within 2 ulp of exp on [-708, 0], values in [0, 1], exp_dec(0) == 1.
+ *
+ * The program arrays live on the device and cannot be checked on the host, so the definition covers bad input, as the
+ * payload filter's does: both ends of t_ptr / t_cl_ptr / c_set_ptr ranges are clamped to the arrays (a descending pair is
+ * empty); terms and clauses beyond the caps are IGNORED (the Python binding raises instead); an ill-formed clause hits
+ * nothing; an ill-formed TERM -- a column outside [0, n_cols) on a FIELD or DECAY, an unknown kind, mode or sub, a bit
+ * above bit 24 of t_op -- is NEUTRAL: the score goes unboosted by it, never dropped.
+ *
+ * OUT OF SCOPE: logarithmic modifiers (no libm-free log here yet), geo distance, boosts applied to the passage prior
+ * BEFORE the PPR, evaluation inside the retrieve call itself (hrag_last_boosted re-ranks the rows a call left: that
+ * call's own ranking is computed and discarded), the row-shard, hybrid and captured forms. */
+#define HRAG_BOOST_MAX_TERMS 32          /* terms of one query that hrag_boost_rows reads */
+#define HRAG_BOOST_CONST 0               /* term kinds: the low byte of t_op */
+#define HRAG_BOOST_FIELD 1
+#define HRAG_BOOST_DECAY 2
+#define HRAG_BOOST_MUL 0                 /* term modes: the second byte */
+#define HRAG_BOOST_ADD 1
+#define HRAG_BOOST_NONE 0                /* FIELD modifiers: the third byte */
+#define HRAG_BOOST_SQRT 1
+#define HRAG_BOOST_LINEAR 0              /* DECAY shapes: the third byte */
+#define HRAG_BOOST_EXP 1
+#define HRAG_BOOST_GAUSS 2
+#define HRAG_BOOST_HAS_MISSING (1 << 24) /* the term carries a `missing` value */
+
+/* The program arrays, all on the device: t_ptr int32 [batch + 1] ([2] when broadcast); t_op / t_col int32 [n_terms];
+ * t_num fp64 [n_terms][5]; t_cl_ptr int32 [n_terms + 1]; the clause arrays as hrag_payload_filter takes them (c_set_ptr
+ * int32 [n_clauses + 1]).  The term arrays may be NULL when n_terms == 0, the clause arrays when n_clauses == 0, set_vals
+ * when set_nnz == 0.  The struct itself is read on the host, at the call. */
+typedef struct hrag_boost_program {
+    const int32_t *t_ptr;
+    const int32_t *t_op;
+    const int32_t *t_col;
+    const double *t_num;
+    const int32_t *t_cl_ptr;
+    const int32_t *c_col;
+    const int32_t *c_op;
+    const int64_t *c_lo;
+    const int64_t *c_hi;
+    const int32_t *c_set_ptr;
+    const int64_t *set_vals;
+    int64_t n_terms, n_clauses, set_nnz;
+} hrag_boost_program;
+
+/* rows_dev fp32 [batch, ld] boosted in place by the definition above, n = the passages of `pay`.  Engine-free; enqueues on
+ * `stream`; nothing is allocated, synchronised or read back; a program with n_terms == 0 launches nothing.  HRAG_EINVAL: a
+ * NULL handle, rows or program, batch outside [1, 65535], ld < n_passages, rows not 4-byte aligned, only one of mn_dev /
+ * mx_dev, a negative count, a NULL array with a positive count. */
+hrag_status hrag_boost_rows(const hrag_payload *pay, float *rows_dev, int64_t ld, int32_t batch, const float *mn_dev,
+                            const float *mx_dev, const hrag_boost_program *program, int32_t broadcast, hrag_stream stream);
+
+/* The boosted ranking over the score rows the last call left on this handle (as hrag_last_group_hits and hrag_last_fused
+ * read them: a retrieve, a scored or a grouped dense call, or a fusion): the first `batch` rows, one per query, are boosted
+ * IN PLACE by `program` (no mn / mx: the rows are final scores) and then ranked as that call would have ranked them -- the
+ * k best under the doc filter into doc_idx_out / doc_score_out (both or neither), or with group_agg >= 0 the grouped
+ * ranking into the three group outputs (hrag_retrieve_grouped's; group_agg -1: ungrouped).  Afterwards
+ * hrag_last_group_hits, hrag_last_doc_scores and hrag_last_fused read the boosted rows (a fusion then fuses boosted member
+ * rows; hrag_last_boosted after hrag_last_fused boosts the fused rows instead).  Calling it twice boosts twice.
+ * HRAG_EINVAL: a row-shard engine, a payload index over another number of passages, no score rows on the handle, batch
+ * above the queries of the call that wrote them, k outside [1, max_topk], and what hrag_boost_rows rejects. */
+hrag_status hrag_last_boosted(hrag_engine *e, const hrag_payload *pay, int32_t batch, const hrag_boost_program *program,
+                              int32_t broadcast, int32_t k, const uint32_t *filter_dev, int64_t filter_ld_words,
+                              int32_t group_agg, int32_t *doc_idx_out, float *doc_score_out, int32_t *group_idx_out,
+                              float *group_score_out, int32_t *best_doc_idx_out, hrag_stream stream);
 
 /* ---- lower-level seams (used by the per-method adapters and by the parity tests) ---- */
 
