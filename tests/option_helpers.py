@@ -1,8 +1,9 @@
 """The composed retrieve call restated in numpy: every option of HippoRAGEngine.retrieve / retrieve_scored / dense_retrieve /
-retrieve_converged / last_fused (doc filter, filter_scope="seeds", group_agg, group_hits, fusion, mmr_*, lexical) is a pure
-function of the fp32 score rows R the call leaves on the handle (last_doc_scores), the filter bits, the group table, the
-passage embeddings and the option values.  expected_outputs composes the per-feature restatements of tests/*_helpers.py in
-the order engine.py documents; servable is the refusal table of engine.py's docstrings; random_spec / plan generate calls.
+retrieve_converged / last_fused (doc filter, filter_scope="seeds", group_agg, group_hits, fusion, mmr_*, lexical, boost) is a
+pure function of the fp32 score rows R the UNBOOSTED call leaves on the handle (last_doc_scores), the filter bits, the group
+table, the passage embeddings, the payload columns and the option values.  expected_outputs composes the per-feature
+restatements of tests/*_helpers.py in the order engine.py documents; servable is the refusal table of engine.py's
+docstrings; random_spec / plan generate calls.
 numpy only: nothing here needs a device (tests/test_option_helpers_host.py holds this file to a naive loop)."""
 
 import dataclasses
@@ -19,13 +20,13 @@ from tests.mmr_helpers import mmr_batch_np
 ENTRIES = ("retrieve", "retrieve_scored", "dense_retrieve", "retrieve_converged", "last_fused")
 FILTER_KINDS = ("none", "all", "empty", "one", "few", "half", "sparse", "payload")
 FILTER_FORMS = ("bool", "words", "payload")
-OPTIONS = ("filter", "seeds", "group_agg", "group_hits", "fusion", "mmr", "lexical")
+OPTIONS = ("filter", "seeds", "group_agg", "group_hits", "fusion", "mmr", "lexical", "boost")
 GROUP_KINDS = ("one", "singletons", "two", "contiguous", "shuffled", "sorted")
 BATCHES = (1, 8, 9, 64, 65, 130, 257)      # the last small-batch kernel; both ends of the fp16 state; one e4m3 slab; a slab
 #                                            pair; a pair plus an odd slab
 MMR_MAX_CANDIDATES = 1024
 LOOP_ROWS = 8                              # rows per call the Python-loop restatements (MMR, hits) check
-PLAN_SEED, PLAN_CASES, PLAN_CALLS = 60611, 84, 6     # the plan the three GPU slices of tests/test_gpu_soak_slices.py run between
+PLAN_SEED, PLAN_CASES, PLAN_CALLS = 60612, 84, 6     # the plan the three GPU slices of tests/test_gpu_soak_slices.py run between
 #                                                      them; tests/test_option_helpers_host.py asserts what it covers
 
 # filter dicts over the keys of payload_helpers.random_metadata: a broad one, a conjunction, $any, a set that holds a
@@ -35,13 +36,39 @@ PAYLOAD_FILTERS = [{"year": {"$gte": 2020}}, {"user": ["alice", "bob"], "$not": 
                    {"user": "dave", "year": 2018, "score": 3.5, "flag": True}, {"user": "nobody"}, None,
                    {"score": {"$gt": 0.5, "$lte": 2.5}, "$not": {"flag": {"$exists": False}}}]
 
+# term lists of hipporag_amd/boost.py's grammar over the same keys (BOOST_PROGRAMS[i] is one query's boost):
+#  0  a constant MUL under $any, a constant ADD under $not of an IN-list
+#  1  FIELD terms: sqrt with a `missing` value on a column with holes, the plain value with and without one
+#  2  NaN entries: the metadata holds no negative number, so no sqrt is NaN; year * 1e306 is +inf in fp64 and two such ADDs
+#     of opposite sign sum to NaN wherever the condition holds and the passage has a year
+#  3 / 4 / 5  the linear / exp / gauss decays (MUL with missing, MUL without: no hit where the value is absent, ADD)
+#  6  mul 0.0 under a condition (and a negative MUL on top: M = -0.0): exact ties at zero over most of a row
+#  7  an ADD far above every score on a handful of passages: they lead the second ranking whatever the first one was
+#  8 / 9  [] and None: a query without terms (None only as an entry of a per-query program)
+BOOST_PROGRAMS = [
+    [{"if": {"$any": {"user": "alice", "year": 2022}}, "mul": 1.5}, {"if": {"$not": {"user": ["bob", "carol"]}}, "add": -1e-3}],
+    [{"field": "score", "modifier": "sqrt", "add": 1e-4, "missing": 0.0}, {"field": "mixed", "mul": 0.5, "missing": 2.0},
+     {"field": "score", "add": -2e-5}],
+    [{"if": {"flag": True}, "field": "year", "add": 1e306}, {"if": {"flag": True}, "field": "year", "add": -1e306},
+     {"field": "mixed", "modifier": "sqrt", "mul": 1.25}],
+    [{"decay": {"field": "year", "origin": 2023, "scale": 3, "kind": "linear"}, "mul": 1.0, "missing": 0.25}],
+    [{"decay": {"field": "score", "origin": 0.0, "scale": 1.5, "offset": 0.5, "kind": "exp"}, "mul": 2.0}],
+    [{"decay": {"field": "mixed", "origin": 2.5, "scale": 0.7, "decay": 0.3, "kind": "gauss"}, "add": 1e-3, "missing": -1.0}],
+    [{"if": {"year": {"$lte": 2021}}, "mul": 0.0}, {"if": {"user": "dave"}, "mul": -1.0}],
+    [{"if": {"user": "dave", "year": 2018}, "add": 10.0}],
+    [], None]
+BOOST_KINDS = ("one", "per_query")
+BOOST_FORMS = ("grammar", "program")
+
 
 @dataclasses.dataclass
 class CallSpec:
     """One call.  filter_kind "none": no doc filter; "payload": the rows of PAYLOAD_FILTERS named by payload_ids, in any
     form; the other kinds in the forms "bool" / "words".  filter_per_query: [rows, n] (one row for the batch otherwise),
     rows = the questions of a last_fused, else the batch.  entry "last_fused": a retrieve (carrying the scope, its filter
-    and the lexical blend) followed by last_fused (carrying the filter, the groups, the hits and MMR)."""
+    and the lexical blend) followed by last_fused (carrying the filter, the groups, the hits, MMR and the boost).
+    boost_kind None: no boost; "one": BOOST_PROGRAMS[boost_ids[0]] for every row (BoostProgram.broadcast); "per_query": row r
+    takes BOOST_PROGRAMS[boost_ids[r]]; boost_form: the grammar itself handed to the call, or compile_boosts' program."""
     entry: str = "retrieve"
     k: int = 10
     filter_kind: str = "none"
@@ -62,6 +89,9 @@ class CallSpec:
     rrf_c: int = 60
     rrf_depth: Optional[int] = None
     workspace: bool = False
+    boost_kind: Optional[str] = None
+    boost_ids: Optional[List[int]] = None
+    boost_form: str = "grammar"
 
     def to_json(self) -> str:
         return json.dumps(dataclasses.asdict(self))
@@ -86,6 +116,8 @@ class CallSpec:
             on.append("mmr")
         if self.lexical_weight is not None:
             on.append("lexical")
+        if self.boost_kind is not None:
+            on.append("boost")
         return on
 
     def rows(self, batch: int) -> int:
@@ -108,7 +140,11 @@ def servable(spec: CallSpec, limits=None):
       - mmr_candidates without mmr_lambda, c > 1024, c > max_topk: ValueError (mmr_candidates);
       - group_hits without group_agg: ValueError (group_hits);
       - the "seeds" scope takes its kept facts from score_facts(scope_filter=), which without fact sources raises
-        RuntimeError (HragError) naming set_fact_sources.
+        RuntimeError (HragError) naming set_fact_sources;
+      - dense_retrieve(boost=) with group_agg / group_hits / mmr_lambda / mmr_candidates / lexical: ValueError naming it, then
+        with filter_scope="seeds": ValueError (filter_scope) -- all before dense_retrieve's lexical refusals.  On every
+        other entry boost adds no refusal: retrieve / retrieve_scored / retrieve_converged / last_fused compile it after
+        their own checks and serve it with every option they serve.
     limits: dict(max_topk=, fact_sources=); what is missing is not checked."""
     lim = limits or {}
     seeds, lex = spec.filter_scope == "seeds", spec.lexical_weight is not None
@@ -122,6 +158,13 @@ def servable(spec: CallSpec, limits=None):
         mmr_err = (ValueError, "mmr_candidates")
     hits_err = (ValueError, "group_hits") if spec.group_hits is not None and spec.group_agg is None else None
     src_err = (RuntimeError, "fact_sources") if seeds and not lim.get("fact_sources", True) else None
+    if spec.entry == "dense_retrieve" and spec.boost_kind is not None:
+        for name in ("group_agg", "group_hits", "mmr_lambda", "mmr_candidates"):
+            if getattr(spec, name) is not None:
+                return ValueError, name
+        if lex:
+            return ValueError, "lexical"
+        return (ValueError, "filter_scope") if seeds else None
     if spec.entry == "dense_retrieve" and lex:
         for name in ("group_agg", "group_hits", "mmr_lambda", "mmr_candidates"):
             if getattr(spec, name) is not None:
@@ -174,6 +217,53 @@ def payload_allowed_fn(host_columns):
     return fn
 
 
+# ------------------------------------------------------------------------------------------ the boost
+def boost_arg(spec: CallSpec, rows: int):
+    """The grammar the spec's call takes as boost=: one term list, or one list (or None) per output row."""
+    if spec.boost_kind is None:
+        return None
+    if spec.boost_kind == "one":
+        return BOOST_PROGRAMS[spec.boost_ids[0]]
+    return [BOOST_PROGRAMS[i] for i in spec.boost_ids[:rows]]
+
+
+def boost_ctx(spec: CallSpec, host_columns, rows: int):
+    """ctx["boost"] of expected_outputs (None without a boost): the program arrays of compile_boosts over a PayloadColumns
+    (host code: no device) and the columns as boost_helpers.boost_rows_np takes them."""
+    if spec.boost_kind is None:
+        return None
+    from hipporag_amd.boost import compile_boosts
+    from tests.payload_helpers import cols_for_restatement
+    prog = compile_boosts(host_columns, boost_arg(spec, rows), rows)
+    assert prog.broadcast == (spec.boost_kind == "one") and (prog.broadcast or prog.batch == rows)
+    return dict(cols=cols_for_restatement(host_columns), prog=prog.arrays(), broadcast=prog.broadcast, n_terms=prog.n_terms)
+
+
+def boosted_rows(X, n: int, boost, mn=None, mx=None, naive=False):
+    """X fp32 [r, >= n] boosted row by row (row r by query r of the program): boost_helpers.boost_rows_np, or its
+    element-by-element loop."""
+    from tests.boost_helpers import boost_rows_naive, boost_rows_np
+    fn = boost_rows_naive if naive else boost_rows_np
+    return fn(np.asarray(X, np.float32)[:, :n], n, boost["cols"], boost["prog"], boost["broadcast"], mn=mn, mx=mx)
+
+
+def boost_score_rows(X, spec: CallSpec, ctx, naive=False):
+    """The rows a boosted call ranks and leaves behind (None: the call has no boost, or a program without any term on
+    dense_retrieve, which is the plain call).  X: the fused rows on last_fused, else R.  The ungrouped dense_retrieve -- the
+    only dense call that serves a boost -- boosts the min-max of its RAW rows ctx["rank_rows"] (numpy's min / max of each
+    row), a query without terms keeping its raw scores; every other entry boosts X as it stands."""
+    boost = ctx.get("boost") if spec.boost_kind is not None else None
+    if boost is None:
+        return None
+    n = ctx["n_passages"]
+    if spec.entry != "dense_retrieve":
+        return boosted_rows(X, n, boost, naive=naive)
+    if not boost["n_terms"]:
+        return None
+    raw = np.asarray(ctx["rank_rows"], np.float32)[:, :n]
+    return boosted_rows(raw, n, boost, mn=raw.min(axis=1), mx=raw.max(axis=1), naive=naive)
+
+
 # ------------------------------------------------------------------------------------------ the restatement
 def rank_rows(x, k: int, allowed=None):
     """(idx int32 [B, k], score fp32 [B, k]): every row ranked by the project rule (score descending, ties to the larger
@@ -200,13 +290,16 @@ def expected_outputs(R, spec: CallSpec, ctx, rows=None, hit_rows=None):
     """Every output field of the call from the score rows R fp32 [B, n] alone, for the output rows `rows` (ascending; None:
     all), the hit arrays for hit_rows (a subset of rows; None: rows).
     ctx: dict(n_passages, groups int [n] or None, allowed bool [rows of the call, n] or None, gram(ids int [r, c]) -> fp32
-    [r, c, c], max_topk; rank_rows: the raw rows fp32 [B, n] an UNGROUPED dense_retrieve ranks -- hrag_sim_scores, or the
+    [r, c, c], max_topk; boost: boost_ctx's dict (read when the spec has a boost); rank_rows: the raw rows fp32 [B, n] an
+    UNGROUPED dense_retrieve ranks -- hrag_sim_scores, or the
     blended rows -- while its scores are their min-max, R: two raw scores one ulp apart can round to one normalised score,
     so that call's ids are a function of the raw rows, not of R; every other call ranks R itself, the ungrouped dense call
     in the "seeds" scope included: there the rows are normalised over the allowed passages BEFORE the ranking).  -> dict(doc_idx, doc_score, group_idx, hit_idx, hit_score, mmr_value: arrays over `rows` or
-    None; fused: F fp32 [Q, n] of a fusion (every question), else None).  The order engine.py documents: fuse; rank under
-    the filter (grouped: group_rank_np); MMR picks k of the c ranked entries, group_idx following the slots; the hits of
-    the final group_idx under the same filter."""
+    None; fused: F fp32 [Q, n] of a fusion (every question), else None; rows: the boosted rows fp32 [rows of the call, n]
+    (every row) the call ranks and leaves on the handle, None without a boost).  The order engine.py documents: fuse; boost
+    (boost_score_rows: R on every entry but last_fused, where the fused rows are boosted); rank under the filter (grouped:
+    group_rank_np); MMR picks k of the c ranked entries, group_idx following the slots; the hits of the final group_idx
+    under the same filter, over the same -- boosted -- rows."""
     n = ctx["n_passages"]
     X = np.asarray(R, np.float32)[:, :n]
     allowed = ctx.get("allowed")
@@ -218,11 +311,17 @@ def expected_outputs(R, spec: CallSpec, ctx, rows=None, hit_rows=None):
             depth = min(c, ctx["max_topk"], n) if spec.rrf_depth is None else spec.rrf_depth
         fused = fuse_np(X, spec.member_ptr, spec.fuse, spec.weights, spec.rrf_c, depth, allowed)
         X = fused
+    XB = boost_score_rows(X, spec, ctx)
+    if XB is not None:
+        X = XB
     rows = np.arange(X.shape[0]) if rows is None else np.asarray(rows, np.int64)
     a = None if allowed is None else np.asarray(allowed, bool)[rows]
-    out = dict(doc_idx=None, doc_score=None, group_idx=None, hit_idx=None, hit_score=None, mmr_value=None, fused=fused)
+    out = dict(doc_idx=None, doc_score=None, group_idx=None, hit_idx=None, hit_score=None, mmr_value=None, fused=fused,
+               rows=XB)
     if spec.group_agg is None:
         raw = ctx.get("rank_rows") if spec.entry == "dense_retrieve" and spec.filter_scope != "seeds" else None
+        if XB is not None:          # (the boosted dense call ranks the boosted rows themselves)
+            raw = None
         if raw is None:
             idx, sc = rank_rows(X[rows], c, a)
         else:       # the ungrouped dense call ranks the RAW rows and returns the normalised scores of what it ranked
@@ -302,6 +401,14 @@ def random_spec(rng, limits) -> CallSpec:
             cand = [None, s.k, min(2 * s.k, cmax), min(max(s.k, 50), cmax), cmax if rng.random() < 0.2 else None, 1]
             v = cand[int(rng.integers(0, len(cand)))]
             s.mmr_candidates = None if v is None else int(v)
+    plain_dense = s.entry == "dense_retrieve" and (s.group_agg, s.mmr_lambda, s.lexical_weight) == (None, None, None) \
+        and s.filter_scope != "seeds"           # the dense call serves a boost with nothing but the ranking filter
+    if rng.random() < (0.38 if s.entry != "dense_retrieve" else 0.75) and (s.entry != "dense_retrieve" or plain_dense):
+        s.boost_kind = str(rng.choice(BOOST_KINDS, p=[0.35, 0.65]))
+        s.boost_form = str(rng.choice(BOOST_FORMS))
+        s.boost_ids = [int(i) for i in rng.integers(0, len(BOOST_PROGRAMS), b if s.boost_kind == "per_query" else 1)]
+        if s.boost_kind == "one" and BOOST_PROGRAMS[s.boost_ids[0]] is None:      # (None is a per-query entry only)
+            s.boost_ids[0] = int(rng.integers(0, len(BOOST_PROGRAMS) - 1))
     if s.entry == "last_fused":
         s.fuse = str(rng.choice(["sum", "max", "rrf"]))
         cuts = partitions(rng, b)

@@ -1,6 +1,8 @@
 """Boosted retrieval on the device (include/hrag.h, "boosted retrieval"; csrc/boost.hip): hrag_boost_rows held bit for bit to
 the numpy restatement of tests/boost_helpers.py, the host validation, retrieve(boost=) and its relatives held bit for bit to
-tests/option_helpers.expected_outputs over the restated boosted rows, and the mirror on the toy corpus."""
+tests/option_helpers.expected_outputs over the restated boosted rows, the convergence contract's repeats held row by row to
+each query's own program, and the mirror on the toy corpus.  (boost composed with every other option on every entry:
+tests/test_gpu_option_matrix.py and the option slices of tests/test_gpu_soak_slices.py.)"""
 
 import ctypes as C
 
@@ -520,6 +522,82 @@ def test_retrieve_with_a_boost_is_the_restatement_over_the_boosted_rows(case, b,
     eng.last_boosted(one, b, k=k)
     out = eng.last_boosted(one, b, k=k)
     _check(out, oh.expected_outputs(boosted(boosted(R, one), one), spec, ctx), "twice")
+
+
+@pytest.mark.parametrize("b,want_state", [(9, 2), (65, 8)])
+def test_the_contract_repeats_boost_each_row_by_its_own_program(gpu_device, b, want_state):
+    """retrieve_converged(boost= one program per query) when finish() repeats SOME rows: the ring of
+    tests/test_gpu_fp8_adversarial.py mixes slowly and the shortest sweep count its state runs on (12 on the fp16 state, 20
+    on the e4m3 one; plus the 9 the device adds) does not reach ppr_tol, so PPR rows are flagged and repeated on the fp32 state, while the DPR-fallback rows (every fourth, row 0 among them)
+    converge at once and are not.  The repeat runs rows [1, 2, 3, 5, ...] of the batch and must boost them by the
+    programs of exactly those queries (BoostProgram.select) under exactly their filter rows: each query adds its own
+    constant to its own set of passages, so a row boosted by a neighbour's program differs in every entry.  Every row of
+    all_scores is boost_rows_np of the unboosted contract's row, and the ranked outputs are the restatement over them."""
+    import torch
+    from hipporag_amd._lib import FLAG_NOT_CONVERGED
+    from hipporag_amd.boost import compile_boosts
+    from hipporag_amd.engine import HippoRAGEngine
+    from hipporag_amd.payload import PayloadIndex, encode_columns
+    from tests.group_helpers import random_groups
+    from tests.payload_helpers import columns_of, random_metadata
+    from tests.test_gpu_fp8_adversarial import CASES, _index
+    make, damping, _ = CASES["ring"]
+    n_v, src, dst, w, pv, pinned = make()
+    csr, pass_bits, fact_bits, index = _index(n_v, src, dst, w, pv, 64, seed=11, pinned_facts=pinned)
+    n, k, tol, iters = len(pv), 20, 1.5e-6, (12 if b <= 64 else 20)
+    rng = np.random.default_rng(31 + b)
+    host = encode_columns(columns_of(random_metadata(rng, n), ["year", "user", "score", "flag", "mixed"]), n)
+    cols = cols_for_restatement(host)
+    groups = random_groups(rng, n, "shuffled")
+    per = [[{"if": {"year": {"$gte": 2018 + q % 6}}, "add": 1.0 + q}, {"mul": 1.0 + q / 64.0}] for q in range(b)]
+    allowed = rng.random((b, n)) < 0.5
+    qf = _bf16(synth.make_queries_np(fact_bits, b, seed=5)[0], gpu_device)
+    qp = _bf16(synth.make_queries_np(pass_bits, b, seed=6)[0], gpu_device)
+    ix = PayloadIndex(host)
+    try:
+        with HippoRAGEngine(csr, index.passage_vertex, pass_bits, fact_bits, index.subj_vertex, index.obj_vertex,
+                            index.num_chunks, max_batch=b, max_topk=n) as eng:
+            eng.set_payload_index(ix)
+            eng.set_passage_groups(groups)
+            prog = compile_boosts(ix, per)
+            assert not prog.broadcast and prog.batch == b
+            gram = _gram_fn(_bf16(pass_bits, gpu_device).contiguous(), n, 64, gpu_device)
+            idx, sc = eng.score_facts(qf, k=5)
+            cnt = torch.full((b,), 5, dtype=torch.int32, device=gpu_device)
+            cnt[::4] = 0                                          # DPR fallback rows
+            kw = dict(damping=damping, ppr_iters=iters, ppr_tol=tol, ppr_max_iters=400, want_all_scores=True)
+            first = eng.retrieve(qp, idx, sc, cnt, damping=damping, ppr_iters=iters, ppr_tol=tol, ppr_max_iters=400, k=1)
+            assert eng.stats()["last_ppr_state"] == want_state
+            late = (_np(first.flags) & FLAG_NOT_CONVERGED) != 0   # what finish() will repeat: some rows, not all
+            assert late.any() and not late.all() and not late[::4].any(), late
+            assert not np.array_equal(np.flatnonzero(late), np.arange(late.sum()))     # (the repeat's rows are not 0 .. r - 1)
+            flt = torch.from_numpy(allowed).to(gpu_device)
+            for what, okw, alw in (("plain", {}, None),
+                                   ("grouped, hits, a filter per query", dict(group_agg="sum", group_hits=2, doc_filter=flt), allowed),
+                                   ("mmr", dict(mmr_lambda=0.5, mmr_candidates=40), None)):
+                plain = eng.retrieve_converged(qp, idx, sc, cnt, k=k, **kw, **okw)
+                pend = eng.retrieve_converged_start(qp, idx, sc, cnt, k=k, boost=prog, **kw, **okw)
+                out = pend.finish()
+                torch.cuda.synchronize()
+                used = _np(out.iters_used)
+                assert pend.repeated and len(np.unique(used)) > 1, (what, used)       # repeats happened, on a strict subset
+                assert (used[late] > used[~late].max()).all() and not (_np(out.flags) & FLAG_NOT_CONVERGED).any(), (what, used)
+                assert torch.equal(out.flags, plain.flags) and torch.equal(out.iters_used, plain.iters_used), what
+                assert torch.equal(out.residual.view(torch.int32), plain.residual.view(torch.int32)), what
+                R = _np(plain.all_scores)[:, :n]
+                RB = boost_rows_np(R, n, cols, prog.arrays())
+                got = _np(out.all_scores)[:, :n]
+                for q in range(b):                                # row by row: its own program, nobody else's
+                    _same(got[q], RB[q], f"{what}: all_scores row {q} ({'repeated' if late[q] else 'first run'})")
+                    other = boost_rows_np(R[q:q + 1], n, cols, compile_boosts(host, [per[(q + 1) % b]]).arrays())[0]
+                    assert not np.array_equal(other.view(np.uint32), RB[q].view(np.uint32)), q
+                spec = oh.CallSpec(entry="retrieve_converged", k=k, group_agg=okw.get("group_agg"), group_hits=okw.get("group_hits"),
+                                   mmr_lambda=okw.get("mmr_lambda"), mmr_candidates=okw.get("mmr_candidates"))
+                rows = np.array(sorted({0, 1, 2, b - 1})) if "mmr_lambda" in okw else None
+                ctx = dict(n_passages=n, groups=groups, allowed=alw, gram=gram, max_topk=n)
+                _check(out, oh.expected_outputs(RB, spec, ctx, rows=rows), (b, what), rows)
+    finally:
+        ix.close()
 
 
 def test_a_boost_without_terms_is_the_plain_call_and_errors_name_the_argument(case):

@@ -1,6 +1,6 @@
-"""Every subset of {doc filter, filter_scope="seeds", group_agg, group_hits, mmr, lexical} on every entry (retrieve,
+"""Every subset of {doc filter, filter_scope="seeds", group_agg, group_hits, mmr, lexical, boost} on every entry (retrieve,
 retrieve_scored, dense_retrieve, retrieve_converged, last_fused behind a retrieve) of one engine, at B = 9 (the fp16 PPR
-state) and B = 65 (the e4m3 state).  Each combination does one of two things: it raises the exception tests/option_helpers.py's
+state) and B = 65 (the e4m3 state): 128 subsets, 64 per test -- those without the boost and those with it.  Each combination does one of two things: it raises the exception tests/option_helpers.py's
 servable names -- the refusal table of engine.py's docstrings -- with the argument's name in the message, and leaves a
 following plain call bit-identical to one made before; or every output matches option_helpers.expected_outputs, the numpy
 restatement of the whole composed call over the score rows the call leaves on the handle (tools/soak_options.py's check).
@@ -13,11 +13,11 @@ import os
 import numpy as np
 import pytest
 
-from tests.option_helpers import ENTRIES, CallSpec, servable
+from tests.option_helpers import BOOST_FORMS, BOOST_KINDS, BOOST_PROGRAMS, ENTRIES, CallSpec, servable
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TOGGLES = ("filter", "seeds", "group_agg", "group_hits", "mmr", "lexical")
+TOGGLES = ("filter", "seeds", "group_agg", "group_hits", "mmr", "lexical", "boost")
 # the index of tests/test_gpu_payload.py::case (375 passages, max_topk 200), one engine for both batches
 CASE = dict(v=3000, e=24000, dim=64, pfrac=0.125, b=65, max_topk=200, groups="shuffled", seed=4141)
 MEMBER_PTR = {9: [0, 4, 9], 65: [0, 1, 30, 65]}
@@ -65,13 +65,16 @@ def _spec(entry, on, i, b):
             s.weights = [float(v % 4) / 2 for v in range(b)]
         if s.fuse == "rrf":
             s.rrf_depth = (None, 1, 25)[(i // 3) % 3]
+    if "boost" in on:       # one list or one per row, as the grammar or compiled; the programs rotate over the rows
+        s.boost_kind, s.boost_form = BOOST_KINDS[i % 2], BOOST_FORMS[(i // 2) % 2]
+        s.boost_ids = [(i + 3 * r) % len(BOOST_PROGRAMS) for r in range(b if s.boost_kind == "per_query" else 1)]
+        if s.boost_kind == "one" and BOOST_PROGRAMS[s.boost_ids[0]] is None:       # (None is a per-query entry)
+            s.boost_ids[0] = 7
     return s
 
 
-@pytest.mark.parametrize("entry", ENTRIES)
-@pytest.mark.parametrize("b,want_state", [(9, 2), (65, 8)])
-def test_every_subset_of_the_options_is_refused_by_name_or_is_the_restatement(harness, b, want_state, entry):
-    c = harness
+def _walk(c, b, want_state, entry, boost):
+    """the 64 subsets of TOGGLES with (boost) or without the boost on one entry -> (served, refused)"""
     if c.b != b:
         c.set_batch(b)
     c.eng.retrieve(c.qp, c.idx, c.sc, c.cnt, k=1)
@@ -79,9 +82,12 @@ def test_every_subset_of_the_options_is_refused_by_name_or_is_the_restatement(ha
     lim = dict(max_topk=c.max_topk, fact_sources=True)
     bad, served, refused = [], 0, 0
     subsets = [on for r in range(len(TOGGLES) + 1) for on in itertools.combinations(TOGGLES, r)]
+    assert len(subsets) == 128
+    subsets = [on for on in subsets if ("boost" in on) == boost]
     assert len(subsets) == 64
     for i, on in enumerate(subsets):
         spec = _spec(entry, on, i, b)
+        assert ("boost" in spec.options()) == boost
         err = servable(spec, lim)
         if err is None:
             served += 1
@@ -91,9 +97,29 @@ def test_every_subset_of_the_options_is_refused_by_name_or_is_the_restatement(ha
             why = c.check_refusal(spec, err)
         bad += [(on, w, spec.to_json()) for w in why]
     assert not bad, bad[:5]
+    return served, refused
+
+
+@pytest.mark.parametrize("entry", ENTRIES)
+@pytest.mark.parametrize("b,want_state", [(9, 2), (65, 8)])
+def test_every_subset_of_the_options_is_refused_by_name_or_is_the_restatement(harness, b, want_state, entry):
+    served, refused = _walk(harness, b, want_state, entry, boost=False)
     # what the table refuses here: seeds without a filter (16), group_hits without group_agg among the others (12), seeds
     # with lexical among the rest (6): 34 of the 64; dense_retrieve(lexical=) serves nothing but the ranking filter (44)
     assert (served, refused) == ((20, 44) if entry == "dense_retrieve" else (30, 34))
+
+
+@pytest.mark.parametrize("entry", ENTRIES)
+@pytest.mark.parametrize("b,want_state", [(9, 2), (65, 8)])
+@pytest.mark.parametrize("boost", [True], ids=["boost"])
+def test_every_subset_of_the_options_with_a_boost_is_refused_by_name_or_is_the_restatement(harness, boost, b, want_state, entry):
+    """The other 64 of the 128 subsets: the same walk with boost= on (one list / per query, grammar / BoostProgram, the
+    programs of option_helpers.BOOST_PROGRAMS rotating).  A served call is the restatement over the boosted rows, which are
+    also what last_doc_scores returns afterwards; a refused one leaves the following plain call bit-identical."""
+    served, refused = _walk(harness, b, want_state, entry, boost)
+    # the boost adds no refusal to retrieve / retrieve_scored / retrieve_converged / last_fused: the same 34 of 64 as
+    # without it; dense_retrieve(boost=) serves the ranking filter and nothing else: {boost} and {boost, filter}, 2 of 64
+    assert (served, refused) == ((2, 62) if entry == "dense_retrieve" else (30, 34))
 
 
 def test_more_candidates_than_the_engine_ranks_are_refused_by_name(harness):

@@ -8,8 +8,8 @@ replays it.
 
 The three option slices run the seeded plan of tests/option_helpers.py between them, one per PPR state family (batches <= 8:
 the small-batch kernels; 9 .. 64: the fp16 state; >= 65: the e4m3 slabs): random COMPOSED calls -- doc filter in every form,
-filter_scope="seeds", group_agg, group_hits, fusion, mmr_*, lexical -- on every entry, each held bit for bit to the one
-numpy restatement of the whole call (option_helpers.expected_outputs).  tests/test_option_helpers_host.py asserts, without
+filter_scope="seeds", group_agg, group_hits, fusion, mmr_*, lexical, boost -- on every entry, each held bit for bit to the
+one numpy restatement of the whole call (option_helpers.expected_outputs); every slice boosts calls on all five entries.  tests/test_option_helpers_host.py asserts, without
 a GPU, what that plan covers; `python tools/soak_options.py --replay '<json>'` replays a failing call."""
 
 import importlib.util
@@ -47,7 +47,7 @@ def test_seeded_slice_of_the_shard_soak(gpu_device, capsys):
 def _option_slice(name, batches, capsys, tmp_path):
     import json
     from tests.helpers import write_test_report
-    from tests.option_helpers import PLAN_CALLS, PLAN_CASES, PLAN_SEED
+    from tests.option_helpers import ENTRIES, PLAN_CALLS, PLAN_CASES, PLAN_SEED
     out = tmp_path / "calls.json"
     rc = _tool("soak_options").main(["--seconds", "150", "--cases", str(PLAN_CASES), "--calls", str(PLAN_CALLS), "--seed",
                                      str(PLAN_SEED), "--batches", batches, "--out", str(out)])
@@ -56,6 +56,9 @@ def _option_slice(name, batches, capsys, tmp_path):
     capsys.readouterr()
     assert rc == 0 and "SOAK OK" in text, text[-3000:]
     assert f"{PLAN_CASES // 7 * len(batches.split(','))} cases" in text        # (the time bound did not cut the slice short)
+    report = json.loads(out.read_text())
+    assert report["boosted"] * 4 >= len(report["calls"]) and set(report["boosted_entries"]) == set(ENTRIES), report["boosted"]
+    assert set(report["boosted_batches"]) == {int(x) for x in batches.split(",")}
 
 
 def test_seeded_slice_of_the_option_soak_small_batches(gpu_device, capsys, tmp_path):

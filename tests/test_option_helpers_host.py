@@ -12,8 +12,9 @@ from tests.fuse_helpers import partitions, rank_np
 from tests.group_helpers import random_groups, same_bits
 from tests.group_hits_helpers import group_hits_loop
 from tests.mmr_helpers import gram_np, mmr_np
-from tests.option_helpers import (BATCHES, ENTRIES, FILTER_FORMS, FILTER_KINDS, GROUP_KINDS, OPTIONS, PAYLOAD_FILTERS, PLAN_CALLS,
-                                  PLAN_CASES, PLAN_SEED, CallSpec, case_limits, expected_outputs, loop_rows, make_allowed,
+from tests.option_helpers import (BATCHES, BOOST_FORMS, BOOST_KINDS, BOOST_PROGRAMS, ENTRIES, FILTER_FORMS, FILTER_KINDS,
+                                  GROUP_KINDS, OPTIONS, PAYLOAD_FILTERS, PLAN_CALLS, PLAN_CASES, PLAN_SEED, CallSpec, boost_arg,
+                                  boost_ctx, boost_score_rows, case_limits, expected_outputs, loop_rows, make_allowed,
                                   n_passages_of, payload_allowed_fn, plan, random_spec, rank_rows, servable)
 
 
@@ -64,8 +65,9 @@ def _naive_fuse(R, spec, allowed, depth):
 
 
 def naive_outputs(R, spec, ctx):
-    """expected_outputs by plain loops: sort by the ranking rule, walk, keep the allowed, take the first passage per group,
-    greedy MMR element by element (mmr_helpers.mmr_np), hits by repeated selection (group_hits_loop)."""
+    """expected_outputs by plain loops: the boost element by element with Python floats (boost_helpers.boost_rows_naive),
+    sort by the ranking rule, walk, keep the allowed, take the first passage per group, greedy MMR element by element
+    (mmr_helpers.mmr_np), hits by repeated selection (group_hits_loop)."""
     n = ctx["n_passages"]
     X = np.asarray(R, np.float32)[:, :n]
     allowed, g = ctx.get("allowed"), ctx.get("groups")
@@ -74,9 +76,12 @@ def naive_outputs(R, spec, ctx):
     if spec.entry == "last_fused":
         depth = (min(c, ctx["max_topk"], n) if spec.rrf_depth is None else spec.rrf_depth) if spec.fuse == "rrf" else None
         fused = X = _naive_fuse(X, spec, allowed, depth)
+    XB = boost_score_rows(X, spec, ctx, naive=True)      # (which rows are boosted is the rule; the loop is the boost's)
+    if XB is not None:
+        X = XB
     rows = X.shape[0]
     out = dict(doc_idx=np.full((rows, k), -1, np.int32), doc_score=np.zeros((rows, k), np.float32), group_idx=None,
-               hit_idx=None, hit_score=None, mmr_value=None, fused=fused)
+               hit_idx=None, hit_score=None, mmr_value=None, fused=fused, rows=XB)
     if spec.group_agg is not None:
         out["group_idx"] = np.full((rows, k), -1, np.int32)
     if spec.mmr_lambda is not None:
@@ -89,6 +94,8 @@ def naive_outputs(R, spec, ctx):
         ok = [p for p in range(n) if allowed is None or allowed[r][p]]
         if spec.group_agg is None:
             raw = ctx.get("rank_rows") if spec.entry == "dense_retrieve" and spec.filter_scope != "seeds" else None
+            if XB is not None:
+                raw = None                                              # (a boosted dense call ranks its boosted rows)
             ids = _sorted(s if raw is None else [float(v) for v in raw[r]], ok)[:c]       # (the dense call ranks the raw row)
             sc = [s[p] for p in ids]
             gids = None
@@ -194,7 +201,8 @@ def _grid(seed):
                         groups=GROUP_KINDS[(seed + 2 * t) % len(GROUP_KINDS)], k=kk,
                         agg=[None, "max", "sum"][(t + seed) % 3], hits=[None, 1, 3][(t // 3 + seed) % 3],
                         lam=[0.0, 0.3, 1.0][(t // 2 + seed) % 3] if mmr else None, c=["k", "2k", "n"][(t // 2) % 3],
-                        fuse=fuse, cut=names[(t // 4 + seed) % len(names)], weights=bool(t % 2)))
+                        fuse=fuse, cut=names[(t // 4 + seed) % len(names)], weights=bool(t % 2),
+                        boost=[None, "one", "per_query"][(t // 2 + 2 * seed) % 3], boost_at=(5 * seed + 3 * t) % len(BOOST_PROGRAMS)))
     return out
 
 
@@ -243,6 +251,11 @@ def _build(p):
         spec.mmr_lambda = p["lam"]
         spec.mmr_candidates = {"k": spec.k, "2k": min(2 * spec.k, n), "n": n}[p["c"]]
     rows = spec.rows(b)
+    if p["boost"]:          # the programs rotate from boost_at on: every one comes up as the batch's and as a query's
+        spec.boost_kind = p["boost"]
+        spec.boost_ids = [(p["boost_at"] + 3 * r) % len(BOOST_PROGRAMS) for r in range(rows)]
+        if p["boost"] == "one" and BOOST_PROGRAMS[spec.boost_ids[0]] is None:
+            spec.boost_ids[0] = 2
     groups = random_groups(np.random.default_rng(p["seed"] + 1), n, p["groups"])
     if p["filter"] == "no group allowed":
         allowed = np.zeros((rows, n), bool)                              # row 0: nothing; the others: one whole group
@@ -259,6 +272,7 @@ def _build(p):
         allowed = make_allowed(spec, n, rows, fn)
     ctx = _ctx(rng, n, p["groups"], allowed)
     ctx["groups"] = groups
+    ctx["boost"] = boost_ctx(spec, _metadata_columns(p["seed"], n)[0], rows)
     return R, spec, ctx
 
 
@@ -318,6 +332,62 @@ def test_the_naive_grid_covers_what_it_claims():
     assert any(p["fuse"] and p["agg"] and p["lam"] is not None for p in ps)
     for fuse in ("sum", "max", "rrf"):
         assert {p["cut"] for p in ps if p["fuse"] == fuse} >= {"singletons", "one", "random", "one_then_big"}, fuse
+    # the boost: both kinds; with the groups, the hits, MMR and a filter at once; behind every fusion mode; every program as
+    # the batch's and as one query's; NaN entries and rows of exact zeros in the boosted rows of grouped SUM and of MMR calls
+    assert {p["boost"] for p in ps} == {None, "one", "per_query"}
+    assert any(p["boost"] and p["agg"] and p["hits"] and p["lam"] is not None and p["filter"] != "none" for p in ps)
+    assert {p["fuse"] for p in ps if p["boost"]} == {None, "sum", "max", "rrf"}
+    one = {s.boost_ids[0] for s in built if s.boost_kind == "one"}
+    per = {i for s, p in zip(built, ps) if s.boost_kind == "per_query" for i in s.boost_ids}
+    assert one == set(range(len(BOOST_PROGRAMS) - 1)) and per == set(range(len(BOOST_PROGRAMS)))
+    nan_in, zeros_in = set(), set()
+    for p, s in zip(ps, built):
+        if s.boost_kind is not None:
+            R, _, ctx = _build(p)
+            XB = expected_outputs(R, s, ctx)["rows"]
+            what = (s.group_agg, s.mmr_lambda is not None)
+            if np.isnan(XB).any():
+                nan_in.add(what)
+            if ((XB == 0).sum(axis=1) > XB.shape[1] // 3).any() and (XB != 0).any():
+                zeros_in.add(what)
+    for got in (nan_in, zeros_in):
+        assert {a for a, _ in got} >= {None, "max", "sum"} and {m for _, m in got} == {False, True}, got
+
+
+def test_the_boosted_dense_call_boosts_the_min_max_of_the_raw_rows():
+    """dense_retrieve(boost=) is its own rule (engine.py): numpy's min-max of the raw rows, the boost over the normalised
+    entries, the plain ranking of the result under the filter -- no normalisation behind the boost.  In a per-query
+    program a query without terms keeps its RAW scores, and a program without any term is the plain call: the raw rows
+    ranked, their min-max returned.  Both forms against the naive loop, and against each other where they must differ."""
+    from tests.lex_helpers import minmax_np, row_minmax_np
+    rng = np.random.default_rng(9)
+    n, b = 150, 6
+    raw = (rng.random((b, n)).astype(np.float32) - np.float32(0.3)) * np.float32(0.7)
+    raw[:, rng.integers(0, n, 20)] = np.float32(0.25)                      # a tie class in every row
+    R = np.stack([minmax_np(r, *[v[0] for v in row_minmax_np(r[None])]) for r in raw])
+    host = _metadata_columns(9, n)[0]
+    for allowed in (None, rng.random((b, n)) < 0.5, np.zeros((b, n), bool)):
+        for kind, ids in (("one", [1]), ("one", [8]), ("per_query", [0, 9, 2, 8, 7, 6]), ("per_query", [8, 9, 9, 8, 8, 9])):
+            spec = CallSpec(entry="dense_retrieve", k=40, boost_kind=kind, boost_ids=ids)
+            ctx = dict(_ctx(rng, n, "two", allowed), rank_rows=raw, boost=boost_ctx(spec, host, b))
+            got, want = expected_outputs(R, spec, ctx), naive_outputs(R, spec, ctx)
+            _same(got, want, (kind, ids))
+            plain = expected_outputs(R, CallSpec(entry="dense_retrieve", k=40), ctx)
+            if all(not BOOST_PROGRAMS[i] for i in ids):                    # no term at all: the plain call
+                assert got["rows"] is None
+                _same(got, plain, ("no terms", ids))
+                continue
+            XB = got["rows"]
+            for q in range(b):
+                terms = BOOST_PROGRAMS[ids[q if kind == "per_query" else 0]]
+                if not terms:                                              # its raw scores, bit for bit: not their min-max
+                    assert same_bits(XB[q], raw[q]) and not same_bits(XB[q], R[q])
+                    np.testing.assert_array_equal(got["doc_idx"][q], plain["doc_idx"][q])
+                else:
+                    assert not same_bits(XB[q], raw[q])
+            wi, ws = rank_np(XB, 40, allowed)                              # ... and the ranking is the plain one of XB
+            np.testing.assert_array_equal(got["doc_idx"], wi)
+            assert same_bits(got["doc_score"], ws)
 
 
 def test_rank_rows_is_the_loop_of_fuse_helpers():
@@ -377,8 +447,78 @@ def test_the_refusal_table():
                      (dict(entry="dense_retrieve", lexical_weight=0.3, filter_scope="seeds", **f), (ValueError, "filter_scope")),
                      (dict(entry="dense_retrieve", lexical_weight=0.3, **f), None)):
         assert servable(CallSpec(**kw), lim) == want, kw
+    # the boost: dense_retrieve serves it with the ranking filter alone and names what it refuses -- in its own order, and
+    # before the lexical refusals; every other entry refuses exactly what it refuses without the boost
+    bst, d = dict(boost_kind="one", boost_ids=[0]), dict(entry="dense_retrieve")
+    for kw, want in ((dict(), None), (f, None), (dict(group_agg="max"), (ValueError, "group_agg")),
+                     (dict(group_agg="max", group_hits=2, mmr_lambda=0.5, lexical_weight=0.3), (ValueError, "group_agg")),
+                     (dict(group_hits=2, mmr_lambda=0.5), (ValueError, "group_hits")),
+                     (dict(mmr_lambda=0.5, mmr_candidates=5, lexical_weight=0.3), (ValueError, "mmr_lambda")),
+                     (dict(mmr_lambda=0.5, k=51), (ValueError, "mmr_lambda")),
+                     (dict(mmr_candidates=5, lexical_weight=0.3), (ValueError, "mmr_candidates")),
+                     (dict(lexical_weight=0.3, **f), (ValueError, "lexical")),
+                     (dict(lexical_weight=0.3, filter_scope="seeds", **f), (ValueError, "lexical")),
+                     (dict(filter_scope="seeds", **f), (ValueError, "filter_scope")),
+                     (dict(filter_scope="seeds"), (ValueError, "filter_scope"))):
+        assert servable(CallSpec(**d, **bst, **kw), lim) == want, kw
+        assert servable(CallSpec(**d, boost_kind="per_query", boost_ids=[9, 8], boost_form="program", **kw), lim) == want, kw
+    for entry in ENTRIES:
+        if entry != "dense_retrieve":
+            for kw in (dict(), f, dict(filter_scope="seeds"), dict(filter_scope="seeds", **f), dict(group_hits=2),
+                       dict(filter_scope="seeds", lexical_weight=0.3, **f), dict(mmr_candidates=20), dict(mmr_lambda=0.5, k=51),
+                       dict(group_agg="sum", group_hits=2, mmr_lambda=0.5, mmr_candidates=50, lexical_weight=0.3, **f)):
+                assert servable(CallSpec(entry=entry, **bst, **kw), lim) == servable(CallSpec(entry=entry, **kw), lim), (entry, kw)
     assert servable(CallSpec(mmr_lambda=0.5, mmr_candidates=1025), None) == (ValueError, "mmr_candidates")
     assert servable(CallSpec(filter_scope="seeds", **f), dict(fact_sources=False)) == (RuntimeError, "fact_sources")
+
+
+def test_a_spec_without_the_boost_fields_still_loads():
+    """A replay JSON written before the boost fields existed is a call without a boost."""
+    import json
+    d = json.loads(CallSpec(entry="last_fused", fuse="rrf", member_ptr=[0, 2, 3], group_agg="max").to_json())
+    for name in ("boost_kind", "boost_ids", "boost_form"):
+        d.pop(name)
+    s = CallSpec.from_dict(d)
+    assert s.boost_kind is None and "boost" not in s.options() and boost_arg(s, 2) is None and boost_ctx(s, None, 2) is None
+    assert "boost" in CallSpec(boost_kind="one", boost_ids=[0]).options()
+
+
+def test_the_boost_programs_hold_what_they_claim():
+    """BOOST_PROGRAMS compiles over random_metadata's columns, and over them: a constant MUL and ADD under $any / $not / an
+    IN-list, FIELD with and without sqrt, `missing` on a column with holes, the three decays, NaN entries, a row of exact
+    zeros, and an ADD that puts a handful of passages above everything else."""
+    from hipporag_amd._lib import (BOOST_ADD, BOOST_CONST, BOOST_DECAY, BOOST_EXP, BOOST_FIELD, BOOST_GAUSS, BOOST_HAS_MISSING,
+                                   BOOST_LINEAR, BOOST_MUL, BOOST_NONE, BOOST_SQRT)
+    from hipporag_amd.boost import compile_boosts
+    from tests.payload_helpers import cols_for_restatement
+    n = 400
+    host = _metadata_columns(21, n)[0]
+    prog = compile_boosts(host, BOOST_PROGRAMS)
+    assert not prog.broadcast and prog.batch == len(BOOST_PROGRAMS)
+    assert compile_boosts(host, []).broadcast and compile_boosts(host, []).n_terms == 0
+    ops = [(int(o) & 0xFF, (int(o) >> 8) & 0xFF, (int(o) >> 16) & 0xFF, bool(int(o) & BOOST_HAS_MISSING)) for o in prog.t_op]
+    assert {(k_, m) for k_, m, _, _ in ops} >= {(BOOST_CONST, BOOST_MUL), (BOOST_CONST, BOOST_ADD)}
+    assert {sub for k_, _, sub, _ in ops if k_ == BOOST_FIELD} == {BOOST_NONE, BOOST_SQRT}
+    assert {sub for k_, _, sub, _ in ops if k_ == BOOST_DECAY} == {BOOST_LINEAR, BOOST_EXP, BOOST_GAUSS}
+    cols = cols_for_restatement(host)
+    assert any(has and cols[int(c)][2] is not None and not cols[int(c)][2].all() for (_, _, _, has), c in zip(ops, prog.t_col))
+    text = repr(BOOST_PROGRAMS)
+    assert "$any" in text and "$not" in text and "['bob', 'carol']" in text and "'mul': 0.0" in text
+    assert BOOST_PROGRAMS[-2:] == [[], None]
+    rng = np.random.default_rng(2)
+    R = rng.random((len(BOOST_PROGRAMS), n)).astype(np.float32)
+    spec = CallSpec(k=10, boost_kind="per_query", boost_ids=list(range(len(BOOST_PROGRAMS))))
+    ctx = dict(n_passages=n, allowed=None, boost=boost_ctx(spec, host, len(BOOST_PROGRAMS)))
+    out = expected_outputs(R, spec, ctx)
+    XB, first = out["rows"], rank_rows(R, 10)[0]
+    assert 0 < np.isnan(XB[2]).sum() < n and np.isnan(out["doc_score"][2]).all()       # NaN ranks first
+    assert not np.isnan(np.delete(XB, 2, axis=0)).any()
+    assert (XB[6] == 0).sum() > n // 3 and (XB[6] != 0).any()
+    top = np.flatnonzero(XB[7] > 5)
+    assert 2 <= len(top) <= 10 and set(out["doc_idx"][7][:len(top)]) == set(top) and not set(top) <= set(first[7])
+    assert same_bits(XB[8:], R[8:]) and np.array_equal(out["doc_idx"][8:], first[8:])   # no terms: the row, the plain ranking
+    for q in range(8):
+        assert not same_bits(XB[q], R[q]), q
 
 
 def test_random_spec_draws_only_servable_specs():
@@ -389,6 +529,12 @@ def test_random_spec_draws_only_servable_specs():
             s = random_spec(rng, lim)
             assert servable(s, lim) is None and 1 <= s.k <= lim["max_topk"]
             assert CallSpec.from_dict(__import__("json").loads(s.to_json())) == s          # JSON round trip
+            if s.boost_kind is not None:
+                assert s.boost_kind in BOOST_KINDS and s.boost_form in BOOST_FORMS
+                assert len(s.boost_ids) == (b if s.boost_kind == "per_query" else 1)
+                assert s.boost_kind == "per_query" or BOOST_PROGRAMS[s.boost_ids[0]] is not None
+                arg = boost_arg(s, s.rows(b))
+                assert len(arg) == s.rows(b) if s.boost_kind == "per_query" else all(isinstance(t, dict) for t in arg)
         lim["fact_sources"] = False
         assert all(random_spec(rng, lim).filter_scope != "seeds" for _ in range(60))
 
@@ -415,6 +561,8 @@ def _pair_is_servable(a, b):
                 s.lexical_weight = 0.3
             if o == "fusion":
                 s.fuse, s.member_ptr = "sum", [0, 1]
+            if o == "boost":
+                s.boost_kind, s.boost_ids = "one", [0]
         if servable(s, dict(max_topk=100)) is None:
             return True
     return False
@@ -428,7 +576,9 @@ def test_the_plan_of_the_gpu_slices_covers_every_condition():
     for o in OPTIONS:                                                            # every option in a quarter of the calls
         assert sum(o in s.options() for s in specs) * 4 >= len(specs), o
     pairs = [(a, b) for a, b in itertools.combinations(OPTIONS, 2) if _pair_is_servable(a, b)]
-    assert ("seeds", "lexical") not in pairs and len(pairs) == 20
+    # seeds x lexical is served nowhere; the boost composes with each of the other seven on some entry: 20 + 7 pairs
+    assert ("seeds", "lexical") not in pairs and len(pairs) == 27
+    assert len([p for p in pairs if "boost" in p]) == len(OPTIONS) - 1
     for a, b in pairs:
         assert any(a in s.options() and b in s.options() for s in specs), (a, b)
     assert {s.filter_kind for s in specs} == set(FILTER_KINDS) and {s.filter_form for s in specs} == set(FILTER_FORMS)
@@ -442,5 +592,21 @@ def test_the_plan_of_the_gpu_slices_covers_every_condition():
     for fam in ((1, 8), (9, 64), (65, 130, 257)):                                # each slice: a grouped MMR call with c > k and hits
         assert any(s.group_agg and s.group_hits and s.mmr_lambda is not None and s.candidates() > s.k
                    for c, ss in cases if c["b"] in fam for s in ss), fam
+        # ... and a boosted one under a per-query filter; a boosted call on every entry
+        mine = [s for c, ss in cases if c["b"] in fam for s in ss if s.boost_kind is not None]
+        assert any(s.group_agg and s.group_hits and s.mmr_lambda is not None and s.candidates() > s.k
+                   and s.filter_kind != "none" and s.filter_per_query for s in mine), fam
+        assert {s.entry for s in mine} == set(ENTRIES), fam
+    boosted = [s for s in specs if s.boost_kind is not None]
+    assert {s.boost_kind for s in boosted} == set(BOOST_KINDS) and {s.boost_form for s in boosted} == set(BOOST_FORMS)
+    assert {(s.boost_kind, s.boost_form) for s in boosted} == set(itertools.product(BOOST_KINDS, BOOST_FORMS))
+    assert any(s.filter_kind in ("few", "one") for s in boosted)                 # fewer than k allowed: the -1 / 0 padding
+    assert any(s.filter_kind == "empty" for s in boosted)
+    assert any(s.filter_scope == "seeds" for s in boosted)
+    assert any(s.workspace for s in boosted) and any(s.lexical_weight is not None for s in boosted)
+    assert {i for s in boosted for i in s.boost_ids} == set(range(len(BOOST_PROGRAMS)))
+    assert any(s.k == case_limits(c)["max_topk"] == case_limits(c)["n_passages"] for c, ss in cases for s in ss
+               if s.boost_kind is not None)                                      # k = max_topk = n
+    assert any(case_limits(c)["max_topk"] == 10 for c, ss in cases for s in ss if s.boost_kind is not None)
     for c, ss in cases:                                                          # servable under the case's own limits
         assert all(servable(s, case_limits(c)) is None for s in ss)

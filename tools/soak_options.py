@@ -1,12 +1,18 @@
 #!/usr/bin/env python
 """Randomised soak of COMPOSED retrieve options (GPU): random small indexes x batch sizes x random servable calls of
 retrieve / retrieve_scored / dense_retrieve / retrieve_converged / last_fused with the doc filter (bool, packed words,
-PayloadFilter; one row or per query), filter_scope="seeds", group_agg, group_hits, fusion, mmr_* and lexical drawn together
-(tests/option_helpers.py: random_spec, plan), every output held to ONE numpy restatement of the whole call,
+PayloadFilter; one row or per query), filter_scope="seeds", group_agg, group_hits, fusion, mmr_*, lexical and boost drawn
+together (tests/option_helpers.py: random_spec, plan), every output held to ONE numpy restatement of the whole call,
 option_helpers.expected_outputs, which composes the per-feature restatements over the score rows R the call leaves on the
 handle (last_doc_scores).  Per call: ids exactly, floats bit for bit, the -1 / 0 padding included; flags / residual /
 iters_used bit-identical to the plain call of the same scoring configuration (None behind last_fused); last_doc_scores
 after the call bit-identical to R (to the fused rows after a fusion): no option may change scoring.
+
+boost= (one term list or one per query, as the grammar or as compile_boosts' program) is the one option that rewrites the
+rows: a boosted call is held to expected_outputs over boost_rows_np of the UNBOOSTED call's R (of the fused rows behind
+last_fused; of the min-max of the raw rows on dense_retrieve), last_doc_scores after it bit-identical to those boosted rows
+on every row, flags / residual / iters_used still the plain call's, and behind a workspace call the root handle's rows
+bit-identical to what they were.
 
 The rankings (plain, filtered, grouped), the fused rows and R itself are checked on every row.  The Python-loop
 restatements check at most 8 rows per call -- the hit arrays always, every field of an MMR call: row 0, the last row, every
@@ -40,6 +46,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 from hipporag_amd import _lib, synth  # noqa: E402
+from hipporag_amd.boost import compile_boosts  # noqa: E402
 from hipporag_amd.engine import HippoRAGEngine, LexicalIndex, pack_mask  # noqa: E402
 from hipporag_amd.payload import PayloadIndex, compile_filters, encode_columns  # noqa: E402
 from tests import option_helpers as oh  # noqa: E402
@@ -251,12 +258,24 @@ class Case:
         self._anchors[key] = (R, a, bad, raw)
         return self._anchors[key]
 
+    @staticmethod
+    def boost_kind(spec):
+        """None, "one" or "per_query" (a spec that carries no boost fields is a call without a boost)"""
+        return getattr(spec, "boost_kind", None)
+
+    def boost_arg(self, spec):
+        """boost= in the spec's form: the grammar itself, or its BoostProgram"""
+        arg = oh.boost_arg(spec, spec.rows(self.b))
+        return compile_boosts(self.pay, arg) if spec.boost_form == "program" else arg
+
     def invoke(self, spec, h, flt, kept, skw):
         """make the call -> (fields dict of torch tensors, flags triple or None, the rows the handle holds afterwards)"""
         kw = dict(k=spec.k, group_agg=spec.group_agg, group_hits=spec.group_hits, mmr_lambda=spec.mmr_lambda,
                   mmr_candidates=spec.mmr_candidates)
         if flt is not None:
             kw["doc_filter"] = flt
+        if self.boost_kind(spec) is not None:
+            kw["boost"] = self.boost_arg(spec)
         if spec.entry == "last_fused":
             out = h.last_fused(spec.member_ptr, weights=spec.weights, fuse=spec.fuse, rrf_c=spec.rrf_c, rrf_depth=spec.rrf_depth,
                                **kw)
@@ -294,12 +313,21 @@ class Case:
         flt = self.filter_arg(spec, allowed)
         R, a, bad, raw = self.anchor(spec, h, kept, skw)
         bad = list(bad)
+        boosted = self.boost_kind(spec) is not None
+        root = None
+        if boosted and spec.workspace:                  # the root handle holds rows of its own: the workspace's boost must
+            self.eng.retrieve(self.qp, self.idx, self.sc, self.cnt, k=1)       # leave them as they are
+            root = self.eng.last_doc_scores(self.b)
         out, after = self.invoke(spec, h, flt, kept, skw)
+        if root is not None and not _bits_equal(self.eng.last_doc_scores(self.b), root):
+            bad.append("a boosted workspace call changed the root handle's rows")
         torch.cuda.synchronize()
         fb = [] if spec.entry == "last_fused" else self.fallback
         sel_all, sel_hits = oh.loop_rows(spec, rows, fb, row_rng)
         want = oh.expected_outputs(R, spec, dict(n_passages=self.n, groups=self.groups, allowed=allowed, gram=self.gram,
-                                                 max_topk=self.max_topk, rank_rows=raw), rows=sel_all, hit_rows=sel_hits)
+                                                 max_topk=self.max_topk, rank_rows=raw,
+                                                 boost=oh.boost_ctx(spec, self.columns, rows) if boosted else None),
+                                   rows=sel_all, hit_rows=sel_hits)
         for name in FIELDS:
             g, w = _np(getattr(out, name)), want[name]
             sel = sel_hits if name.startswith("hit_") else sel_all
@@ -316,7 +344,13 @@ class Case:
             w = None if a is None or spec.entry == "last_fused" else getattr(a, name)
             if not _bits_equal(g, w):
                 bad.append(f"{name} differs from the plain call's")
-        if after is not None:
+        if boosted and after is not None:             # the handle holds the boosted rows (boosted fused rows; all_scores)
+            live = np.ones(rows, bool)
+            if spec.filter_scope == "seeds" and spec.entry != "last_fused":    # (an empty allowed set leaves a row without meaning)
+                live = allowed.any(axis=1)
+            if not same_bits(_np(after)[live][:, :self.n], want["rows"][live]):
+                bad.append("last_doc_scores after the boosted call is not the boosted rows")
+        elif after is not None:
             if spec.entry == "last_fused":
                 if not same_bits(_np(after)[:, :self.n], want["fused"]):
                     bad.append("last_doc_scores after the fusion is not the fused rows")
@@ -378,7 +412,7 @@ def run_case(case, specs, dev, only=None, out_lines=None):
         for i, spec in enumerate(specs):
             if only is not None and i != only:
                 continue
-            rec = dict(case=case, call=i, spec=json.loads(spec.to_json()))
+            rec = dict(case=case, call=i, spec=json.loads(spec.to_json()), boost_kind=Case.boost_kind(spec))
             fault = False
             try:
                 why = c.check_call(spec, np.random.default_rng([case["seed"], i]))
@@ -431,11 +465,14 @@ def main(argv=None):
     except GpuFault as stop:
         bad += stop.args[0]
         print("the device faulted: the soak stops here", flush=True)
+    n_boosted = sum(1 for r in lines if r.get("boost_kind"))
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
-            json.dump({"calls": lines, "cases": n_cases, "failed": bad}, f, indent=0)
-    print(f"{n_cases} cases, {len(lines)} calls;", "SOAK OK" if bad == 0 else f"SOAK FAILED ({bad})")
+            json.dump({"calls": lines, "cases": n_cases, "failed": bad, "boosted": n_boosted,
+                       "boosted_entries": sorted({r["spec"]["entry"] for r in lines if r.get("boost_kind")}),
+                       "boosted_batches": sorted({r["case"]["b"] for r in lines if r.get("boost_kind")})}, f, indent=0)
+    print(f"{n_cases} cases, {len(lines)} calls, {n_boosted} boosted;", "SOAK OK" if bad == 0 else f"SOAK FAILED ({bad})")
     return 1 if bad else 0
 
 
