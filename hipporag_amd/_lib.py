@@ -24,6 +24,9 @@ BOOST_MUL, BOOST_ADD = 0, 1
 BOOST_NONE, BOOST_SQRT = 0, 1
 BOOST_LINEAR, BOOST_EXP, BOOST_GAUSS = 0, 1, 2
 BOOST_HAS_MISSING = 1 << 24
+# HRAG_FACET_* (facets): the cap on n_bins, the bins one workgroup holds in LDS, the spec kinds
+FACET_MAX_BINS, FACET_WINDOW = 1 << 20, 4096
+FACET_CODES, FACET_EDGES = 0, 1
 HRAG_VERSION = 8      # HRAG_VERSION_MAJOR * 1000 + HRAG_VERSION_MINOR of include/hrag.h
 FLAG_DPR_FALLBACK, FLAG_ZERO_MASS, FLAG_ZERO_PHRASE, FLAG_FP8_SATURATED, FLAG_NOT_CONVERGED = 1, 2, 4, 8, 16
 # the convergence contract's error bound (include/hrag.h): error <= max(PPR_ERR_K * residual, floor of the state type);
@@ -113,6 +116,11 @@ class BoostProgramDesc(C.Structure):
                                   "c_set_ptr", "set_vals")] + [("n_terms", _I64), ("n_clauses", _I64), ("set_nnz", _I64)]
 
 
+class FacetSpecDesc(C.Structure):
+    """hrag_facet_spec: one facet spec (include/hrag.h, facets)."""
+    _fields_ = [("column", _I32), ("kind", _I32), ("n_bins", _I64), ("lo", _I64), ("edges_dev", _P), ("n_edges", _I64)]
+
+
 # name -> (restype, argtypes); every symbol include/hrag.h declares
 SIGNATURES = {
     "hrag_last_error": (C.c_char_p, []),
@@ -176,6 +184,9 @@ SIGNATURES = {
     "hrag_payload_destroy": (C.c_int, [_P]),
     "hrag_payload_filter": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I32, _P, _I64, _P, _I64, _P]),
     "hrag_bitset_count_rows": (C.c_int, [_P, _I64, _I64, _I32, _P, _P]),
+    "hrag_payload_facet_ws_bytes": (C.c_int, [_P, _I64, _I32, C.POINTER(_I64)]),
+    "hrag_payload_facet": (C.c_int, [_P, C.POINTER(FacetSpecDesc), _P, _I64, _I32, _P, _I64, _P, _I64, _P]),
+    "hrag_payload_facet_ids": (C.c_int, [_P, C.POINTER(FacetSpecDesc), _P, _I64, _I32, _I32, _P, _I64, _P]),
     "hrag_boost_rows": (C.c_int, [_P, _P, _I64, _I32, _P, _P, C.POINTER(BoostProgramDesc), _I32, _P]),
     "hrag_last_boosted": (C.c_int, [_P, _P, _I32, C.POINTER(BoostProgramDesc), _I32, _I32, _P, _I64, _I32, _P, _P, _P, _P,
                                     _P, _P]),

@@ -120,7 +120,7 @@ struct Ppr8Session {
 using namespace hrag;
 
 // a payload index (include/hrag.h, payload filters): typed per-passage columns on the device, read by payload.hip (the
-// doc filter words) and boost.hip (boosted retrieval) through the clause code of payload_clause.h
+// doc filter words) and boost.hip (boosted retrieval) through the clause code of payload_clause.h, and by facet.hip (facets)
 namespace hrag {
 struct PayCol {
     const int64_t *values;      // [n_passages] int64, or the bit patterns of doubles
@@ -134,6 +134,7 @@ struct hrag_payload {
     int32_t n_cols = 0;
     std::vector<void *> owned;          // every device allocation of the handle
     hrag::PayCol *d_cols = nullptr;     // [n_cols]
+    std::vector<int32_t> col_type;      // [n_cols] on the host: what a host check of a column's type reads (facet.hip)
 };
 
 namespace hrag {

@@ -132,6 +132,7 @@ hrag_status hrag_payload_create(int64_t n_passages, int32_t n_cols, const int32_
     if (!x) { set_error("out of host memory"); return HRAG_ENOMEM; }
     x->n_passages = n_passages;
     x->n_cols = n_cols;
+    x->col_type.assign(col_type, col_type + n_cols);
     const int64_t words = ceil_div(n_passages, 32);
     std::vector<PayCol> table((size_t)n_cols);
     hrag_status st = HRAG_OK;

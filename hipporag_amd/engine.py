@@ -22,6 +22,7 @@ from .lexical import invert_postings
 from .payload import PayloadFilter, PayloadIndex, compile_filters     # noqa: F401  (re-exported: the payload filters)
 from .boost import BoostProgram, check_program, compile_boosts        # noqa: F401  (re-exported: boosted retrieval)
 from .boost import boost_rows as _boost_rows
+from .facet import FacetCounts, FacetSpec, compile_facet              # noqa: F401  (re-exported: facets)
 
 
 def _torch():
@@ -1018,6 +1019,27 @@ class HippoRAGEngine:
                 out = self._pay_words = self._empty((self.max_batch, ix.words), _torch().int32)
         words = ix.evaluate(doc_filter, out=out)
         return words, (0 if doc_filter.broadcast else words.stride(0))
+
+    # ------------------------------------------------------------------ facets
+    def facet(self, spec_or_field, doc_filter=None, *, ids=None, batch: Optional[int] = None) -> "FacetCounts":
+        """The per-bin counts of one column of the engine's payload index (include/hrag.h, facets): spec_or_field a
+        FacetSpec (compile_facet) or the name of a keyword column; over the passages doc_filter allows -- anything a
+        doc_filter= takes, a PayloadFilter included (None: every passage) -- or over the ids int32 [B, k] a retrieve call
+        returned.  batch: the rows of a per-query doc_filter (None: what the filter itself holds); one filter for the batch
+        gives one row.  A workspace handle counts over its parent's index."""
+        ix = self._payload_ix("facet")
+        spec = spec_or_field if isinstance(spec_or_field, FacetSpec) else compile_facet(ix, spec_or_field)
+        if ids is not None:
+            if doc_filter is not None:
+                raise ValueError("facet: doc_filter or ids, not both")
+            return ix.facet(spec, ids=ids)
+        if doc_filter is None:
+            return ix.facet(spec)
+        if batch is None:
+            batch = (doc_filter.batch if isinstance(doc_filter, PayloadFilter)
+                     else doc_filter.shape[0] if getattr(doc_filter, "ndim", 1) == 2 else 1)
+        words, _ = self._filter_words(doc_filter, batch, own=True)
+        return ix.facet(spec, words)
 
     # ------------------------------------------------------------------ lexical retrieval
     def set_lexical_index(self, ix: Optional["LexicalIndex"]):

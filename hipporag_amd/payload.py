@@ -427,6 +427,16 @@ class PayloadIndex(PayloadColumns):
         """int32 [B]: how many passages each row of packed doc filter words ([W] or [B, W]) allows (hrag_bitset_count_rows)."""
         return count_rows(words, self.n_passages)
 
+    def facet(self, spec, words=None, *, ids=None, out=None):
+        """The per-bin counts of a FacetSpec (facet.compile_facet; include/hrag.h, facets) as a FacetCounts: over the
+        passages `words` allows -- None (all of them), packed words [W] / [B, W], a bool mask [n] / [B, n], or a PayloadFilter
+        (evaluated first; a broadcast one gives one row) -- by hrag_payload_facet, or over the passage ids `ids` int32 device
+        [B, k] as retrieve returns them (the -1 padding and ids outside the index are skipped, a repeated id counts each
+        time) by hrag_payload_facet_ids.  out: int32 device [>= B, >= n_bins + 2] to write into (entries beyond n_bins + 2
+        of a row are left alone).  The workspace is allocated per call; enqueues on the current stream."""
+        from .facet import facet_counts
+        return facet_counts(self, spec, words, ids=ids, out=out)
+
     def close(self):
         if getattr(self, "_handle", None) and self._handle.value:
             check(self._lib.hrag_payload_destroy(self._handle))

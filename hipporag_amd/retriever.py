@@ -1012,6 +1012,36 @@ class HippoRAG:
             if hasattr(self.engine, "set_payload_index"):      # (boost= evaluates over it inside the engine's calls)
                 self.engine.set_payload_index(self.payload_index)
 
+    # ------------------------------------------------------------------ facets
+    def facets(self, fields, doc_filter=None, limit: int = 10, **spec_kw) -> List[dict]:
+        """What is in there (include/hrag.h, facets; needs RetrievalConfig.payload_index=True): for each metadata key of
+        `fields` (a name or a list of names; "source_id" included) the number of passages per value, over the passages
+        doc_filter allows -- what retrieve takes: one dict / bool array for every query, or a list with one per query; None:
+        every passage.  spec_kw: compile_facet's edges= or lo= / n_values= for a number key.  One dict per query (one for a
+        single filter): {field: {"values": [(label, count), ...] -- the `limit` largest, count descending --, "other",
+        "missing", "total" (the allowed passages)}}."""
+        if not self.global_config.payload_index:
+            raise ValueError("facets needs RetrievalConfig.payload_index=True (the counts are taken over the chunk metadata as "
+                             "typed columns on the device)")
+        import torch
+        from .facet import compile_facet, top_of
+        self._ensure_ready()
+        ix = self.payload_index
+        if ix is None:
+            raise ValueError("facets: the index holds no passages")
+        names = [fields] if isinstance(fields, str) else list(fields)
+        nq = len(doc_filter) if isinstance(doc_filter, list) else 1
+        words = self._doc_filter_words(doc_filter, nq)
+        if words is not None:
+            words = torch.from_numpy(np.ascontiguousarray(words).view(np.int32)).to(ix.device)
+        out = [{} for _ in range(nq)]
+        for name in names:
+            fc = ix.facet(compile_facet(ix, name, **spec_kw), words)
+            raw = fc.raw.cpu().numpy()
+            for q, top in enumerate(top_of(raw[:, :fc.spec.n_bins], fc.labels, limit)):
+                out[q][name] = {"values": top, "other": int(raw[q, -2]), "missing": int(raw[q, -1]), "total": int(raw[q].sum())}
+        return out
+
     # ------------------------------------------------------------------ lexical retrieval
     def _drop_lexical(self):
         ix = getattr(self, "lexical_index", None)

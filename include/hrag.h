@@ -75,7 +75,9 @@ extern "C" {
  *        hrag_lex_blend_rows;
  *        later in 0.8 (detect by the symbol): payload filters -- hrag_payload_create, hrag_payload_destroy,
  *        hrag_payload_filter, hrag_bitset_count_rows;
- *        later in 0.8 (detect by the symbol): boosted retrieval -- hrag_boost_rows, hrag_last_boosted. */
+ *        later in 0.8 (detect by the symbol): boosted retrieval -- hrag_boost_rows, hrag_last_boosted;
+ *        later in 0.8 (detect by the symbol): facets -- hrag_payload_facet, hrag_payload_facet_ids,
+ *        hrag_payload_facet_ws_bytes. */
 #define HRAG_VERSION_MAJOR 0
 #define HRAG_VERSION_MINOR 8
 
@@ -973,6 +975,80 @@ hrag_status hrag_payload_filter(const hrag_payload *pay, const int32_t *f_ptr_de
  * Enqueues on `stream`. */
 hrag_status hrag_bitset_count_rows(const uint32_t *words_dev, int64_t ld, int64_t n, int32_t batch, int32_t *count_out_dev,
                                    hrag_stream stream);
+
+/* ---- facets: per-value counts of a payload column, counted on the device ----
+ * A payload condition restricts a retrieval and hrag_bitset_count_rows says how many passages it leaves.  A FACET says what
+ * is in there: for one column of a payload index and a set of allowed passages -- the words of any doc filter, or a list
+ * of passage ids as a retrieve call returns them -- how many of them fall into each bin of the column's values (Qdrant's
+ * facet API, Elasticsearch's terms / range / histogram aggregations).
+ *
+ * A facet SPEC names the column and maps a present value x to a bin in [0, n_bins) or to "other":
+ *   HRAG_FACET_CODES  (I64 columns only; a keyword column is this with lo = 0)
+ *                     bin = x - lo when x >= lo && (uint64)(x - lo) < n_bins, else other.  Both conditions are needed:
+ *                     x = INT64_MIN with lo = INT64_MAX wraps to 1 and is other.
+ *   HRAG_FACET_EDGES  (I64 or F64 columns) edges_dev holds n_edges ascending bounds as 8-byte words of the column's type and
+ *                     n_bins == n_edges + 1; bin = the number of edges <= x, found by binary search with comparisons in the
+ *                     column's type, as HRAG_PAY_IN matches its set: bin 0 is x < edges[0], bin i is edges[i - 1] <= x <
+ *                     edges[i], the last bin is x >= edges[n_edges - 1].  No arithmetic on values is involved, so nothing
+ *                     rounds; -0.0 equals 0.0; a NaN value of an F64 column is other; equal neighbouring edges give an
+ *                     empty bin; n_edges == 0 is legal and gives one bin.
+ * For query b the output row counts_out_dev[b * ld_c ...] (int32, ld_c >= n_bins + 2) holds
+ *   [v], v < n_bins   the allowed passages p < n_passages at which the column is present and whose value maps to bin v;
+ *   [n_bins]          "other": allowed and present, the value maps to no bin;
+ *   [n_bins + 1]      "missing": allowed, the column is not present;
+ * so a row sums to the number of allowed passages -- exactly what hrag_bitset_count_rows gives for the same words.  The
+ * entries [n_bins + 2, ld_c) of a row are never written.
+ *
+ * The edges live on the device and their order cannot be checked on the host: unsorted edges (or NaN edges) give
+ * UNSPECIFIED bins but never an out-of-range write -- the search keeps 0 <= bin <= n_edges whatever the edges hold, and
+ * every bin index is bounded by n_bins before it is used.
+ *
+ * Counts are integers and integer addition does not depend on its order, so the result is exact and the same on every
+ * run although the kernels add with LDS atomics (csrc/facet.hip: one workgroup per query, window of HRAG_FACET_WINDOW bins
+ * and split of the passage range; an int32 histogram of the window in LDS; the splits summed in split order by a second
+ * kernel).  No global atomics, no memset; every output word is written exactly once.
+ *
+ * OUT OF SCOPE: score-weighted facets (the sum of scores per value is what group_agg = "sum" computes), facets of several
+ * columns at once, multi-valued fields, facets inside the row-shard, hybrid or captured forms. */
+#define HRAG_FACET_MAX_BINS (1 << 20)    /* n_bins of one spec */
+#define HRAG_FACET_WINDOW 4096           /* bins one workgroup holds in LDS (tests pick their sizes by it) */
+#define HRAG_FACET_CODES 0               /* spec kinds */
+#define HRAG_FACET_EDGES 1
+
+typedef struct hrag_facet_spec {
+    int32_t column;             /* the column of the payload index */
+    int32_t kind;               /* HRAG_FACET_CODES / HRAG_FACET_EDGES */
+    int64_t n_bins;             /* 1 .. HRAG_FACET_MAX_BINS; EDGES: n_edges + 1 */
+    int64_t lo;                 /* CODES: the value of bin 0 */
+    const void *edges_dev;      /* EDGES: n_edges 8-byte words on the device (may be NULL when n_edges == 0) */
+    int64_t n_edges;            /* EDGES: the number of bounds; CODES: ignored */
+} hrag_facet_spec;
+
+/* The bytes of workspace hrag_payload_facet needs for (the handle's n_passages, n_bins, batch): 0 when one workgroup per
+ * (query, window) streams the whole passage range -- batch * ceil(n_bins / HRAG_FACET_WINDOW) >= 1024 workgroups fill the
+ * machine on their own -- else 4 * batch * n_splits * (n_bins + 2) for the partial counts of n_splits equal runs of
+ * HRAG_PAY_TILE-passage tiles, n_splits a pure function of the three numbers (about 1024 workgroups in all, at most one
+ * split per tile).  A caller that wants n_splits reads it off this value. */
+hrag_status hrag_payload_facet_ws_bytes(const hrag_payload *pay, int64_t n_bins, int32_t batch, int64_t *out);
+
+/* The counts of `spec` under doc filter words: words_dev uint32 [batch, ld_w] (ld_w >= ceil(n_passages / 32)), one row for
+ * the batch when ld_w == 0, every passage allowed when NULL.  Bits at or above n_passages in the last word are ignored and
+ * words beyond ceil(n_passages / 32) are never read.  ws_dev: ws_bytes >= hrag_payload_facet_ws_bytes of workspace (may be
+ * NULL when that is 0); its contents before and after the call mean nothing.  Enqueues on `stream`; nothing is allocated,
+ * synchronised or read back.  HRAG_EINVAL: a NULL handle, spec or output; a column outside the index; an unknown kind;
+ * CODES on an F64 column; n_bins outside [1, HRAG_FACET_MAX_BINS]; EDGES with n_bins != n_edges + 1 or NULL edges; ld_c <
+ * n_bins + 2; ld_w neither 0 nor >= ceil(n_passages / 32); rows that are not 4-byte (edges: 8-byte) aligned; batch outside
+ * [1, 65535]; ws_bytes below what the query call returns. */
+hrag_status hrag_payload_facet(const hrag_payload *pay, const hrag_facet_spec *spec, const uint32_t *words_dev, int64_t ld_w,
+                               int32_t batch, int32_t *counts_out_dev, int64_t ld_c, void *ws_dev, int64_t ws_bytes,
+                               hrag_stream stream);
+
+/* The same counts over lists of passage ids: idx_dev int32 [batch, ld_i], the first k of a row read (ld_i >= k >= 1), as
+ * the retrieve calls return them.  An id outside [0, n_passages) -- the -1 padding included -- is skipped and counted
+ * nowhere; a repeated id counts each time.  One workgroup per (query, window): the ids read coalesced, the column gathered
+ * at each id.  No workspace. */
+hrag_status hrag_payload_facet_ids(const hrag_payload *pay, const hrag_facet_spec *spec, const int32_t *idx_dev, int64_t ld_i,
+                                   int32_t k, int32_t batch, int32_t *counts_out_dev, int64_t ld_c, hrag_stream stream);
 
 /* ---- boosted retrieval: payload-driven score boosts and decay functions on the device ----
  * A payload condition above can only EXCLUDE a passage.  A boost PROGRAM prefers instead: it rewrites score rows in place
