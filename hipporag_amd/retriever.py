@@ -251,9 +251,17 @@ def unpack_mask(words, n: int) -> np.ndarray:
     return np.unpackbits(w.view(np.uint8), axis=-1, bitorder="little")[..., :n].astype(bool)
 
 
+def ranked_scores(sc):
+    """fp32 scores as every device ranking returns them: the quiet NaN, -0 as +0."""
+    sc = np.array(sc, np.float32)
+    sc[np.isnan(sc)] = np.float32(np.nan)
+    return sc + np.float32(0)
+
+
 def rank_allowed(full, allowed, want: int):
     """The host form of the filtered ranking: per row, the first `want` entries of np.argsort(x, kind="stable")[::-1]
-    that `allowed` (bool [n] or [B, n]) admits, -1 / 0 beyond them -> (ids int32 [B, want], scores fp32 [B, want])."""
+    that `allowed` (bool [n] or [B, n]) admits, -1 / 0 beyond them -> (ids int32 [B, want], scores fp32 [B, want]);
+    scores as every ranking returns them (ranked_scores)."""
     full = np.asarray(full, np.float32)
     b = full.shape[0]
     allowed = np.broadcast_to(np.asarray(allowed, bool), full.shape)
@@ -264,7 +272,7 @@ def rank_allowed(full, allowed, want: int):
         order = order[allowed[i][order]][:want]
         idx[i, :len(order)] = order
         sc[i, :len(order)] = full[i][order]
-    return idx, sc
+    return idx, ranked_scores(sc)
 
 
 def group_hits_rows(full, group_of, allowed, group_idx, hits: int):
@@ -291,8 +299,7 @@ def group_hits_rows(full, group_of, allowed, group_idx, hits: int):
                 top = members[start[gg]: min(start[gg + 1], start[gg] + hits)]
                 hi[i, j, :len(top)] = top
                 hs[i, j, :len(top)] = full[i][top]
-    hs[np.isnan(hs)] = np.float32(np.nan)
-    return hi, hs + np.float32(0)
+    return hi, ranked_scores(hs)
 
 
 def group_rank_rows(full, group_of, allowed, want: int, agg: str = "max", hits: Optional[int] = None):
@@ -323,6 +330,7 @@ def group_rank_rows(full, group_of, allowed, want: int, agg: str = "max", hits: 
         rank = np.argsort(score, kind="stable")[::-1]
         rank = rank[has[rank]][:want]
         gi[i, :len(rank)], gs[i, :len(rank)], rep[i, :len(rank)] = rank, score[rank], best[rank]
+    gs = ranked_scores(gs)
     if hits is not None:
         return (gi, gs, rep) + group_hits_rows(full, group_of, allowed, gi, hits)
     return gi, gs, rep
@@ -605,7 +613,7 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
                 d_idx, d_sc = rank_allowed(full, unpack_mask(rows_w, full.shape[1]), want)
             else:
                 d_idx = np.stack([np.argsort(r, kind="stable")[::-1][:want] for r in full]).astype(np.int32)
-                d_sc = np.take_along_axis(full, d_idx.astype(np.int64), axis=1)
+                d_sc = ranked_scores(np.take_along_axis(full, d_idx.astype(np.int64), axis=1))
         tick("ppr_time", t0)
         rows = BatchRows()
         rows.doc_idx, rows.doc_score, rows.group_idx = d_idx, d_sc, g_idx
