@@ -27,6 +27,8 @@ BOOST_HAS_MISSING = 1 << 24
 # HRAG_FACET_* (facets): the cap on n_bins, the bins one workgroup holds in LDS, the spec kinds
 FACET_MAX_BINS, FACET_WINDOW = 1 << 20, 4096
 FACET_CODES, FACET_EDGES = 0, 1
+# HRAG_LATE_* (late-interaction reranking): the caps on dim, on the tokens of one query and on the candidates of one row
+LATE_MAX_DIM, LATE_MAX_QUERY_TOKENS, LATE_MAX_CANDIDATES = 256, 64, 1024
 HRAG_VERSION = 8      # HRAG_VERSION_MAJOR * 1000 + HRAG_VERSION_MINOR of include/hrag.h
 FLAG_DPR_FALLBACK, FLAG_ZERO_MASS, FLAG_ZERO_PHRASE, FLAG_FP8_SATURATED, FLAG_NOT_CONVERGED = 1, 2, 4, 8, 16
 # the convergence contract's error bound (include/hrag.h): error <= max(PPR_ERR_K * residual, floor of the state type);
@@ -190,6 +192,12 @@ SIGNATURES = {
     "hrag_boost_rows": (C.c_int, [_P, _P, _I64, _I32, _P, _P, C.POINTER(BoostProgramDesc), _I32, _P]),
     "hrag_last_boosted": (C.c_int, [_P, _P, _I32, C.POINTER(BoostProgramDesc), _I32, _I32, _P, _I64, _I32, _P, _P, _P, _P,
                                     _P, _P]),
+    "hrag_late_create": (C.c_int, [_I64, _P, _P, _I32, _I32, C.POINTER(_P)]),
+    "hrag_late_destroy": (C.c_int, [_P]),
+    "hrag_late_scores": (C.c_int, [_P, _P, _P, _P, _I32, _P, _I32, _P, _I64, _P]),
+    "hrag_late_rank_rows": (C.c_int, [_P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _P]),
+    "hrag_late_workspace_bytes": (C.c_int64, [_I32, _I32]),
+    "hrag_late_rerank": (C.c_int, [_P, _P, _P, _P, _I32, _P, _I32, _I32, _P, _P, _P, _P, C.c_size_t, _P]),
     "hrag_ppr_sweeps": (C.c_int, [_P, _I32, _I32, _F32, _I32, _P]),
     "hrag_ppr_layout": (C.c_int, [_P, _I32, C.POINTER(_I32), C.POINTER(_I32)]),
     "hrag_row_minmax": (C.c_int, [_P, _I32, _I64, _I64, _P, _P, _P]),

@@ -23,6 +23,8 @@ from .payload import PayloadFilter, PayloadIndex, compile_filters     # noqa: F4
 from .boost import BoostProgram, check_program, compile_boosts        # noqa: F401  (re-exported: boosted retrieval)
 from .boost import boost_rows as _boost_rows
 from .facet import FacetCounts, FacetSpec, compile_facet              # noqa: F401  (re-exported: facets)
+from .late import (LATE_DTYPES, LateQueries, TokenIndex, check_late, late_plan,      # noqa: F401  (re-exported: late-interaction
+                   refuse_late)                                                    # reranking)
 
 
 def _torch():
@@ -411,6 +413,8 @@ class RetrieveOutput:
     hit_score: "object" = None   # torch fp32 [B, k, m]: each hit's own passage score (0 where hit_idx is -1)
     mmr_value: "object" = None   # mmr_lambda=: torch fp32 [B, k], the MMR value of each pick; doc_idx / doc_score then hold
                                  # the picks in MMR order with their own retrieval scores
+    first_score: "object" = None  # late=: torch fp32 [B, k], the first-stage score of each returned entry (0 where doc_idx is
+                                  # -1); doc_score then holds the late scores
 
     @property
     def group_score(self):       # the grouped call's names for the two tensors above
@@ -517,6 +521,8 @@ class PendingRetrieve:
                 out.hit_idx[rt], out.hit_score[rt] = o2.hit_idx, o2.hit_score
             if out.mmr_value is not None:
                 out.mmr_value[rt] = o2.mmr_value
+            if out.first_score is not None:
+                out.first_score[rt] = o2.first_score
             out.flags[rt], out.residual[rt], out.iters_used[rt] = o2.flags, o2.residual, o2.iters_used
             if self.want_all_scores:
                 out.all_scores[rt] = o2.all_scores
@@ -716,7 +722,7 @@ class HippoRAGEngine:
         w._handle = C.c_void_p(0)
         w._workspaces = []
         w._parent = root
-        w._fuse_ws = w._fuse_host = w._mmr_ws = None         # last_fused / mmr: scratch buffers of its own
+        w._fuse_ws = w._fuse_host = w._mmr_ws = w._late_ws = None      # last_fused / mmr / late: scratch buffers of its own
         w._pay_words = None                                  # ... and the words of a PayloadFilter doc filter
         with _torch().cuda.device(root.device):
             check(root._lib.hrag_workspace_create(root._handle, C.byref(w._handle)))
@@ -830,7 +836,8 @@ class HippoRAGEngine:
                  want_residual: bool = True, doc_filter=None, filter_scope: str = "ranking",
                  group_agg: Optional[str] = None, group_hits: Optional[int] = None,
                  mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None,
-                 lexical=None, lexical_weight: float = 0.5, boost=None) -> RetrieveOutput:
+                 lexical=None, lexical_weight: float = 0.5, boost=None, late=None,
+                 late_candidates: Optional[int] = None) -> RetrieveOutput:
         """Phase B: seeds + passage prior + PPR + ranking (DPR ranking where kept_count == 0).
         ppr_tol / ppr_max_iters: the convergence contract of include/hrag.h (0 = exactly ppr_iters sweeps);
         the output carries the per-query residual and the sweeps that ran.
@@ -856,33 +863,47 @@ class HippoRAGEngine:
         the call runs as it does without it, then hrag_last_boosted rewrites the score rows it left as s * M + A and ranks
         them again with the call's k, doc filter, group_agg, group_hits and mmr_*: every ranking output is that of the
         boosted rows, flags / residual / iters_used stay the call's, and last_doc_scores / last_fused afterwards read the
-        boosted rows.  The first ranking is computed and discarded.  None: the call is exactly the plain one."""
+        boosted rows.  The first ranking is computed and discarded.  None: the call is exactly the plain one.
+        late= a LateQueries (after set_token_index; include/hrag.h, late-interaction reranking): the call ranks
+        c = max(late_candidates, k) <= min(max_topk, 1024) entries (late_candidates None: k) as it does without it -- under
+        the doc filter, the lexical blend and the boost -- then hrag_late_rerank rescores them by MaxSim over the token index
+        and the k best by late score are returned: doc_score carries the late scores, first_score each entry's first-stage
+        score, a tie goes to the earlier first-stage rank.  With mmr_lambda, MMR picks its k among the c rescored entries
+        with the late scores as relevance (mmr_candidates is then refused: the candidates are the late ones).  Not with
+        group_agg / group_hits: a group's score is not a passage's.  None: the call is exactly the plain one."""
+        lp = late_plan(late, late_candidates, k)
         if lexical is not None:
             mmr = mmr_plan(mmr_lambda, mmr_candidates, k)     # (refused before the blend is enqueued)
             self._check_mmr_fits(mmr)
+            self._check_late_fits(lp, mmr, group_agg, group_hits)
             rows = self._lexical_blend(None, q_pass, lexical, lexical_weight, filter_scope, doc_filter)
             return self._retrieve("hrag_retrieve_scored", rows, (kept_idx, kept_score, kept_count),
                                   (link_top_k, damping, passage_node_weight, ppr_iters, max(ppr_max_iters, ppr_iters), ppr_tol),
                                   k, want_residual or ppr_tol > 0, doc_filter=doc_filter, filter_scope=filter_scope,
-                                  group_agg=group_agg, group_hits=group_hits, mmr=mmr, boost=boost)
+                                  group_agg=group_agg, group_hits=group_hits, mmr=mmr, boost=boost, late=lp)
         return self._retrieve("hrag_retrieve", q_pass, (kept_idx, kept_score, kept_count),
                               (link_top_k, damping, passage_node_weight, ppr_iters, max(ppr_max_iters, ppr_iters), ppr_tol), k,
                               want_residual or ppr_tol > 0, doc_filter=doc_filter, filter_scope=filter_scope,
                               group_agg=group_agg, group_hits=group_hits, mmr=mmr_plan(mmr_lambda, mmr_candidates, k),
-                              boost=boost)
+                              boost=boost, late=lp)
 
     def _retrieve(self, base, source, kept, ppr, k, report, *, doc_filter, filter_scope, group_agg, group_hits, mmr=None,
-                  boost=None):
+                  boost=None, late=None):
         """The one binding behind retrieve / retrieve_scored / dense_retrieve (base = "hrag_retrieve", "hrag_retrieve_scored"
         or "hrag_dense_retrieve"): the scope / agg / hits checks, inputs and outputs on the device, the filter words, the
         argument list from its named pieces, and the exported function that serves this combination -- base itself, or base +
         "_filtered" / "_scoped" / "_grouped".  kept (idx, score, count) and ppr (link_top_k .. ppr_tol, in the ABI's order)
         are None / () for the dense call, which has no flags either; report: allocate residual / iters_used.
         mmr: None or mmr_plan's (lambda, c): c entries are ranked and _mmr_picks keeps k of them.
-        boost: None, or the rows the call left are boosted and ranked again (_last_boosted) before MMR and the hits."""
+        boost: None, or the rows the call left are boosted and ranked again (_last_boosted) before MMR and the hits.
+        late: None or late_plan's (LateQueries, c): c entries are ranked, _late_picks rescores them and keeps the k best
+        (all c of them in late order when MMR follows)."""
         torch = _torch()
         k_out, k = k, (k if mmr is None else mmr[1])
         self._check_mmr_fits(mmr)
+        self._check_late_fits(late, mmr, group_agg, group_hits)
+        if late is not None:
+            k = late[1]
         scoped = check_filter_scope(filter_scope, doc_filter)
         agg = check_group_agg(group_agg)
         hits = check_group_hits(group_hits, group_agg)
@@ -895,6 +916,8 @@ class HippoRAGEngine:
             src = self._q(source)
             head = (self._handle, src.data_ptr(), src.shape[0])
         b = src.shape[0]
+        if late is not None:
+            check_late(late[0], k_out, late[1], b)
         prog = None if boost is None else self._boost_program(boost, b)      # (refused before anything is enqueued)
         out = RetrieveOutput(self._empty((b, k), torch.int32), self._empty((b, k), torch.float32), None)
         tail = (_stream(),)
@@ -924,6 +947,8 @@ class HippoRAGEngine:
             check(getattr(self._lib, base + ("_scoped" if scoped else "_filtered"))(*head, k, *docs, *tail, fw.data_ptr(), fld))
         if prog is not None:
             self._last_boosted(out, prog, b, k, fw, fld, agg)
+        if late is not None:
+            self._late_picks(out, late[0], k if mmr is not None else k_out)
         if mmr is not None:
             self._mmr_picks(out, k_out, mmr[0])
         if hits is not None:    # over the rows this call left, with its group ids and its filter
@@ -1143,6 +1168,95 @@ class HippoRAGEngine:
         rows, _, _ = self._lex_rows(qp, qt, qw)
         return self._rank_rows(rows, k, False, doc_filter)
 
+    # ------------------------------------------------------------------ late-interaction reranking
+    def set_token_index(self, ix: Optional["TokenIndex"]):
+        """The TokenIndex the late= calls of this engine and of its workspaces rescore against (None: none; include/hrag.h,
+        late-interaction reranking).  Held by reference on the Python side only: the library's engine does not know it, and
+        closing it is the caller's."""
+        root = getattr(self, "_parent", None) or self
+        if ix is not None:
+            if root.n_rows != root.num_vertices or root.passage_rows != root.n_passages:
+                raise NotImplementedError("set_token_index on a row-shard engine: late reranking is served by the unsharded "
+                                          "engine only")
+            if ix.n_passages != root.n_passages:
+                raise ValueError(f"the token index covers {ix.n_passages} passages, the engine {root.n_passages}")
+            if ix.device != root.device:
+                raise ValueError(f"the token index lives on {ix.device}, the engine on {root.device}")
+        root._token_index = ix
+
+    def _token_ix(self, late: "LateQueries") -> "TokenIndex":
+        ix = getattr(getattr(self, "_parent", None) or self, "_token_index", None)
+        if ix is None or not ix._handle.value:
+            raise ValueError("late: no token index on this engine (set_token_index)")
+        if late.dim != ix.dim or late.dtype != ix.dtype:
+            raise ValueError(f"late: the queries are {late.dtype} of dim {late.dim}, the token index {ix.dtype} of dim {ix.dim}")
+        if late.device != self.device:
+            raise ValueError(f"late: the queries live on {late.device}, the engine on {self.device}")
+        return ix
+
+    def _late_cand(self, cand_idx, late, k: int):
+        torch = _torch()
+        ci = cand_idx.to(self.device, torch.int32).contiguous()
+        if ci.dim() != 2:
+            raise ValueError("cand_idx must be [B, c]")
+        check_late(late, k, ci.shape[1], ci.shape[0])
+        return ci, self._token_ix(late)
+
+    def late_scores(self, cand_idx, late: "LateQueries"):
+        """The late scores fp32 [B, c] (hrag_late_scores) of candidates int32 [B, c] (passage positions; -1 or an id outside
+        [0, n_passages): an empty slot, 0.0) under the late queries of the batch, over the engine's token index."""
+        torch = _torch()
+        ci, ix = self._late_cand(cand_idx, late, 1)
+        b, c = ci.shape
+        out = self._empty((b, c), torch.float32)
+        check(self._lib.hrag_late_scores(ix._handle, late.q_ptr.ctypes.data, late.q_ptr_dev.data_ptr(),
+                                         late.q_tok.data_ptr() if late.n_tokens else None, b, ci.data_ptr(), c,
+                                         out.data_ptr(), out.stride(0), _stream()))
+        return out
+
+    def late_rerank(self, cand_idx, late: "LateQueries", k: int, return_sel: bool = False):
+        """Late reranking (hrag_late_rerank) of candidates int32 [B, c] in the order a ranking returned them: (idx int32,
+        score fp32) [B, k], the k best by late score -- a tie to the smaller slot -- and -1 / 0 once the non-empty slots
+        run out.  return_sel: a third entry, the slot of each pick in its candidate row (-1 beyond).  Everything stays on
+        the device."""
+        torch = _torch()
+        ci, ix = self._late_cand(cand_idx, late, k)
+        b, c = ci.shape
+        idx, sc = self._empty((b, k), torch.int32), self._empty((b, k), torch.float32)
+        sel = self._empty((b, k), torch.int32)
+        need = int(self._lib.hrag_late_workspace_bytes(b, c))
+        ws = getattr(self, "_late_ws", None)
+        if ws is None or ws.numel() < need or ws.device != self.device:
+            ws = self._late_ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        check(self._lib.hrag_late_rerank(ix._handle, late.q_ptr.ctypes.data, late.q_ptr_dev.data_ptr(),
+                                         late.q_tok.data_ptr() if late.n_tokens else None, b, ci.data_ptr(), c, k,
+                                         sel.data_ptr(), idx.data_ptr(), sc.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+        return (idx, sc, sel) if return_sel else (idx, sc)
+
+    def _check_late_fits(self, late, mmr=None, group_agg=None, group_hits=None) -> None:
+        """What a late= call refuses before any work: grouping, mmr_candidates, c entries beyond max_topk."""
+        if late is None:
+            return
+        for name, v in (("group_agg", group_agg), ("group_hits", group_hits)):
+            if v is not None:
+                raise ValueError(f"late does not serve {name}: a group's score is not a passage's -- rescore the passages "
+                                 "(retrieve(late=...)) and group the result, or use late_rerank on the representatives")
+        if mmr is not None and mmr[1] > late[1]:
+            raise ValueError(f"late with mmr_candidates={mmr[1]}: MMR picks among the c = {late[1]} late candidates -- pass "
+                             "late_candidates, not mmr_candidates")
+        if late[1] > self.max_topk:
+            raise ValueError(f"late_candidates: the call would rank c = max(late_candidates, k) = {late[1]} entries, the "
+                             f"engine ranks at most max_topk={self.max_topk}")
+
+    def _late_picks(self, out: RetrieveOutput, late: "LateQueries", k: int) -> None:
+        """Replace the ranked c entries of `out` by their k best by late score: doc_idx, doc_score (the late scores) and
+        first_score (each entry's first-stage score, by the slot of the pick)."""
+        torch = _torch()
+        idx, sc, sel = self.late_rerank(out.doc_idx, late, k, return_sel=True)
+        first = torch.gather(out.doc_score, 1, sel.clamp_min(0).long())
+        out.first_score = torch.where(sel >= 0, first, torch.zeros_like(first))
+        out.doc_idx, out.doc_score = idx, sc
+
     def mmr(self, cand_idx, cand_score, k: int, lam: float = 0.5, normalize: bool = True, return_sel: bool = False):
         """MMR re-ranking (hrag_mmr; include/hrag.h, diversified retrieval) of candidates int32 [B, c] (passage positions in
         the order a ranking returned them; -1 or an id outside [0, n_passages): an empty slot) with their scores fp32
@@ -1192,6 +1306,9 @@ class HippoRAGEngine:
         if out.group_idx is not None:
             gi = torch.gather(out.group_idx, 1, sel.clamp_min(0).long())
             out.group_idx = torch.where(sel >= 0, gi, torch.full_like(gi, -1))
+        if out.first_score is not None:      # (after _late_picks: the first-stage scores follow the picks)
+            fs = torch.gather(out.first_score, 1, sel.clamp_min(0).long())
+            out.first_score = torch.where(sel >= 0, fs, torch.zeros_like(fs))
         out.doc_idx, out.doc_score, out.mmr_value = idx, sc, val
 
     def last_group_hits(self, group_idx, hits: int, filter_words=None, filter_ld: int = 0):
@@ -1211,7 +1328,8 @@ class HippoRAGEngine:
     def last_fused(self, member_ptr, *, weights=None, fuse: str = "rrf", rrf_c: int = 60, rrf_depth: Optional[int] = None,
                    k: int = 200, doc_filter=None, group_agg: Optional[str] = None,
                    group_hits: Optional[int] = None, mmr_lambda: Optional[float] = None,
-                   mmr_candidates: Optional[int] = None, boost=None) -> RetrieveOutput:
+                   mmr_candidates: Optional[int] = None, boost=None, late=None,
+                   late_candidates: Optional[int] = None) -> RetrieveOutput:
         """One ranking per QUESTION from the score rows the last retrieve / retrieve_scored / grouped dense_retrieve on this
         handle left (hrag_last_fused; include/hrag.h, fused retrieval): member_ptr int [Q + 1] cuts those B = member_ptr[-1]
         rows into Q questions of consecutive member rows, weights [B] (None: all 1) weigh them, fuse = "sum" (fp64, in member
@@ -1222,11 +1340,16 @@ class HippoRAGEngine:
         Afterwards last_doc_scores(Q) returns the fused rows.  mmr_lambda / mmr_candidates: as on retrieve, over the fused
         ranking.  boost= (one list for the questions, or one per question): the fused rows are boosted (hrag_last_boosted)
         and the ranking, the groups, the hits and MMR are those of the boosted fused rows; the fusion itself then ranks
-        nothing.  (After a retrieve(boost=) the member rows are boosted already: last_fused fuses boosted rows.)"""
+        nothing.  (After a retrieve(boost=) the member rows are boosted already: last_fused fuses boosted rows.)
+        late= / late_candidates= (one LateQueries entry per QUESTION): as on retrieve, over the fused ranking."""
         torch = _torch()
         mmr = mmr_plan(mmr_lambda, mmr_candidates, k)
+        lp = late_plan(late, late_candidates, k)
         k_out, k = k, (k if mmr is None else mmr[1])
         self._check_mmr_fits(mmr)
+        self._check_late_fits(lp, mmr, group_agg, group_hits)
+        if lp is not None:
+            k = lp[1]
         agg = check_group_agg(group_agg)
         hits = check_group_hits(group_hits, group_agg)
         b = int(np.asarray(member_ptr).reshape(-1)[-1]) if np.size(member_ptr) else 0
@@ -1234,6 +1357,8 @@ class HippoRAGEngine:
         mode, mp, w, c, depth = check_fuse(fuse, member_ptr, b, weights, rrf_c,
                                            min(k, dmax) if rrf_depth is None else rrf_depth, dmax)
         nq = mp.shape[0] - 1
+        if lp is not None:
+            check_late(lp[0], k_out, lp[1], nq)
         prog = None if boost is None else self._boost_program(boost, nq)
         fw, fld = (None, 0) if doc_filter is None else self._filter_words(doc_filter, nq)
         need = int(self._lib.hrag_fuse_workspace_bytes(b, self.n_passages, mode, depth, 1 if fld else 0))
@@ -1258,6 +1383,8 @@ class HippoRAGEngine:
         out.group_idx = gi
         if prog is not None:        # (the fusion above ranked nothing: the boosted fused rows are ranked here)
             self._last_boosted(out, prog, nq, k, fw, fld, agg)
+        if lp is not None:
+            self._late_picks(out, lp[0], k if mmr is not None else k_out)
         if mmr is not None:
             self._mmr_picks(out, k_out, mmr[0])
         if hits is not None:
@@ -1270,18 +1397,20 @@ class HippoRAGEngine:
                         filter_scope: str = "ranking", group_agg: Optional[str] = None,
                         group_hits: Optional[int] = None, mmr_lambda: Optional[float] = None,
                         mmr_candidates: Optional[int] = None, lexical=None, lexical_weight: float = 0.5,
-                        boost=None) -> RetrieveOutput:
+                        boost=None, late=None, late_candidates: Optional[int] = None) -> RetrieveOutput:
         """retrieve() with the raw passage scores fp32 [B, >= Np] supplied by the caller (hrag_retrieve_scored).
         lexical / lexical_weight: as on retrieve(), blended into the caller's rows (which are left as they are).
-        boost: as on retrieve()."""
+        boost, late / late_candidates: as on retrieve()."""
         mmr = mmr_plan(mmr_lambda, mmr_candidates, k)
+        lp = late_plan(late, late_candidates, k)
         if lexical is not None:
             self._check_mmr_fits(mmr)                         # (refused before the blend is enqueued)
+            self._check_late_fits(lp, mmr, group_agg, group_hits)
             pass_scores = self._lexical_blend(pass_scores, None, lexical, lexical_weight, filter_scope, doc_filter)
         return self._retrieve("hrag_retrieve_scored", pass_scores, (kept_idx, kept_score, kept_count),
                               (link_top_k, damping, passage_node_weight, ppr_iters, max(ppr_max_iters, ppr_iters), ppr_tol), k,
                               True, doc_filter=doc_filter, filter_scope=filter_scope, group_agg=group_agg,
-                              group_hits=group_hits, mmr=mmr, boost=boost)
+                              group_hits=group_hits, mmr=mmr, boost=boost, late=lp)
 
     def retrieve_converged(self, q_pass, kept_idx, kept_score, kept_count, *, damping: float = 0.5,
                            ppr_iters: int = 20, ppr_tol: float = 1.5e-6, ppr_max_iters: int = 400,
@@ -1304,8 +1433,15 @@ class HippoRAGEngine:
                                  want_all_scores: bool = False, **kw) -> "PendingRetrieve":
         """Enqueue the batch and the copy of its flag words to (pinned) host memory; nothing waits.  .finish() waits for
         the flags -- not for whatever was enqueued behind them -- and does the host half of the contract."""
-        self._check_mmr_fits(mmr_plan(kw.get("mmr_lambda"), kw.get("mmr_candidates"), kw.get("k", 200)))   # before any work
+        mmr = mmr_plan(kw.get("mmr_lambda"), kw.get("mmr_candidates"), kw.get("k", 200))
+        self._check_mmr_fits(mmr)   # before any work
         q = self._q(q_pass)
+        # late: every run rescores its own rows by its own late queries (LateQueries.select)
+        late = kw.pop("late", None)
+        lp = late_plan(late, kw.get("late_candidates"), kw.get("k", 200))
+        self._check_late_fits(lp, mmr, kw.get("group_agg"), kw.get("group_hits"))
+        if lp is not None:
+            check_late(late, kw.get("k", 200), lp[1], q.shape[0])
         kept_idx, kept_score, kept_count = (t.to(self.device) for t in (kept_idx, kept_score, kept_count))
         doc_filter = kw.pop("doc_filter", None)
         check_filter_scope(kw.get("filter_scope", "ranking"), doc_filter)   # (filter_scope travels in kw to every run)
@@ -1326,6 +1462,8 @@ class HippoRAGEngine:
                 kw["doc_filter"] = fw if fld == 0 else fw[sel]
             if prog is not None:
                 kw["boost"] = prog if rows is None else prog.select(rows.cpu().numpy())
+            if late is not None:
+                kw["late"] = late if rows is None else late.select(rows.cpu().numpy())
             if blended is not None:
                 o = self.retrieve_scored(blended[sel], kept_idx[sel], kept_score[sel], kept_count[sel], damping=damping,
                                          ppr_iters=iters, ppr_tol=ppr_tol, ppr_max_iters=max(max_iters, iters),
@@ -1351,7 +1489,8 @@ class HippoRAGEngine:
     def dense_retrieve(self, q_pass, k: int = 200, doc_filter=None, filter_scope: str = "ranking",
                        group_agg: Optional[str] = None, group_hits: Optional[int] = None,
                        mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None,
-                       lexical=None, lexical_weight: float = 0.5, boost=None):
+                       lexical=None, lexical_weight: float = 0.5, boost=None, late=None,
+                       late_candidates: Optional[int] = None):
         """DPR top-k; filter_scope="seeds": normalised over the allowed passages (hrag_dense_retrieve_scoped).
         group_agg="max" | "sum": (group ids, group scores, best passage of each group) over the normalised scores
         (hrag_dense_retrieve_grouped); group_hits=m adds two entries, (hit_idx, hit_score) [B, k, m] over those scores.
@@ -1362,10 +1501,13 @@ class HippoRAGEngine:
         boost= (as on retrieve): (idx, score) of the boosted min-max scores -- hrag_sim_scores, hrag_row_minmax,
         hrag_boost_rows with the row min / max, then the plain top-k (under a doc_filter of scope "ranking"); a program
         without any term is the plain call, and in a per-query program a query without terms keeps its raw scores (its
-        ranking is the plain one).  Not with group_agg, group_hits, mmr_*, lexical or filter_scope="seeds"."""
+        ranking is the plain one).  Not with group_agg, group_hits, mmr_*, lexical or filter_scope="seeds".
+        late / late_candidates: as on retrieve (the scores are then the late ones); the tuple ends with one more entry,
+        first_score [B, k].  Not with boost or lexical here."""
         if boost is not None:
             for name, v in (("group_agg", group_agg), ("group_hits", group_hits), ("mmr_lambda", mmr_lambda),
-                            ("mmr_candidates", mmr_candidates), ("lexical", lexical)):
+                            ("mmr_candidates", mmr_candidates), ("lexical", lexical), ("late", late),
+                            ("late_candidates", late_candidates)):
                 if v is not None:
                     raise ValueError(f"dense_retrieve(boost=) does not serve {name}: it ranks the boosted rows and keeps no "
                                      "score rows on the handle -- use retrieve(boost=...) or boost_rows yourself")
@@ -1382,7 +1524,7 @@ class HippoRAGEngine:
                 return self._rank_rows(rows, k, False, doc_filter)
         if lexical is not None:
             for name, v in (("group_agg", group_agg), ("group_hits", group_hits), ("mmr_lambda", mmr_lambda),
-                            ("mmr_candidates", mmr_candidates)):
+                            ("mmr_candidates", mmr_candidates), ("late", late), ("late_candidates", late_candidates)):
                 if v is not None:
                     raise ValueError(f"dense_retrieve(lexical=) does not serve {name}: it ranks the blended rows and keeps "
                                      "no score rows on the handle -- use retrieve(lexical=...) or rank lexical_scores yourself")
@@ -1393,8 +1535,9 @@ class HippoRAGEngine:
             return self._rank_rows(rows, k, True, doc_filter)
         out = self._retrieve("hrag_dense_retrieve", q_pass, None, (), k, False, doc_filter=doc_filter,
                              filter_scope=filter_scope, group_agg=group_agg, group_hits=group_hits,
-                             mmr=mmr_plan(mmr_lambda, mmr_candidates, k))
+                             mmr=mmr_plan(mmr_lambda, mmr_candidates, k), late=late_plan(late, late_candidates, k))
         extra = () if out.mmr_value is None else (out.mmr_value,)
+        extra += () if out.first_score is None else (out.first_score,)
         if out.group_idx is None:
             return (out.doc_idx, out.doc_score) + extra
         return (out.group_idx, out.doc_score, out.doc_idx) + (() if out.hit_idx is None else (out.hit_idx, out.hit_score)) + extra
@@ -1609,9 +1752,11 @@ class HippoRAGEngine:
         check(self._lib.hrag_shard_ppr_gate(self._handle, step, C.byref(o), _stream()))
         return bool(o.value)
 
-    def shard_finish(self, mn, mx, flags, k: int, want_residual: bool = False, doc_filter=None, boost=None):
+    def shard_finish(self, mn, mx, flags, k: int, want_residual: bool = False, doc_filter=None, boost=None, late=None,
+                     late_candidates=None):
         """doc_filter: the GLOBAL filter ([B, n_passages of the whole index] or packed); the shard reads its slice."""
         refuse_boost("shard_finish", {"boost": boost})
+        refuse_late("shard_finish", {"late": late, "late_candidates": late_candidates})
         torch = _torch()
         b = mn.shape[0]
         idx = self._empty((b, k), torch.int32)
@@ -1648,6 +1793,7 @@ class CapturedPipeline:
         refuse_mmr("CapturedPipeline", retrieve_kw)
         refuse_lexical("CapturedPipeline", retrieve_kw)
         refuse_boost("CapturedPipeline", retrieve_kw)
+        refuse_late("CapturedPipeline", retrieve_kw)
         self.engine, self.batch = engine, int(batch)
         dev, dt = engine.device, engine.emb_dtype
         self._qf = torch.zeros((batch, engine.dim), dtype=dt, device=dev)

@@ -206,6 +206,10 @@ class RetrievalConfig:
                                          # columns on the device; metadata dict filters are then evaluated there and may use
                                          # $gt / $gte / $lt / $lte / $exists / $not / $any (payload.compile_filters); False:
                                          # the host bitsets, equality only
+    late_candidates: Optional[int] = None   # late-interaction reranking (include/hrag.h; needs HippoRAG(token_encoder=)):
+                                         # retrieve() / retrieve_dpr() / rag_qa() rank max(this, num_to_retrieve) entries, rescore
+                                         # them by MaxSim over the token vectors and return the best by late score; None: off
+    late_dtype: str = "bf16"             # the 16-bit type of the token vectors on the device: "bf16" or "fp16"
     boost: Optional[list] = None         # boosted retrieval (include/hrag.h): the default boost of every retrieve call, one list
                                          # of items in the grammar of boost.compile_boosts over the chunk-metadata columns
                                          # (needs payload_index=True); None: no boost
@@ -417,7 +421,8 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
                           filter_scope: str = "ranking", group_agg: Optional[str] = None, group_of=None,
                           group_hits: Optional[int] = None, keep_all_scores: bool = False,
                           mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None,
-                          lexical_encode: Optional[Callable] = None, lexical_weight: float = 0.0, boost=None):
+                          lexical_encode: Optional[Callable] = None, lexical_weight: float = 0.0, boost=None,
+                          late_encode: Optional[Callable] = None, late_candidates: Optional[int] = None):
     """The body of retrieve() (HippoRAG.py:459-480), shared by the mirror class below and by
     reference_adapter.attach(): phase A on the device, the recognition-memory filter on the host (rerank_facts
     :1659-1707), phase B on the device, in batches of eng.max_batch queries.  Yields (offset of the batch, [(doc ids,
@@ -453,6 +458,11 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
     lexical_weight=; with 0 its arguments are exactly the plain ones.
     boost (include/hrag.h, boosted retrieval): a BoostProgram over all the queries (or a broadcast one); every batch's
     phase B gets boost= with its own rows of it, so every ranking output -- and all_scores -- is that of the boosted rows.
+    late_encode / late_candidates (include/hrag.h, late-interaction reranking): every batch's query strings are encoded
+    (late_encode(strings) -> a LateQueries) and phase B gets late= / late_candidates=: each batch ranks
+    max(late_candidates, want) entries, rescores them and returns the `want` best by late score -- doc scores are the late
+    scores, rows.first_score [b, want] each entry's first-stage score.  Not with group_agg or beyond max_topk; with
+    mmr_lambda MMR picks among the rescored entries (mmr_candidates is then not used).
     keep_all_scores: rows.all_scores is the device tensor of every passage's score of the batch and rows.repeated tells
     whether the contract ran rows again (retrieve_fused: the engine's own score rows are then not the batch's)."""
     import torch
@@ -477,6 +487,16 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
     # more documents than the device top-k holds (HippoRAG.py:501-507 slices any prefix of the full ranking): the
     # scores of all passages come back and are ranked here with the library's rule (score desc, larger index first)
     beyond = k_docs < want and hasattr(eng, "last_doc_scores")
+    late_c = None
+    if late_encode is not None:
+        from .late import LATE_MAX_CANDIDATES
+        if group_agg is not None:
+            raise ValueError("late_candidates does not serve group_agg: a group's score is not a passage's")
+        late_c = max(int(want if late_candidates is None else late_candidates), want)
+        late_c = min(late_c, n_passages)
+        if want > eng.max_topk or late_c > min(eng.max_topk, LATE_MAX_CANDIDATES):
+            raise ValueError(f"late_candidates={late_c} (at least num_to_retrieve={want}) exceeds what one device ranking "
+                             f"holds, min({LATE_MAX_CANDIDATES}, max_topk={eng.max_topk})")
     if k_docs < want and not beyond:
         logger.warning("num_to_retrieve=%d exceeds the engine's max_topk=%d: %d documents per query are returned "
                        "(create the engine with a larger retrieval_top_k)", num_to_retrieve, eng.max_topk, k_docs)
@@ -558,9 +578,11 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
         if group_hits is not None and not beyond:
             kw["group_hits"] = group_hits
         if mmr is not None:
-            kw.update(mmr_lambda=mmr[0], mmr_candidates=mmr[1])
+            kw.update(mmr_lambda=mmr[0], **({} if late_c is not None else {"mmr_candidates": mmr[1]}))
         if lexical_encode is not None and lexical_weight > 0:
             kw.update(lexical=lexical_encode(qs), lexical_weight=lexical_weight)
+        if late_c is not None:
+            kw.update(late=late_encode(qs), late_candidates=late_c)
         if boost is not None:
             kw["boost"] = boost.select(range(bt.lo, bt.lo + b))
         if two_halves:
@@ -573,6 +595,8 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
                 bt.copies += (host_copy_async(o.hit_idx), host_copy_async(o.hit_score))
             if mmr is not None:
                 bt.mmr_copy = host_copy_async(o.mmr_value)
+            if late_c is not None:
+                bt.first_copy = host_copy_async(o.first_score)
         else:                                       # an engine with the one-call form only (test doubles)
             bt.pending, bt.out = None, eng.retrieve_converged(*args, **kw)
         tick("ppr_time", t0)
@@ -622,6 +646,10 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
         if mmr is not None:
             copied = bt.pending is not None and not bt.pending.repeated
             rows.mmr_value = host_wait(bt.mmr_copy).copy() if copied else out.mmr_value.cpu().numpy()
+        rows.first_score = None
+        if late_c is not None:
+            copied = bt.pending is not None and not bt.pending.repeated
+            rows.first_score = host_wait(bt.first_copy).copy() if copied else out.first_score.cpu().numpy()
         if keep_all_scores:
             rows.all_scores = getattr(out, "all_scores", None)
             rows.repeated = bt.pending is None or bt.pending.repeated
@@ -657,10 +685,12 @@ _NO_GROUP = object()     # a passage without the group_by key: a group of its ow
 
 class HippoRAG:
     def __init__(self, global_config: Optional[RetrievalConfig] = None, embedding_model=None,
-                 rerank_filter: Optional[Callable] = None, qa_fn: Optional[Callable] = None):
+                 rerank_filter: Optional[Callable] = None, qa_fn: Optional[Callable] = None, token_encoder=None):
         """embedding_model: object with batch_encode(texts, instruction=..., norm=True) -> [n, D]
         (reference embedding_model/base.py); rerank_filter: callable like DSPyFilter (identity by
-        default); qa_fn(query_solutions) -> (solutions, messages, metadata) like HippoRAG.qa (:808)."""
+        default); qa_fn(query_solutions) -> (solutions, messages, metadata) like HippoRAG.qa (:808);
+        token_encoder: object with encode_tokens(texts, is_query) -> one float array [t_i, dim] per text (a ColBERT-style
+        encoder; late-interaction reranking, late_candidates=)."""
         self.global_config = global_config or RetrievalConfig()
         self.embedding_model = embedding_model
         self.rerank_filter = rerank_filter or identity_rerank_filter
@@ -687,6 +717,9 @@ class HippoRAG:
         self._arrays = None
         self.lexical_model = self.lexical_index = None     # lexical retrieval (lexical_weight > 0): built with the engine
         self.payload_index = None                          # payload filters (payload_index=True): built with the engine
+        self.token_encoder = token_encoder                 # late-interaction reranking (late_candidates=)
+        self.token_index = None                            # ... its TokenIndex, built with the engine or on first use
+        self._token_cache: Dict[str, np.ndarray] = {}      # passage key -> its token vectors [t, dim] (encoded once)
 
     # ------------------------------------------------------------------ index side
     def index_from_openie(self, docs: Sequence, chunk_triples: Sequence[Sequence[Sequence[str]]],
@@ -945,6 +978,7 @@ class HippoRAG:
                 fe = compose("facts", self.fact_node_keys, a["fact_emb"], held["facts"])
         self._drop_lexical()
         self._drop_payload()
+        self._drop_late()
         if old is not None:
             # the gathered matrices no longer depend on the old engine: free its index before the new one is built
             # (peak device memory = one index + the embedding matrices, not two indexes)
@@ -981,6 +1015,8 @@ class HippoRAG:
             self._build_lexical()
         if self.global_config.payload_index:
             self._build_payload()
+        if self.global_config.late_candidates is not None and self.token_encoder is not None:
+            self._build_late()
         self.ready_to_retrieve = True
 
     # ------------------------------------------------------------------ payload filters
@@ -1049,6 +1085,74 @@ class HippoRAG:
             for q, top in enumerate(top_of(raw[:, :fc.spec.n_bins], fc.labels, limit)):
                 out[q][name] = {"values": top, "other": int(raw[q, -2]), "missing": int(raw[q, -1]), "total": int(raw[q].sum())}
         return out
+
+    # ------------------------------------------------------------------ late-interaction reranking
+    def _drop_late(self):
+        ix = getattr(self, "token_index", None)
+        if ix is not None:
+            if getattr(getattr(self, "engine", None), "_token_index", None) is ix:
+                self.engine.set_token_index(None)
+            ix.close()
+        self.token_index = None
+
+    def _build_late(self):
+        """The token index of the passages the mirror holds: token_encoder.encode_tokens(texts, False) for the passages
+        that are not in the per-passage cache yet (keyed like the passage texts, so index() encodes the new chunks only and
+        delete() none), then a TokenIndex on the engine's device.  An engine without set_token_index (a test double) gets
+        the cache only."""
+        self._drop_late()
+        keys, texts = self.passage_node_keys, self.passage_texts
+        live = set(keys)
+        for k in [k for k in self._token_cache if k not in live]:
+            del self._token_cache[k]
+        fresh = [i for i, k in enumerate(keys) if k not in self._token_cache]
+        if fresh:
+            toks = self.token_encoder.encode_tokens([texts[i] for i in fresh], False)
+            if len(toks) != len(fresh):
+                raise ValueError(f"token_encoder.encode_tokens returned {len(toks)} arrays for {len(fresh)} passages")
+            for i, t in zip(fresh, toks):
+                self._token_cache[keys[i]] = np.asarray(t, np.float32)
+        if hasattr(self.engine, "set_token_index"):
+            from .late import TokenIndex
+            self.token_index = TokenIndex.from_ragged([self._token_cache[k] for k in keys], self.global_config.late_dtype,
+                                                      self.engine.device.index)
+            self.engine.set_token_index(self.token_index)
+
+    def _late(self, late_candidates, who: str = "retrieve") -> dict:
+        """The late arguments of a call as iter_batched_retrieve takes them: the argument, else
+        RetrievalConfig.late_candidates; {} when off.  Builds the token index on first use."""
+        c = self.global_config.late_candidates if late_candidates is None else late_candidates
+        if c is None:
+            return {}
+        if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or c < 1:
+            raise ValueError(f"late_candidates={c!r}: an int >= 1 expected")
+        if self.token_encoder is None:
+            raise ValueError(f"{who}(late_candidates={c}) needs HippoRAG(token_encoder=...): an object with "
+                             "encode_tokens(texts, is_query)")
+        if getattr(self, "token_index", None) is None:     # (a test double's engine: the cache alone, nothing is re-encoded)
+            self._build_late()
+        dtype = self.global_config.late_dtype
+        device = getattr(self.engine, "device", None)
+
+        def encode(strings):
+            from .late import LateQueries
+            return LateQueries.from_ragged(self.token_encoder.encode_tokens(list(strings), True), dtype, device)
+        return {"late_encode": encode, "late_candidates": int(c)}
+
+    def _refuse_late(self, who: str, late_candidates=None) -> None:
+        c = self.global_config.late_candidates if late_candidates is None else late_candidates
+        if c is not None:
+            raise ValueError(f"{who} does not serve late_candidates={c}: late reranking rescores one plain ranking per query "
+                             "-- use retrieve(late_candidates=...)")
+
+    @staticmethod
+    def _late_metadata(solutions, first) -> None:
+        """"late_score" and "first_score" into the metadata of every returned entry of a late call."""
+        if first is None:
+            return
+        for s, f in zip(solutions, first):
+            for d, x, y in zip(s.doc_metadata, s.doc_scores, f):
+                d["late_score"], d["first_score"] = float(x), float(y)
 
     # ------------------------------------------------------------------ lexical retrieval
     def _drop_lexical(self):
@@ -1446,8 +1550,13 @@ class HippoRAG:
                  gold_docs: Optional[List[List[str]]] = None, doc_filter=None, filter_scope: Optional[str] = None,
                  group_by=None, group_agg: Optional[str] = None, group_hits: Optional[int] = None,
                  mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None,
-                 lexical_weight: Optional[float] = None, boost=None):
-        """boost (default RetrievalConfig.boost; include/hrag.h, boosted retrieval; needs payload_index=True): one list of
+                 lexical_weight: Optional[float] = None, boost=None, late_candidates: Optional[int] = None):
+        """late_candidates (default RetrievalConfig.late_candidates; include/hrag.h, late-interaction reranking; needs
+        token_encoder=): every query ranks max(late_candidates, num_to_retrieve) entries as below, the token vectors of the
+        query string are scored against theirs by MaxSim on the device and the docs come in late order: doc_scores are the
+        late scores and every entry's metadata carries "late_score" and "first_score".  Not with group_by or more documents
+        than the engine's max_topk.
+        boost (default RetrievalConfig.boost; include/hrag.h, boosted retrieval; needs payload_index=True): one list of
         boost items (boost.compile_boosts) for every query, or one list per query, or a BoostProgram: the scores become
         s * M + A over the chunk-metadata columns before they are ranked -- a recency decay, a trusted source, a penalty --
         and everything below ranks the boosted scores; every entry's metadata then carries "boosted": True.
@@ -1484,9 +1593,12 @@ class HippoRAG:
         mmr = self._mmr(mmr_lambda, mmr_candidates)
         lex = self._lexical(lexical_weight)
         prog = self._boost(boost, len(queries))
+        late = self._late(late_candidates)
+        if late and agg is not None:
+            raise ValueError("retrieve does not serve late_candidates with group_by: a group's score is not a passage's")
         self.get_query_embeddings(queries)
         results: List[QuerySolution] = []
-        self._retrieve_into(results, queries, num_to_retrieve, words, scope, agg, table, hits, mmr, lex, prog)
+        self._retrieve_into(results, queries, num_to_retrieve, words, scope, agg, table, hits, mmr, lex, prog, late)
         self.all_retrieval_time += time.time() - t_start
         logger.info("Total Retrieval Time %.2fs", self.all_retrieval_time)
         logger.info("Total Recognition Memory Time %.2fs", self.rerank_time)
@@ -1496,11 +1608,12 @@ class HippoRAG:
         return results
 
     def _retrieve_into(self, results, queries, num_to_retrieve, doc_filter=None, filter_scope: str = "ranking",
-                       group_agg=None, table=None, group_hits=None, mmr=None, lex=None, boost=None):
+                       group_agg=None, table=None, group_hits=None, mmr=None, lex=None, boost=None, late=None):
         cfg = self.global_config
         extra = {} if doc_filter is None else {"doc_filter": doc_filter, "filter_scope": filter_scope}
         extra.update(mmr or {})
         extra.update(lex or {})
+        extra.update(late or {})
         if boost is not None:
             extra["boost"] = boost
         if group_agg is not None:
@@ -1524,6 +1637,7 @@ class HippoRAG:
                 self._mmr_metadata(sols, getattr(rows, "mmr_value", None))
                 self._lexical_metadata(sols, lex)
                 self._boost_metadata(sols, boost)
+                self._late_metadata(sols, getattr(rows, "first_score", None))
                 results.extend(sols)
 
     # ------------------------------------------------------------------ fused retrieval
@@ -1531,7 +1645,7 @@ class HippoRAG:
                        rrf_depth: Optional[int] = None, num_to_retrieve: Optional[int] = None, doc_filter=None,
                        filter_scope: Optional[str] = None, group_by=None, group_agg: Optional[str] = None,
                        group_hits: Optional[int] = None, mmr_lambda: Optional[float] = None,
-                       mmr_candidates: Optional[int] = None, boost=None):
+                       mmr_candidates: Optional[int] = None, boost=None, late_candidates: Optional[int] = None):
         """One ranked list per QUESTION, each question given as several sub-queries -- a decomposition, paraphrases, the
         thoughts of an IRCoT chain (include/hrag.h, fused retrieval).  Every sub-query runs phase A and phase B as in
         retrieve(); the score rows of a question's sub-queries are fused ON THE DEVICE over all passages -- fuse="sum"
@@ -1543,6 +1657,7 @@ class HippoRAG:
         sub-queries share one device batch: at most max_batch of them."""
         from .engine import check_fuse
         self._refuse_mmr("retrieve_fused", mmr_lambda, mmr_candidates)
+        self._refuse_late("retrieve_fused", late_candidates)
         self._refuse_lexical("retrieve_fused")
         if boost is not None or self.global_config.boost is not None:
             raise ValueError("retrieve_fused does not serve boost: it fuses the score rows of plain member calls -- use "
@@ -1655,7 +1770,8 @@ class HippoRAG:
                        gold_docs: Optional[List[List[str]]] = None, reason_fn: Optional[Callable] = None,
                        doc_filter=None, filter_scope: Optional[str] = None, group_by=None,
                        group_agg: Optional[str] = None, mmr_lambda: Optional[float] = None,
-                       mmr_candidates: Optional[int] = None, lexical_weight: Optional[float] = None, boost=None):
+                       mmr_candidates: Optional[int] = None, lexical_weight: Optional[float] = None, boost=None,
+                       late_candidates: Optional[int] = None):
         """Iterative retrieval: alternate retrieval and one reasoning step per query, merging the document
         scores by max (:526-543).  reason_fn(query, ranked_docs, thoughts) -> str stands for
         utils/qa_utils.reason_step (the IRCoT prompt + reader LLM are outside this package).  The reference
@@ -1665,6 +1781,7 @@ class HippoRAG:
         RetrievalConfig.lexical_weight): every step's retrieve() takes it, the thoughts being the query strings.  boost
         (default RetrievalConfig.boost): every step's retrieve() takes it, a per-query one cut to the step's queries."""
         self._refuse_mmr("retrieve_ircot", mmr_lambda, mmr_candidates)
+        self._refuse_late("retrieve_ircot", late_candidates)
         if max_qa_steps < 1:
             raise ValueError("max_qa_steps must be at least 1.")
         if max_qa_steps > 1 and reason_fn is None:
@@ -1761,8 +1878,10 @@ class HippoRAG:
                      gold_docs: Optional[List[List[str]]] = None, doc_filter=None, filter_scope: Optional[str] = None,
                      group_by=None, group_agg: Optional[str] = None, group_hits: Optional[int] = None,
                      mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None,
-                     lexical_weight: Optional[float] = None, boost=None):
-        """Dense retrieval; doc_filter / filter_scope as in retrieve() ("seeds": the scores are normalised over the
+                     lexical_weight: Optional[float] = None, boost=None, late_candidates: Optional[int] = None):
+        """late_candidates: as in retrieve(), over the dense ranking; then not with group_by, lexical_weight, boost or more
+        documents than the engine's max_topk (ValueError naming late_candidates).
+        Dense retrieval; doc_filter / filter_scope as in retrieve() ("seeds": the scores are normalised over the
         allowed passages); group_by / group_agg / group_hits as in retrieve(), over the normalised dense scores;
         mmr_lambda / mmr_candidates as in retrieve(), over the dense ranking.
         lexical_weight (default RetrievalConfig.lexical_weight) above 0: the ranking of the dense scores blended with the
@@ -1818,6 +1937,18 @@ class HippoRAG:
                     raise ValueError(f"retrieve_dpr does not serve boost with {name}: the boosted rows are ranked once on the "
                                      "device -- use retrieve(boost=...)")
 
+        late = self._late(late_candidates, "retrieve_dpr")
+        if late:
+            from .late import LATE_MAX_CANDIDATES
+            late_c = min(max(late["late_candidates"], want), len(self.passage_node_keys))
+            for name, on in (("group_by", agg is not None), ("lexical_weight", bool(lex)), ("boost", prog is not None),
+                             (f"num_to_retrieve above max_topk={eng.max_topk}", beyond),
+                             (f"more than min({LATE_MAX_CANDIDATES}, max_topk={eng.max_topk}) candidates",
+                              late_c > min(eng.max_topk, LATE_MAX_CANDIDATES))):
+                if on:
+                    raise ValueError(f"retrieve_dpr does not serve late_candidates={late_c} with {name}: late reranking "
+                                     "rescores one plain device ranking of passages")
+
         def rows_of(lo, b):                 # the packed filter rows of queries [lo, lo + b)
             return words if words.ndim == 1 else words[lo: lo + b]
 
@@ -1837,6 +1968,11 @@ class HippoRAG:
                 extra.update(lexical=lex["lexical_encode"](qs), lexical_weight=lex["lexical_weight"])
             if prog is not None:
                 extra["boost"] = prog.select(range(lo, lo + len(qs)))
+            if late:                        # (MMR then picks among the rescored entries: no mmr_candidates)
+                extra.update(late=late["late_encode"](qs), late_candidates=late_c)
+                idx, sc, *h = eng.dense_retrieve(self._q_tensor(qs, "passage"), k=k_docs, **extra,
+                                                 **({"mmr_lambda": mmr["mmr_lambda"]} if mmr else {}))
+                return (qs, host_copy_async(idx), host_copy_async(sc), None) + tuple(map(host_copy_async, h))
             idx, sc, *h = eng.dense_retrieve(self._q_tensor(qs, "passage"), k=k_docs, **extra, **mmr)
             return (qs, host_copy_async(idx), host_copy_async(sc)) + ((None,) + tuple(map(host_copy_async, h)) if h else ())
 
@@ -1846,7 +1982,7 @@ class HippoRAG:
         for n in range(len(starts)):
             qs, idx_h, sc_h, *gi_h = pending
             pending = enqueue(starts[n + 1]) if n + 1 < len(starts) else None
-            gi = h_idx = h_sc = values = None
+            gi = h_idx = h_sc = values = first_sc = None
             if beyond:
                 raw = host_wait(idx_h)[:, :len(self.passage_node_keys)]
                 if scope == "seeds":
@@ -1866,7 +2002,10 @@ class HippoRAG:
                     sc = np.take_along_axis(full, idx.astype(np.int64), axis=1)
             else:
                 idx, sc = host_wait(idx_h).copy(), host_wait(sc_h).copy()
-                if mmr:                     # dense_retrieve's tuple ends with mmr_value
+                if late:                    # dense_retrieve's tuple ends with first_score
+                    first_sc = host_wait(gi_h[-1]).copy()
+                    gi_h = gi_h[:-1]
+                if mmr:                     # ... and, before it, with mmr_value
                     values = host_wait(gi_h[-1]).copy()
                     gi_h = gi_h[:-1]
                 gi = host_wait(gi_h[0]).copy() if gi_h and gi_h[0] is not None else None
@@ -1888,6 +2027,7 @@ class HippoRAG:
             self._mmr_metadata(results[first:], values)
             self._lexical_metadata(results[first:], lex)
             self._boost_metadata(results[first:], prog)
+            self._late_metadata(results[first:], first_sc)
         if gold_docs is not None:
             return results, self._recall(gold_docs, [r.docs for r in results])
         return results
@@ -1895,13 +2035,13 @@ class HippoRAG:
     # ------------------------------------------------------------------ rag_qa :591-663
     def rag_qa(self, queries, gold_docs: Optional[List[List[str]]] = None,
                gold_answers: Optional[List[List[str]]] = None, doc_filter=None, filter_scope: Optional[str] = None,
-               lexical_weight: Optional[float] = None, boost=None):
+               lexical_weight: Optional[float] = None, boost=None, late_candidates: Optional[int] = None):
         if self.qa_fn is None:
             raise NotImplementedError("rag_qa needs a qa_fn (the reader LLM is outside this package)")
         retrieval_metrics = None
         if not isinstance(queries[0], QuerySolution):
             out = self.retrieve(queries=queries, gold_docs=gold_docs, doc_filter=doc_filter, filter_scope=filter_scope,
-                                lexical_weight=lexical_weight, boost=boost)
+                                lexical_weight=lexical_weight, boost=boost, late_candidates=late_candidates)
             queries, retrieval_metrics = out if gold_docs is not None else (out, None)
         solutions, messages, metadata = self.qa_fn(queries)
         if gold_answers is not None:

@@ -77,7 +77,9 @@ extern "C" {
  *        hrag_payload_filter, hrag_bitset_count_rows;
  *        later in 0.8 (detect by the symbol): boosted retrieval -- hrag_boost_rows, hrag_last_boosted;
  *        later in 0.8 (detect by the symbol): facets -- hrag_payload_facet, hrag_payload_facet_ids,
- *        hrag_payload_facet_ws_bytes. */
+ *        hrag_payload_facet_ws_bytes;
+ *        later in 0.8 (detect by the symbol): late-interaction reranking -- hrag_late_create, hrag_late_destroy,
+ *        hrag_late_scores, hrag_late_rank_rows, hrag_late_workspace_bytes, hrag_late_rerank. */
 #define HRAG_VERSION_MAJOR 0
 #define HRAG_VERSION_MINOR 8
 
@@ -825,6 +827,79 @@ hrag_status hrag_mmr_sel(hrag_engine *e, const int32_t *cand_idx_dev, const floa
                          int32_t k, float lambda, int32_t normalize, int32_t *sel_out_dev, int32_t *idx_out_dev,
                          float *score_out_dev, float *value_out_dev, void *workspace_dev, size_t workspace_bytes,
                          hrag_stream stream);
+
+/* ---- late-interaction reranking: MaxSim over per-token embeddings of the candidates a ranking returned ----
+ * A passage embedding is one vector, the mean of what the passage says; the rankings above order the candidates by that
+ * one vector whatever the individual query tokens match.  Late interaction (ColBERT's MaxSim; the multivector max_sim /
+ * rank_vectors of search engines) scores a candidate by its best-matching token for every query token.  ("rerank" names
+ * the reference's LLM fact filter in this project: the option is called LATE everywhere.)
+ *
+ * A TOKEN INDEX holds, for n passages,
+ *   tok_ptr   int64 [n + 1], ascending, tok_ptr[0] = 0; passage p owns the token rows tok_ptr[p] .. tok_ptr[p + 1] - 1
+ *             (an empty range is allowed);
+ *   tok_emb   16-bit [T, dim] on the device, T = tok_ptr[n]: HRAG_BF16 or HRAG_FP16 by the dtype code, as in
+ *             hrag_sim_gemm; dim a multiple of 8 with 8 <= dim <= HRAG_LATE_MAX_DIM; the base pointer 16-byte aligned.
+ * It is an object of its own, like hrag_lex and hrag_payload: its vectors are NOT the engine's passage embeddings, and
+ * there is no split-fp32 form.
+ * A BATCH OF LATE QUERIES is q_ptr int32 [batch + 1] (ascending from 0) and q_tok 16-bit [q_ptr[batch], dim] on the
+ * device in the index's dtype, 16-byte aligned; at most HRAG_LATE_MAX_QUERY_TOKENS tokens per query.
+ *
+ * For query b and candidate slot s holding passage p = cand_idx[b][s]:
+ *   s_ij   = the fp32 dot product of query token i and passage token j: the products are exact, the fp32 accumulation
+ *            runs on v_mfma_f32_16x16x32_{bf16,f16}, the k tail zero-filled in 8-element chunks;
+ *   m_i    = fmaxf over j in [tok_ptr[p], tok_ptr[p + 1]) of s_ij, starting from -inf (np.fmax: a NaN s_ij is ignored);
+ *   score  = (float)(sum over i, in ascending order, of (double)m_i) + 0.0f: one rounding, -0 becomes +0; a NaN is the
+ *            quiet NaN 0x7fc00000.
+ * A passage without tokens scores -inf when the query has tokens; a query without tokens scores +0.0 everywhere.  An
+ * EMPTY slot (id < 0 or id >= n) has no score: it reads 0.0 in the scores output and never ranks.  Rows beyond a
+ * passage's last token and columns beyond a query's last token are masked, not zero-filled, and no load reaches past
+ * tok_ptr[p + 1].
+ * RANKING: the live slots ordered by the ranking key of this header (every NaN above +inf, -0 ties +0), a tie to the
+ * SMALLER slot -- the earlier first-stage rank, the tie rule of hrag_mmr; the first k as (sel, idx, score), score
+ * canonical, and -1 / -1 / 0 once the live slots run out.  1 <= k <= c <= HRAG_LATE_MAX_CANDIDATES.
+ * No atomics, every output written exactly once: the score of a (query, passage) pair has the same bits at any batch,
+ * in any slot, next to any neighbours (csrc/late.hip). */
+#define HRAG_LATE_MAX_DIM 256
+#define HRAG_LATE_MAX_QUERY_TOKENS 64
+#define HRAG_LATE_MAX_CANDIDATES 1024
+
+typedef struct hrag_late hrag_late; /* opaque; independent of any engine: engines and workspaces over the same passages share one */
+
+/* The index over tok_ptr (HOST, validated here, copied to the current device) and tok_emb_dev (DEVICE, kept by
+ * reference: it must outlive the index; nothing of it is copied).  HRAG_EINVAL, and nothing is allocated: tok_ptr[0] != 0
+ * or tok_ptr descending, dim not a multiple of 8 or outside [8, HRAG_LATE_MAX_DIM], a dtype other than HRAG_BF16 /
+ * HRAG_FP16, a misaligned or missing tok_emb_dev, n_passages outside [1, 2^31). */
+hrag_status hrag_late_create(int64_t n_passages, const int64_t *tok_ptr, const uint16_t *tok_emb_dev, int32_t dim,
+                             int32_t dtype, hrag_late **out);
+hrag_status hrag_late_destroy(hrag_late *ix);
+
+/* The scores above: out_dev fp32 [batch, ld], ld >= c, the columns c .. ld not touched; cand_idx_dev int32 [batch, c].
+ * q_ptr is read on the HOST (the rules are checked before anything is enqueued: HRAG_EINVAL for q_ptr[0] != 0, a
+ * descending q_ptr, a query of more than HRAG_LATE_MAX_QUERY_TOKENS tokens, c outside [1, HRAG_LATE_MAX_CANDIDATES],
+ * ld < c, a NULL or misaligned pointer) and q_ptr_dev is the same array on the device, which the kernel reads (were it to
+ * differ, its ranges are clamped to q_tok's q_ptr[batch] rows and the cap).  Enqueues on `stream`; nothing is allocated,
+ * synchronised or read back.  Any number of calls may read one index at the same time. */
+hrag_status hrag_late_scores(const hrag_late *ix, const int32_t *q_ptr, const int32_t *q_ptr_dev, const uint16_t *q_tok_dev,
+                             int32_t batch, const int32_t *cand_idx_dev, int32_t c, float *out_dev, int64_t ld,
+                             hrag_stream stream);
+
+/* The ranking above over any score rows scores_dev fp32 [batch, ld] of candidates cand_idx_dev int32 [batch, c],
+ * engine-free: outputs [batch, k]; sel_out_dev may be NULL.  n_ids > 0: an id >= n_ids is an empty slot too; n_ids <= 0:
+ * a negative id only.  HRAG_EINVAL: c or k out of range, ld < c, a NULL pointer. */
+hrag_status hrag_late_rank_rows(const float *scores_dev, int64_t ld, const int32_t *cand_idx_dev, int64_t n_ids,
+                                int32_t batch, int32_t c, int32_t k, int32_t *sel_out_dev, int32_t *idx_out_dev,
+                                float *score_out_dev, hrag_stream stream);
+
+/* Bytes of workspace hrag_late_rerank needs (16-byte aligned device memory, scratch only): the [batch, round_up(c, 4)]
+ * fp32 scores.  Negative on a bad argument. */
+int64_t hrag_late_workspace_bytes(int32_t batch, int32_t c);
+
+/* The two steps: bit-identical to hrag_late_scores (ld = round_up(c, 4)) followed by hrag_late_rank_rows with
+ * n_ids = n_passages on the same buffers; afterwards the workspace holds the scores of every slot. */
+hrag_status hrag_late_rerank(const hrag_late *ix, const int32_t *q_ptr, const int32_t *q_ptr_dev, const uint16_t *q_tok_dev,
+                             int32_t batch, const int32_t *cand_idx_dev, int32_t c, int32_t k, int32_t *sel_out_dev,
+                             int32_t *idx_out_dev, float *score_out_dev, void *workspace_dev, size_t workspace_bytes,
+                             hrag_stream stream);
 
 /* ---- lexical retrieval: sparse-vector (BM25, learned term weights) scores blended into the dense scores ----
  * Every score above starts from the cosine of dense embeddings, which smears the rare surface forms a multi-hop question
