@@ -29,6 +29,9 @@ FACET_MAX_BINS, FACET_WINDOW = 1 << 20, 4096
 FACET_CODES, FACET_EDGES = 0, 1
 # HRAG_LATE_* (late-interaction reranking): the caps on dim, on the tokens of one query and on the candidates of one row
 LATE_MAX_DIM, LATE_MAX_QUERY_TOKENS, LATE_MAX_CANDIDATES = 256, 64, 1024
+# HRAG_RECO_* (recommend by example): the cap on one query's examples, the fused kernel's passage tile, the strategies
+RECO_MAX_EXAMPLES, RECO_TILE = 32, 128
+RECO_BEST_SCORE, RECO_SUM_SCORES, RECO_AVERAGE_VECTOR = 0, 1, 2
 HRAG_VERSION = 8      # HRAG_VERSION_MAJOR * 1000 + HRAG_VERSION_MINOR of include/hrag.h
 FLAG_DPR_FALLBACK, FLAG_ZERO_MASS, FLAG_ZERO_PHRASE, FLAG_FP8_SATURATED, FLAG_NOT_CONVERGED = 1, 2, 4, 8, 16
 # the convergence contract's error bound (include/hrag.h): error <= max(PPR_ERR_K * residual, floor of the state type);
@@ -198,6 +201,12 @@ SIGNATURES = {
     "hrag_late_rank_rows": (C.c_int, [_P, _I64, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _P]),
     "hrag_late_workspace_bytes": (C.c_int64, [_I32, _I32]),
     "hrag_late_rerank": (C.c_int, [_P, _P, _P, _P, _I32, _P, _I32, _I32, _P, _P, _P, _P, C.c_size_t, _P]),
+    "hrag_reco_rows": (C.c_int, [_P, _I64, _P, _P, _I32, _I64, _I32, _P, _I64, _P]),
+    "hrag_reco_workspace_bytes": (C.c_int64, [_I32]),
+    "hrag_reco_scores_rows": (C.c_int, [_P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _I32, _I32, _P, _I64, _P, C.c_size_t, _P]),
+    "hrag_reco_scores": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _P, _I64, _P, C.c_size_t, _P]),
+    "hrag_reco_query": (C.c_int, [_P, _P, _P, _P, _P, _I32, _P, _P, _P, _P]),
+    "hrag_reco_exclude": (C.c_int, [_P, _I64, _I64, _P, _P, _P, _I32, _P]),
     "hrag_ppr_sweeps": (C.c_int, [_P, _I32, _I32, _F32, _I32, _P]),
     "hrag_ppr_layout": (C.c_int, [_P, _I32, C.POINTER(_I32), C.POINTER(_I32)]),
     "hrag_row_minmax": (C.c_int, [_P, _I32, _I64, _I64, _P, _P, _P]),

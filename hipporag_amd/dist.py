@@ -434,7 +434,8 @@ class ShardedRetriever:
                  passage_node_weight=0.05, ppr_iters=20, k=200, ppr_tol=0.0, ppr_max_iters=0,
                  check_saturation=True, doc_filter=None, filter_scope: str = "ranking", group_agg=None,
                  group_hits=None, fuse=None, mmr_lambda=None, mmr_candidates=None,
-                 lexical=None, lexical_weight=None, boost=None, late=None, late_candidates=None):
+                 lexical=None, lexical_weight=None, boost=None, late=None, late_candidates=None, feedback=None,
+                 recommend=None):
         """Returns (doc ids, doc scores, flags) -- and with ppr_tol > 0 additionally (residual, sweeps used): the
         convergence contract of hrag_retrieve on the shards.  Every shard measures the relative update of ITS
         passages; the measures are all-reduced (MAX) before every decision, so all shards run the same steps.
@@ -448,11 +449,13 @@ class ShardedRetriever:
         (= HippoRAGEngine.retrieve(filter_scope="seeds"); the kept facts from score_facts(scope_filter=))."""
         from .engine import refuse_boost, refuse_group_agg, refuse_lexical, refuse_mmr
         from .late import refuse_late
+        from .reco import refuse_reco
         refuse_group_agg("ShardedRetriever", {"group_agg": group_agg, "group_hits": group_hits, "fuse": fuse})
         refuse_mmr("ShardedRetriever", {"mmr_lambda": mmr_lambda, "mmr_candidates": mmr_candidates})
         refuse_lexical("ShardedRetriever", {"lexical": lexical, "lexical_weight": lexical_weight})
         refuse_boost("ShardedRetriever", {"boost": boost})
         refuse_late("ShardedRetriever", {"late": late, "late_candidates": late_candidates})
+        refuse_reco("ShardedRetriever", {"feedback": feedback, "recommend": recommend})
         scoped = serve_seeds_scope(getattr(self, "st", None), filter_scope)
         if scoped:
             from .engine import check_filter_scope
@@ -639,16 +642,19 @@ class NativeShardedRetriever:
     def retrieve(self, q_pass, kept_idx, kept_score, kept_count, *, link_top_k=5, damping=0.5, passage_node_weight=0.05,
                  ppr_iters=20, k=200, ppr_tol=0.0, ppr_max_iters=0, check_saturation=True, doc_filter=None,
                  filter_scope: str = "ranking", group_agg=None, group_hits=None, fuse=None, mmr_lambda=None, mmr_candidates=None,
-                 lexical=None, lexical_weight=None, boost=None, late=None, late_candidates=None):
+                 lexical=None, lexical_weight=None, boost=None, late=None, late_candidates=None, feedback=None,
+                 recommend=None):
         """Same contract as ShardedRetriever.retrieve: (doc ids, doc scores, flags[, residual, sweeps used]);
         doc_filter: hrag_shard_retrieve_filtered with the global filter (filter_scope="seeds": hrag_shard_retrieve_scoped)."""
         from .engine import refuse_boost, refuse_group_agg, refuse_lexical, refuse_mmr
         from .late import refuse_late
+        from .reco import refuse_reco
         refuse_group_agg("NativeShardedRetriever", {"group_agg": group_agg, "group_hits": group_hits, "fuse": fuse})
         refuse_mmr("NativeShardedRetriever", {"mmr_lambda": mmr_lambda, "mmr_candidates": mmr_candidates})
         refuse_lexical("NativeShardedRetriever", {"lexical": lexical, "lexical_weight": lexical_weight})
         refuse_boost("NativeShardedRetriever", {"boost": boost})
         refuse_late("NativeShardedRetriever", {"late": late, "late_candidates": late_candidates})
+        refuse_reco("NativeShardedRetriever", {"feedback": feedback, "recommend": recommend})
         scoped = serve_seeds_scope(getattr(self, "st", None), filter_scope)
         if scoped:
             from .engine import check_filter_scope
@@ -737,11 +743,13 @@ class HybridRetriever:
         passages of the all-to-all'd score rows); needs the fact sources on the embedding shard, like score_facts."""
         from .engine import refuse_boost, refuse_group_agg, refuse_lexical, refuse_mmr
         from .late import refuse_late
+        from .reco import refuse_reco
         refuse_group_agg("HybridRetriever", kw)
         refuse_mmr("HybridRetriever", kw)
         refuse_lexical("HybridRetriever", kw)
         refuse_boost("HybridRetriever", kw)
         refuse_late("HybridRetriever", kw)
+        refuse_reco("HybridRetriever", kw)
         kw.pop("boost", None)
         kw.pop("lexical", None)
         kw.pop("lexical_weight", None)

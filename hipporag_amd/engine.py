@@ -25,6 +25,8 @@ from .boost import boost_rows as _boost_rows
 from .facet import FacetCounts, FacetSpec, compile_facet              # noqa: F401  (re-exported: facets)
 from .late import (LATE_DTYPES, LateQueries, TokenIndex, check_late, late_plan,      # noqa: F401  (re-exported: late-interaction
                    refuse_late)                                                    # reranking)
+from .reco import (Examples, check_examples, check_feedback_weight, check_strategy,  # noqa: F401  (re-exported: recommend by
+                   refuse_reco)                                                      # example)
 
 
 def _torch():
@@ -723,6 +725,7 @@ class HippoRAGEngine:
         w._workspaces = []
         w._parent = root
         w._fuse_ws = w._fuse_host = w._mmr_ws = w._late_ws = None      # last_fused / mmr / late: scratch buffers of its own
+        w._reco_ws = None                                    # ... and recommend's column table
         w._pay_words = None                                  # ... and the words of a PayloadFilter doc filter
         with _torch().cuda.device(root.device):
             check(root._lib.hrag_workspace_create(root._handle, C.byref(w._handle)))
@@ -837,7 +840,8 @@ class HippoRAGEngine:
                  group_agg: Optional[str] = None, group_hits: Optional[int] = None,
                  mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None,
                  lexical=None, lexical_weight: float = 0.5, boost=None, late=None,
-                 late_candidates: Optional[int] = None) -> RetrieveOutput:
+                 late_candidates: Optional[int] = None, feedback=None, feedback_weight: float = 0.3,
+                 feedback_strategy: str = "best_score") -> RetrieveOutput:
         """Phase B: seeds + passage prior + PPR + ranking (DPR ranking where kept_count == 0).
         ppr_tol / ppr_max_iters: the convergence contract of include/hrag.h (0 = exactly ppr_iters sweeps);
         the output carries the per-query residual and the sweeps that ran.
@@ -870,8 +874,30 @@ class HippoRAGEngine:
         and the k best by late score are returned: doc_score carries the late scores, first_score each entry's first-stage
         score, a tie goes to the earlier first-stage rank.  With mmr_lambda, MMR picks its k among the c rescored entries
         with the late scores as relevance (mmr_candidates is then refused: the candidates are the late ones).  Not with
-        group_agg / group_hits: a group's score is not a passage's.  None: the call is exactly the plain one."""
+        group_agg / group_hits: a group's score is not a passage's.  None: the call is exactly the plain one.
+        feedback= an Examples (include/hrag.h, recommend by example): relevance feedback into the passage prior -- the
+        passage scores are the dense ones (hrag_sim_scores) blended with the recommend rows of these examples
+        (hrag_reco_scores, feedback_strategy "best_score" | "sum_scores") at feedback_weight in [0, 1]: hrag_row_minmax of
+        each, hrag_lex_blend_rows, then hrag_retrieve_scored* -- the path lexical= takes, so everything behind it composes.
+        The examples are NOT excluded: the caller's doc_filter decides.  Not with lexical (both own the blend);
+        feedback_weight=0 leaves the call bit-identical to the plain one.  None: the call is exactly the plain one."""
         lp = late_plan(late, late_candidates, k)
+        if feedback is not None:
+            if lexical is not None:
+                raise ValueError("feedback together with lexical: both own the blend of the passage scores -- blend the "
+                                 "rows yourself (lexical_scores, recommend_scores) and call retrieve_scored")
+            check_examples(feedback, None, "feedback")
+            check_strategy(feedback_strategy, True, "feedback_strategy")
+            if check_feedback_weight(feedback_weight) != 0.0:
+                mmr = mmr_plan(mmr_lambda, mmr_candidates, k)     # (refused before the blend is enqueued)
+                self._check_mmr_fits(mmr)
+                self._check_late_fits(lp, mmr, group_agg, group_hits)
+                rows = self._feedback_blend(q_pass, feedback, feedback_weight, feedback_strategy, filter_scope, doc_filter)
+                return self._retrieve("hrag_retrieve_scored", rows, (kept_idx, kept_score, kept_count),
+                                      (link_top_k, damping, passage_node_weight, ppr_iters, max(ppr_max_iters, ppr_iters),
+                                       ppr_tol),
+                                      k, want_residual or ppr_tol > 0, doc_filter=doc_filter, filter_scope=filter_scope,
+                                      group_agg=group_agg, group_hits=group_hits, mmr=mmr, boost=boost, late=lp)
         if lexical is not None:
             mmr = mmr_plan(mmr_lambda, mmr_candidates, k)     # (refused before the blend is enqueued)
             self._check_mmr_fits(mmr)
@@ -1168,6 +1194,138 @@ class HippoRAGEngine:
         rows, _, _ = self._lex_rows(qp, qt, qw)
         return self._rank_rows(rows, k, False, doc_filter)
 
+    # ------------------------------------------------------------------ recommend by example
+    def _reco_args(self, examples, name: str = "examples"):
+        """The checked examples of a call as the library takes them: (host ex_ptr, ex_ptr_dev, ex_idx, ex_sign, batch)."""
+        ex = check_examples(examples, None, name)
+        if ex.device != self.device:
+            raise ValueError(f"{name}: the examples live on {ex.device}, the engine on {self.device}")
+        if self.n_rows != self.num_vertices or self.passage_rows != self.n_passages:
+            raise NotImplementedError("recommend on a row-shard engine: it holds a slice of the passage embeddings (recommend "
+                                      "is served by the unsharded engine only)")
+        if ex.batch > self.max_batch:
+            raise ValueError(f"{name}: {ex.batch} queries, the engine serves at most max_batch={self.max_batch}")
+        return (ex.ex_ptr.ctypes.data, ex.ex_ptr_dev.data_ptr(), ex.ex_idx.data_ptr(), ex.ex_sign.data_ptr(), ex.batch)
+
+    def recommend_scores(self, examples, strategy: str = "best_score"):
+        """The recommend score rows fp32 [B, n_passages] (hrag_reco_scores) of an Examples batch over the engine's passage
+        embeddings: strategy "best_score" or "sum_scores" (include/hrag.h, recommend by example)."""
+        torch = _torch()
+        mode = check_strategy(strategy, True)
+        args = self._reco_args(examples)
+        b = args[-1]
+        out = self._empty((b, self.n_passages), torch.float32)
+        need = int(self._lib.hrag_reco_workspace_bytes(b))
+        ws = getattr(self, "_reco_ws", None)
+        if ws is None or ws.numel() < need or ws.device != self.device:
+            ws = self._reco_ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        check(self._lib.hrag_reco_scores(self._handle, *args, mode, out.data_ptr(), out.stride(0), ws.data_ptr(), ws.numel(),
+                                         _stream()))
+        return out
+
+    def recommend_query(self, examples, return_bits: bool = False):
+        """The average_vector query of an Examples batch (hrag_reco_query): (q, flags) -- q [B, dim] in the dtype this
+        engine's calls take their queries in (bf16 / fp16; fp32 on a split engine, which splits it again exactly), not
+        normalised; flags int32 [B], bit 0: the query has no positive example (q is all zero).  return_bits: (q16, v, flags)
+        with q16 int16 [B, kdim] the 16-bit query as the similarity kernels read it and v fp32 [B, dim] before that
+        rounding."""
+        torch = _torch()
+        args = self._reco_args(examples)
+        b = args[-1]
+        q16 = self._empty((b, self.dim * (3 if self.f32_split else 1)), torch.int16)
+        v = self._empty((b, self.dim), torch.float32)
+        flags = self._empty((b,), torch.int32)
+        check(self._lib.hrag_reco_query(self._handle, *args, q16.data_ptr(), v.data_ptr(), flags.data_ptr(), _stream()))
+        if return_bits:
+            return q16, v, flags
+        return (v if self.f32_split else q16.view(self.emb_dtype)), flags
+
+    def recommend_filter(self, examples, doc_filter=None):
+        """The doc filter of a recommend call with exclusion: int32 words [B, W] -- doc_filter (anything a doc_filter=
+        takes; None: every passage) as one row per query, in a tensor of its own, with the bits of every query's non-empty
+        examples cleared (hrag_reco_exclude).  The caller's filter is left as it is."""
+        torch = _torch()
+        args = self._reco_args(examples)
+        b, n = args[-1], self.n_passages
+        words = (n + 31) // 32
+        if doc_filter is None:
+            w = torch.full((b, words), -1, dtype=torch.int32, device=self.device)
+            if n % 32:
+                w[:, -1] = (1 << (n % 32)) - 1
+        else:
+            fw, fld = self._filter_words(doc_filter, b, own=True)
+            w = (fw.unsqueeze(0).expand(b, -1) if fld == 0 else fw).clone().contiguous()
+        check(self._lib.hrag_reco_exclude(w.data_ptr(), w.stride(0), n, args[1], args[2], args[3], b, _stream()))
+        return w
+
+    def recommend(self, examples, k: int = 200, strategy: str = "best_score", doc_filter=None, exclude_examples: bool = True,
+                  mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None, late=None,
+                  late_candidates: Optional[int] = None, group_agg: Optional[str] = None, group_hits: Optional[int] = None,
+                  boost=None, lexical=None):
+        """Recommend by example: (idx int32, score fp32) [B, k], the k best passages for each query's liked and disliked
+        passage ids -- plus mmr_value / first_score entries as on dense_retrieve.  strategy "best_score" | "sum_scores":
+        the raw recommend rows (recommend_scores) ranked under doc_filter (hrag_topk_rows_ws / hrag_topk_rows_masked), then
+        the mmr and late_rerank seams as retrieve chains them.  "average_vector" IS dense_retrieve(recommend_query(...)),
+        so every option of that call is served.  exclude_examples: the examples themselves are never returned
+        (recommend_filter)."""
+        check_strategy(strategy)
+        self._reco_args(examples)
+        rows_strategy = strategy != "average_vector"
+        mmr = lp = None
+        if rows_strategy:        # (everything is refused before anything is enqueued)
+            for name, v in (("group_agg", group_agg), ("group_hits", group_hits), ("boost", boost), ("lexical", lexical)):
+                if v is not None:
+                    raise ValueError(f"recommend(strategy={strategy!r}) does not serve {name}: it ranks the recommend rows and "
+                                     "keeps no score rows on the handle -- hand recommend_scores to retrieve_scored, or use "
+                                     'strategy="average_vector"')
+            mmr = mmr_plan(mmr_lambda, mmr_candidates, k)
+            lp = late_plan(late, late_candidates, k)
+            self._check_mmr_fits(mmr)
+            self._check_late_fits(lp, mmr)
+            if lp is not None:
+                check_late(lp[0], k, lp[1], examples.batch)
+        filt = self.recommend_filter(examples, doc_filter) if exclude_examples else doc_filter
+        if not rows_strategy:
+            q, _ = self.recommend_query(examples)
+            return self.dense_retrieve(q, k=k, doc_filter=filt, mmr_lambda=mmr_lambda, mmr_candidates=mmr_candidates, late=late,
+                                       late_candidates=late_candidates, group_agg=group_agg, group_hits=group_hits, boost=boost,
+                                       lexical=lexical)
+        c = k if mmr is None else mmr[1]
+        if lp is not None:
+            c = lp[1]
+        rows = self.recommend_scores(examples, strategy)
+        idx, sc = self._rank_rows(rows, c, False, filt)
+        out = RetrieveOutput(idx, sc, None)
+        if lp is not None:
+            self._late_picks(out, lp[0], c if mmr is not None else k)
+        if mmr is not None:
+            self._mmr_picks(out, k, mmr[0])
+        extra = () if out.mmr_value is None else (out.mmr_value,)
+        extra += () if out.first_score is None else (out.first_score,)
+        return (out.doc_idx, out.doc_score) + extra
+
+    def _feedback_blend(self, q_pass, feedback, feedback_weight, feedback_strategy, filter_scope: str = "ranking",
+                        doc_filter=None):
+        """The blended passage score rows fp32 [B, n_passages] of a feedback= call: hrag_sim_scores of q_pass blended in
+        place with the recommend rows, each min-max normalised (hrag_row_minmax, hrag_lex_blend_rows)."""
+        torch = _torch()
+        if check_filter_scope(filter_scope, doc_filter):
+            raise NotImplementedError('filter_scope="seeds" is not served with feedback: the blend\'s two min-maxes would '
+                                      'have to run over the allowed passages -- use filter_scope="ranking"')
+        q = self._q(q_pass)
+        b, n = q.shape[0], self.n_passages
+        check_examples(feedback, b, "feedback")
+        alpha = check_feedback_weight(feedback_weight)
+        rec = self.recommend_scores(feedback, feedback_strategy)
+        src = self.sim_scores("passages", q)
+        mm = [self._empty((b,), torch.float32) for _ in range(4)]
+        check(self._lib.hrag_row_minmax(src.data_ptr(), b, n, src.stride(0), mm[0].data_ptr(), mm[1].data_ptr(), _stream()))
+        check(self._lib.hrag_row_minmax(rec.data_ptr(), b, n, rec.stride(0), mm[2].data_ptr(), mm[3].data_ptr(), _stream()))
+        check(self._lib.hrag_lex_blend_rows(src.data_ptr(), src.stride(0), rec.data_ptr(), rec.stride(0), b, n,
+                                            mm[0].data_ptr(), mm[1].data_ptr(), mm[2].data_ptr(), mm[3].data_ptr(), alpha,
+                                            src.data_ptr(), src.stride(0), _stream()))
+        return src
+
     # ------------------------------------------------------------------ late-interaction reranking
     def set_token_index(self, ix: Optional["TokenIndex"]):
         """The TokenIndex the late= calls of this engine and of its workspaces rescore against (None: none; include/hrag.h,
@@ -1446,6 +1604,17 @@ class HippoRAGEngine:
         doc_filter = kw.pop("doc_filter", None)
         check_filter_scope(kw.get("filter_scope", "ranking"), doc_filter)   # (filter_scope travels in kw to every run)
         lexical, lexical_weight = kw.pop("lexical", None), kw.pop("lexical_weight", 0.5)
+        # feedback: like lexical, the blended rows are formed ONCE (a weight of 0 is the plain call)
+        feedback, feedback_weight = kw.pop("feedback", None), kw.pop("feedback_weight", 0.3)
+        feedback_strategy = kw.pop("feedback_strategy", "best_score")
+        if feedback is not None:
+            if lexical is not None:
+                raise ValueError("feedback together with lexical: both own the blend of the passage scores -- blend the "
+                                 "rows yourself (lexical_scores, recommend_scores) and call retrieve_scored")
+            check_examples(feedback, q.shape[0], "feedback")
+            check_strategy(feedback_strategy, True, "feedback_strategy")
+            if check_feedback_weight(feedback_weight) == 0.0:
+                feedback = None
         # boost: compiled ONCE; every run boosts its own rows by its own program rows (BoostProgram.select)
         boost = kw.pop("boost", None)
         prog = None if boost is None else self._boost_program(boost, q.shape[0])
@@ -1453,6 +1622,9 @@ class HippoRAGEngine:
         # rows of them (a repeat never re-encodes or re-slices the sparse queries)
         blended = None if lexical is None else self._lexical_blend(None, q, lexical, lexical_weight,
                                                                    kw.get("filter_scope", "ranking"), doc_filter)
+        if feedback is not None:
+            blended = self._feedback_blend(q, feedback, feedback_weight, feedback_strategy, kw.get("filter_scope", "ranking"),
+                                           doc_filter)
         # (a PayloadFilter is evaluated ONCE, into words of its own: the repeats of finish() read them after later calls)
         fw, fld = (None, 0) if doc_filter is None else self._filter_words(doc_filter, q.shape[0], own=True)
 
@@ -1753,9 +1925,10 @@ class HippoRAGEngine:
         return bool(o.value)
 
     def shard_finish(self, mn, mx, flags, k: int, want_residual: bool = False, doc_filter=None, boost=None, late=None,
-                     late_candidates=None):
+                     late_candidates=None, feedback=None, recommend=None):
         """doc_filter: the GLOBAL filter ([B, n_passages of the whole index] or packed); the shard reads its slice."""
         refuse_boost("shard_finish", {"boost": boost})
+        refuse_reco("shard_finish", {"feedback": feedback, "recommend": recommend})
         refuse_late("shard_finish", {"late": late, "late_candidates": late_candidates})
         torch = _torch()
         b = mn.shape[0]
@@ -1794,6 +1967,7 @@ class CapturedPipeline:
         refuse_lexical("CapturedPipeline", retrieve_kw)
         refuse_boost("CapturedPipeline", retrieve_kw)
         refuse_late("CapturedPipeline", retrieve_kw)
+        refuse_reco("CapturedPipeline", retrieve_kw)
         self.engine, self.batch = engine, int(batch)
         dev, dt = engine.device, engine.emb_dtype
         self._qf = torch.zeros((batch, engine.dim), dtype=dt, device=dev)

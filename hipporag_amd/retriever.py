@@ -210,6 +210,11 @@ class RetrievalConfig:
                                          # retrieve() / retrieve_dpr() / rag_qa() rank max(this, num_to_retrieve) entries, rescore
                                          # them by MaxSim over the token vectors and return the best by late score; None: off
     late_dtype: str = "bf16"             # the 16-bit type of the token vectors on the device: "bf16" or "fp16"
+    feedback_weight: float = 0.3         # recommend by example (include/hrag.h): the weight in [0, 1] of the recommend rows of
+                                         # retrieve(like=, unlike=) in the passage scores (relevance feedback into the prior)
+    recommend_strategy: str = "best_score"   # "best_score" / "sum_scores" ("average_vector": recommend() only, refused by
+                                         # retrieve(like=)): how the
+                                         # liked and disliked passages of recommend() and retrieve(like=, unlike=) are scored
     boost: Optional[list] = None         # boosted retrieval (include/hrag.h): the default boost of every retrieve call, one list
                                          # of items in the grammar of boost.compile_boosts over the chunk-metadata columns
                                          # (needs payload_index=True); None: no boost
@@ -422,7 +427,8 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
                           group_hits: Optional[int] = None, keep_all_scores: bool = False,
                           mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None,
                           lexical_encode: Optional[Callable] = None, lexical_weight: float = 0.0, boost=None,
-                          late_encode: Optional[Callable] = None, late_candidates: Optional[int] = None):
+                          late_encode: Optional[Callable] = None, late_candidates: Optional[int] = None,
+                          feedback=None, feedback_weight: float = 0.0, feedback_strategy: str = "best_score"):
     """The body of retrieve() (HippoRAG.py:459-480), shared by the mirror class below and by
     reference_adapter.attach(): phase A on the device, the recognition-memory filter on the host (rerank_facts
     :1659-1707), phase B on the device, in batches of eng.max_batch queries.  Yields (offset of the batch, [(doc ids,
@@ -463,6 +469,9 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
     max(late_candidates, want) entries, rescores them and returns the `want` best by late score -- doc scores are the late
     scores, rows.first_score [b, want] each entry's first-stage score.  Not with group_agg or beyond max_topk; with
     mmr_lambda MMR picks among the rescored entries (mmr_candidates is then not used).
+    feedback / feedback_weight / feedback_strategy (include/hrag.h, recommend by example): an Examples over ALL the queries;
+    with a weight above 0 every batch's phase B gets feedback= with its own rows of it (Examples.select); with 0, or without
+    examples, its arguments are exactly the plain ones.
     keep_all_scores: rows.all_scores is the device tensor of every passage's score of the batch and rows.repeated tells
     whether the contract ran rows again (retrieve_fused: the engine's own score rows are then not the batch's)."""
     import torch
@@ -506,6 +515,14 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
     if scoped and lexical_encode is not None and lexical_weight > 0:
         raise NotImplementedError('filter_scope="seeds" is not served with lexical_weight > 0: the blend\'s min-maxes run over '
                                   'every passage -- use filter_scope="ranking"')
+    if feedback is not None and feedback_weight > 0:
+        if lexical_encode is not None and lexical_weight > 0:
+            raise ValueError("like / unlike together with lexical_weight > 0: both own the blend of the passage scores")
+        if scoped:
+            raise NotImplementedError('filter_scope="seeds" is not served with like / unlike: the blend\'s min-maxes run over '
+                                      'every passage -- use filter_scope="ranking"')
+        if feedback.batch != len(queries):
+            raise ValueError(f"like / unlike hold {feedback.batch} queries, the call {len(queries)}")
     if scoped and use_facts and not getattr(eng, "has_fact_sources", False):
         raise ValueError('filter_scope="seeds" needs the fact -> passage table on the engine (set_fact_sources)')
     two_halves = hasattr(eng, "retrieve_converged_start")
@@ -585,6 +602,9 @@ def iter_batched_retrieve(eng, queries: List[str], q_tensor: Callable, facts: Se
             kw.update(late=late_encode(qs), late_candidates=late_c)
         if boost is not None:
             kw["boost"] = boost.select(range(bt.lo, bt.lo + b))
+        if feedback is not None and feedback_weight > 0:
+            kw.update(feedback=feedback.select(range(bt.lo, bt.lo + b)), feedback_weight=feedback_weight,
+                      feedback_strategy=feedback_strategy)
         if two_halves:
             bt.pending = eng.retrieve_converged_start(*args, **kw)
             o = bt.pending.out
@@ -1191,6 +1211,99 @@ class HippoRAG:
             raise ValueError(f"{who} does not serve lexical_weight={w}: it fuses the score rows of plain member calls -- use "
                              "retrieve(lexical_weight=...)")
 
+    # ------------------------------------------------------------------ recommend by example
+    def _doc_positions(self, docs, who: str) -> List[int]:
+        """The passage positions of document strings or chunk hash ids; an unknown document raises."""
+        t = getattr(self, "_pos_table", None)
+        if t is None or t[0] is not self.passage_node_keys or t[1] != len(self.passage_node_keys):
+            table = {}
+            for i, (key, text) in enumerate(zip(self.passage_node_keys, self.passage_texts)):
+                table.setdefault(text, i)
+                table[key] = i
+            t = self._pos_table = (self.passage_node_keys, len(self.passage_node_keys), table)
+        out = []
+        for d in docs:
+            if d not in t[2]:
+                raise ValueError(f"{who}: unknown document {str(d)[:60]!r} (a passage string or a chunk hash id of the index "
+                                 "expected)")
+            out.append(t[2][d])
+        return out
+
+    def _examples(self, positive, negative, n_queries: Optional[int], who: str):
+        """per-query lists of liked / disliked documents -> an engine Examples (None when both are None)"""
+        from .reco import Examples
+        if positive is None and negative is None:
+            return None
+        n = len(positive if positive is not None else negative) if n_queries is None else n_queries
+        pos = [[] for _ in range(n)] if positive is None else list(positive)
+        neg = [[] for _ in range(n)] if negative is None or len(negative) == 0 else list(negative)
+        if len(pos) != n or len(neg) != n:
+            raise ValueError(f"{who}: one list of documents per query expected ({len(pos)} liked and {len(neg)} disliked lists "
+                             f"for {n} queries)")
+        if any(isinstance(x, str) for x in pos + neg):
+            raise ValueError(f"{who}: per-query LISTS of documents expected, not bare strings")
+        device = getattr(self.engine, "device", None)
+        return Examples.from_lists([self._doc_positions(x, who) for x in pos], [self._doc_positions(x, who) for x in neg],
+                                   device=device)
+
+    def _feedback(self, like, unlike, feedback_weight, n_queries: int) -> dict:
+        """The keywords of relevance feedback for the batch pipeline ({} without examples or at weight 0)."""
+        from .reco import check_feedback_weight, check_strategy
+        ex = self._examples(like, unlike, n_queries, "retrieve(like=, unlike=)")
+        if ex is None:
+            return {}
+        w = check_feedback_weight(self.global_config.feedback_weight if feedback_weight is None else feedback_weight)
+        strategy = self.global_config.recommend_strategy
+        if strategy == "average_vector":
+            raise ValueError('retrieve(like=, unlike=) does not serve RetrievalConfig.recommend_strategy="average_vector": '
+                             'relevance feedback blends score ROWS into the passage scores -- set "best_score" or '
+                             '"sum_scores" (recommend() serves the query strategy)')
+        check_strategy(strategy, True, "recommend_strategy")
+        return {"feedback": ex, "feedback_weight": w, "feedback_strategy": strategy} if w > 0 else {}
+
+    @staticmethod
+    def _refuse_like(who: str, like, unlike) -> None:
+        for name, v in (("like", like), ("unlike", unlike)):
+            if v is not None:
+                raise ValueError(f"{who} does not serve {name}: relevance feedback blends the recommend rows into the passage "
+                                 "scores of one plain call -- use retrieve(like=..., unlike=...)")
+
+    def recommend(self, positive, negative=(), num_to_retrieve: Optional[int] = None, strategy: Optional[str] = None,
+                  doc_filter=None, exclude_examples: bool = True, mmr_lambda: Optional[float] = None):
+        """Recommend by example (include/hrag.h): "more like these passages, less like those", no query string.  positive /
+        negative: per-query lists of document strings or chunk hash ids (an unknown document raises); strategy (default
+        RetrievalConfig.recommend_strategy): "best_score", "sum_scores" or "average_vector"; doc_filter as in retrieve();
+        exclude_examples: the examples themselves are never returned; mmr_lambda as in retrieve().  Returns QuerySolutions
+        whose question is None and whose entries carry "recommended": strategy in their metadata."""
+        from .reco import check_strategy
+        cfg = self.global_config
+        self._ensure_ready()
+        strategy = cfg.recommend_strategy if strategy is None else strategy
+        check_strategy(strategy)
+        ex = self._examples(positive, negative, None, "recommend")
+        n_p = len(self.passage_node_keys)
+        want = max(1, min(int(cfg.retrieval_top_k if num_to_retrieve is None else num_to_retrieve), n_p))
+        if want > self.engine.max_topk:
+            raise ValueError(f"recommend: num_to_retrieve={want} exceeds the engine's max_topk={self.engine.max_topk}")
+        words = self._doc_filter_words(doc_filter, ex.batch)
+        results: List[QuerySolution] = []
+        for lo in range(0, ex.batch, self.engine.max_batch):
+            b = min(self.engine.max_batch, ex.batch - lo)
+            out = self.engine.recommend(ex.select(range(lo, lo + b)), k=want, strategy=strategy,
+                                        doc_filter=None if words is None else scope_rows(words, lo, b),
+                                        exclude_examples=exclude_examples, mmr_lambda=mmr_lambda)
+            d_idx, d_sc = out[0].cpu().numpy(), out[1].cpu().numpy()
+            rows = BatchRows((d_idx[i], d_sc[i], []) for i in range(b))
+            rows.doc_idx = None                     # (entries of -1 are dropped one query at a time)
+            sols = self._build_query_solutions([None] * b, rows, want)
+            if mmr_lambda is not None:
+                self._mmr_metadata(sols, out[2].cpu().numpy())
+            for s_ in sols:
+                for d in s_.doc_metadata:
+                    d["recommended"] = strategy
+            results.extend(sols)
+        return results
+
     def _boost(self, boost, n_queries: int, who: str = "retrieve"):
         """None, or the BoostProgram of a call's boost= (default RetrievalConfig.boost): one list of items for every query
         or one list per query, compiled against the payload index (which _ensure_ready has built)."""
@@ -1550,8 +1663,14 @@ class HippoRAG:
                  gold_docs: Optional[List[List[str]]] = None, doc_filter=None, filter_scope: Optional[str] = None,
                  group_by=None, group_agg: Optional[str] = None, group_hits: Optional[int] = None,
                  mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None,
-                 lexical_weight: Optional[float] = None, boost=None, late_candidates: Optional[int] = None):
-        """late_candidates (default RetrievalConfig.late_candidates; include/hrag.h, late-interaction reranking; needs
+                 lexical_weight: Optional[float] = None, boost=None, late_candidates: Optional[int] = None,
+                 like=None, unlike=None, feedback_weight: Optional[float] = None):
+        """like / unlike (include/hrag.h, recommend by example): per-query lists of documents (strings or chunk hash ids) the
+        reader judged useful / off-topic; their recommend rows (RetrievalConfig.recommend_strategy) are blended into the
+        passage scores that feed the passage prior at feedback_weight (default RetrievalConfig.feedback_weight), exactly as
+        lexical_weight blends the BM25 rows -- not together with it, not with filter_scope="seeds".  The examples are not
+        excluded: doc_filter decides.  Every entry's metadata then carries "feedback_weight".
+        late_candidates (default RetrievalConfig.late_candidates; include/hrag.h, late-interaction reranking; needs
         token_encoder=): every query ranks max(late_candidates, num_to_retrieve) entries as below, the token vectors of the
         query string are scored against theirs by MaxSim on the device and the docs come in late order: doc_scores are the
         late scores and every entry's metadata carries "late_score" and "first_score".  Not with group_by or more documents
@@ -1596,9 +1715,13 @@ class HippoRAG:
         late = self._late(late_candidates)
         if late and agg is not None:
             raise ValueError("retrieve does not serve late_candidates with group_by: a group's score is not a passage's")
+        fb = self._feedback(like, unlike, feedback_weight, len(queries))
+        if fb and lex:
+            raise ValueError("retrieve does not serve like / unlike together with lexical_weight > 0: both own the blend of "
+                             "the passage scores")
         self.get_query_embeddings(queries)
         results: List[QuerySolution] = []
-        self._retrieve_into(results, queries, num_to_retrieve, words, scope, agg, table, hits, mmr, lex, prog, late)
+        self._retrieve_into(results, queries, num_to_retrieve, words, scope, agg, table, hits, mmr, lex, prog, late, fb)
         self.all_retrieval_time += time.time() - t_start
         logger.info("Total Retrieval Time %.2fs", self.all_retrieval_time)
         logger.info("Total Recognition Memory Time %.2fs", self.rerank_time)
@@ -1608,12 +1731,13 @@ class HippoRAG:
         return results
 
     def _retrieve_into(self, results, queries, num_to_retrieve, doc_filter=None, filter_scope: str = "ranking",
-                       group_agg=None, table=None, group_hits=None, mmr=None, lex=None, boost=None, late=None):
+                       group_agg=None, table=None, group_hits=None, mmr=None, lex=None, boost=None, late=None, fb=None):
         cfg = self.global_config
         extra = {} if doc_filter is None else {"doc_filter": doc_filter, "filter_scope": filter_scope}
         extra.update(mmr or {})
         extra.update(lex or {})
         extra.update(late or {})
+        extra.update(fb or {})
         if boost is not None:
             extra["boost"] = boost
         if group_agg is not None:
@@ -1638,6 +1762,10 @@ class HippoRAG:
                 self._lexical_metadata(sols, lex)
                 self._boost_metadata(sols, boost)
                 self._late_metadata(sols, getattr(rows, "first_score", None))
+                if fb:
+                    for s_ in sols:
+                        for d in s_.doc_metadata:
+                            d["feedback_weight"] = fb["feedback_weight"]
                 results.extend(sols)
 
     # ------------------------------------------------------------------ fused retrieval
@@ -1645,7 +1773,8 @@ class HippoRAG:
                        rrf_depth: Optional[int] = None, num_to_retrieve: Optional[int] = None, doc_filter=None,
                        filter_scope: Optional[str] = None, group_by=None, group_agg: Optional[str] = None,
                        group_hits: Optional[int] = None, mmr_lambda: Optional[float] = None,
-                       mmr_candidates: Optional[int] = None, boost=None, late_candidates: Optional[int] = None):
+                       mmr_candidates: Optional[int] = None, boost=None, late_candidates: Optional[int] = None,
+                       like=None, unlike=None):
         """One ranked list per QUESTION, each question given as several sub-queries -- a decomposition, paraphrases, the
         thoughts of an IRCoT chain (include/hrag.h, fused retrieval).  Every sub-query runs phase A and phase B as in
         retrieve(); the score rows of a question's sub-queries are fused ON THE DEVICE over all passages -- fuse="sum"
@@ -1658,6 +1787,7 @@ class HippoRAG:
         from .engine import check_fuse
         self._refuse_mmr("retrieve_fused", mmr_lambda, mmr_candidates)
         self._refuse_late("retrieve_fused", late_candidates)
+        self._refuse_like("retrieve_fused", like, unlike)
         self._refuse_lexical("retrieve_fused")
         if boost is not None or self.global_config.boost is not None:
             raise ValueError("retrieve_fused does not serve boost: it fuses the score rows of plain member calls -- use "
@@ -1771,7 +1901,7 @@ class HippoRAG:
                        doc_filter=None, filter_scope: Optional[str] = None, group_by=None,
                        group_agg: Optional[str] = None, mmr_lambda: Optional[float] = None,
                        mmr_candidates: Optional[int] = None, lexical_weight: Optional[float] = None, boost=None,
-                       late_candidates: Optional[int] = None):
+                       late_candidates: Optional[int] = None, like=None, unlike=None):
         """Iterative retrieval: alternate retrieval and one reasoning step per query, merging the document
         scores by max (:526-543).  reason_fn(query, ranked_docs, thoughts) -> str stands for
         utils/qa_utils.reason_step (the IRCoT prompt + reader LLM are outside this package).  The reference
@@ -1782,6 +1912,7 @@ class HippoRAG:
         (default RetrievalConfig.boost): every step's retrieve() takes it, a per-query one cut to the step's queries."""
         self._refuse_mmr("retrieve_ircot", mmr_lambda, mmr_candidates)
         self._refuse_late("retrieve_ircot", late_candidates)
+        self._refuse_like("retrieve_ircot", like, unlike)
         if max_qa_steps < 1:
             raise ValueError("max_qa_steps must be at least 1.")
         if max_qa_steps > 1 and reason_fn is None:
@@ -1878,7 +2009,8 @@ class HippoRAG:
                      gold_docs: Optional[List[List[str]]] = None, doc_filter=None, filter_scope: Optional[str] = None,
                      group_by=None, group_agg: Optional[str] = None, group_hits: Optional[int] = None,
                      mmr_lambda: Optional[float] = None, mmr_candidates: Optional[int] = None,
-                     lexical_weight: Optional[float] = None, boost=None, late_candidates: Optional[int] = None):
+                     lexical_weight: Optional[float] = None, boost=None, late_candidates: Optional[int] = None,
+                     like=None, unlike=None):
         """late_candidates: as in retrieve(), over the dense ranking; then not with group_by, lexical_weight, boost or more
         documents than the engine's max_topk (ValueError naming late_candidates).
         Dense retrieval; doc_filter / filter_scope as in retrieve() ("seeds": the scores are normalised over the
@@ -1889,7 +2021,9 @@ class HippoRAG:
         filter_scope="seeds" or more documents than the engine's max_topk (ValueError naming lexical_weight).
         boost (default RetrievalConfig.boost): the ranking of the boosted min-max scores
         (HippoRAGEngine.dense_retrieve(boost=)); then not with group_by, mmr_lambda, lexical_weight, filter_scope="seeds" or
-        more documents than the engine's max_topk (ValueError naming boost)."""
+        more documents than the engine's max_topk (ValueError naming boost).
+        like / unlike are refused by name: use retrieve(), or recommend()."""
+        self._refuse_like("retrieve_dpr", like, unlike)
         cfg = self.global_config
         if num_to_retrieve is None:
             num_to_retrieve = cfg.retrieval_top_k

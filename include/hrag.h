@@ -79,7 +79,9 @@ extern "C" {
  *        later in 0.8 (detect by the symbol): facets -- hrag_payload_facet, hrag_payload_facet_ids,
  *        hrag_payload_facet_ws_bytes;
  *        later in 0.8 (detect by the symbol): late-interaction reranking -- hrag_late_create, hrag_late_destroy,
- *        hrag_late_scores, hrag_late_rank_rows, hrag_late_workspace_bytes, hrag_late_rerank. */
+ *        hrag_late_scores, hrag_late_rank_rows, hrag_late_workspace_bytes, hrag_late_rerank;
+ *        later in 0.8 (detect by the symbol): recommend by example -- hrag_reco_rows, hrag_reco_workspace_bytes,
+ *        hrag_reco_scores_rows, hrag_reco_scores, hrag_reco_query, hrag_reco_exclude. */
 #define HRAG_VERSION_MAJOR 0
 #define HRAG_VERSION_MINOR 8
 
@@ -900,6 +902,96 @@ hrag_status hrag_late_rerank(const hrag_late *ix, const int32_t *q_ptr, const in
                              int32_t batch, const int32_t *cand_idx_dev, int32_t c, int32_t k, int32_t *sel_out_dev,
                              int32_t *idx_out_dev, float *score_out_dev, void *workspace_dev, size_t workspace_bytes,
                              hrag_stream stream);
+
+/* ---- recommend by example: score rows from liked and disliked passage ids, no query vector ----
+ * Every ranking above starts from a query vector.  "More like these passages, less like those" (the recommend call of
+ * vector databases, more_like_this of search engines) starts from passage ids: a reader's relevance feedback, a user's
+ * liked and dismissed results.  One query b has a list of EXAMPLES ex_idx[ex_ptr[b] .. ex_ptr[b + 1]) with ex_sign +1
+ * (positive) or -1 (negative), all int32.  The ids are passage positions; an id outside [0, n_passages) or a sign 0 is an
+ * EMPTY example: it contributes nothing (it is skipped, not scored as 0).  Repeats are legal.  At most
+ * HRAG_RECO_MAX_EXAMPLES examples of a query are read, later ones are ignored on the device, as HRAG_LEX_MAX_QUERY_TERMS
+ * is (the Python binding refuses longer lists).
+ * s(p, e) is the score hrag_sim_gemm gives passage row p with embedding row ex_idx[e] used as the QUERY -- the same
+ * v_mfma_f32_16x16x32 chain: BK = 64 steps of two MFMAs in ascending k into one fp32 accumulator, the k tail zero-filled
+ * in 8-element chunks; on a split engine the query side reads the stored [hi | lo | hi] row's thirds in the order
+ * (0, 2, 1): exactly what hrag_gram_rows promises.  (hrag_sim_gemm itself serves batches of one or two queries by a
+ * dot-product kernel with another summation order; "the score hrag_sim_gemm gives" is that of a batch of three or more.)
+ * The score rows are out[b][p] for every p in [0, n_passages); columns beyond n_passages are not touched.
+ * HRAG_RECO_BEST_SCORE (Qdrant's best_score):
+ *     bp = bn = -inf
+ *     for each positive in list order: if (s > bp) bp = s
+ *     for each negative in list order: if (s > bn) bn = s        plain >, so a NaN is never taken
+ *     out = bp > bn ? bp : -(bn * bn)                             one fp32 product
+ *   No examples at all gives -inf.
+ * HRAG_RECO_SUM_SCORES:
+ *     acc = +0.0 (fp64);  acc += (double)s for the positives in list order;  acc -= (double)s for the negatives in list
+ *     order;  out = acc rounded once to fp32.  A NaN result is the quiet NaN 0x7fc00000, as in hrag_fuse_rows.
+ * HRAG_RECO_AVERAGE_VECTOR produces no rows but a QUERY per b, which then goes through the ordinary calls.  Per
+ *   component k, in fp64 with every operation rounded on its own and no contraction:
+ *     a = (sum over the positives in list order of value(e, k)) / n_pos;   g = the same over the negatives;
+ *     v = a + (a - g) when n_neg > 0, v = a when n_neg == 0
+ *   value is the stored 16-bit value, or hi + lo on a split engine.  v is rounded to fp32 and then written as the
+ *   engine's query type: bf16 / fp16 round-to-nearest-even, or [qhi | qhi | qlo] exactly as hrag_split_f32(as_query = 1)
+ *   makes it from that fp32 vector.  It is not normalised: every ranking here is invariant to a positive scale of the
+ *   query, so the returned scores are dot products with v, not cosines.  n_pos == 0 gives the all-zero query and sets
+ *   bit 0 of flags_out[b].
+ * EXCLUSION: the doc filter of query b with the bits of its non-empty example ids cleared (every strategy): a call
+ *   without a filter starts from all n bits set, a filter given as one shared row (ld 0) is expanded to one row per query
+ *   first -- both by the caller; hrag_reco_exclude clears the bits.
+ * No atomics; every output word is written once, by plain vector stores; results are bitwise reproducible at any batch
+ * and at any position in it (csrc/reco.hip). */
+#define HRAG_RECO_MAX_EXAMPLES 32
+#define HRAG_RECO_TILE 128          /* passages per workgroup of the fused kernel */
+#define HRAG_RECO_BEST_SCORE 0
+#define HRAG_RECO_SUM_SCORES 1
+#define HRAG_RECO_AVERAGE_VECTOR 2  /* hrag_reco_query; not a mode of the row calls */
+
+/* The reduce alone, engine-free, over caller-supplied example score rows ex_scores_dev fp32 [E, ld] (row ex_ptr[b] + e
+ * holds s(., e) of query b's example e): out_dev fp32 [batch, ld_out], n columns each.  ex_ptr_dev int32 [batch + 1] and
+ * ex_sign_dev int32 [E] on the device; there are no ids here: an empty example is a sign 0; there is no host ex_ptr
+ * either: the device-side one is taken as it is, a range cut at HRAG_RECO_MAX_EXAMPLES.  mode: HRAG_RECO_BEST_SCORE
+ * or HRAG_RECO_SUM_SCORES.  HRAG_EINVAL: a NULL pointer, a bad mode, batch outside [1, 65535], ld or ld_out below n. */
+hrag_status hrag_reco_rows(const float *ex_scores_dev, int64_t ld, const int32_t *ex_ptr_dev, const int32_t *ex_sign_dev,
+                           int32_t batch, int64_t n, int32_t mode, float *out_dev, int64_t ld_out, hrag_stream stream);
+
+/* Bytes of workspace the fused calls need (16-byte aligned device memory, scratch only): the column table -- (id, sign)
+ * of the 32 columns of every query -- and the example counts.  Negative on a bad argument. */
+int64_t hrag_reco_workspace_bytes(int32_t batch);
+
+/* The fused product-and-reduce, engine-free: emb_dev the 16-bit rows [rows, kdim] (dtype, kdim, split as in
+ * hrag_gram_rows); ex_ptr is read on the HOST (ex_ptr[0] == 0, ascending: checked before anything is enqueued) and
+ * ex_ptr_dev is the same array on the device, which the kernels read (were it to differ, its ranges are clamped to
+ * ex_ptr[batch] examples and the cap); ex_idx_dev / ex_sign_dev int32 [ex_ptr[batch]].  out_dev fp32 [batch, ld],
+ * ld >= rows.  Bit-identical to gathering the example rows (on split: as queries [hi | hi | lo]), hrag_sim_gemm of three
+ * or more of them into [E, rows], and hrag_reco_rows with the empty examples' signs 0 -- the [E, rows] matrix stays in
+ * MFMA accumulators.  Nothing is allocated, synchronised or read back. */
+hrag_status hrag_reco_scores_rows(const uint16_t *emb_dev, int64_t rows, int32_t kdim, int32_t dtype, int32_t split,
+                                  const int32_t *ex_ptr, const int32_t *ex_ptr_dev, const int32_t *ex_idx_dev,
+                                  const int32_t *ex_sign_dev, int32_t batch, int32_t mode, float *out_dev, int64_t ld,
+                                  void *workspace_dev, size_t workspace_bytes, hrag_stream stream);
+
+/* The same over the engine's passage embeddings.  It reads only the index half, so it works on a workspace handle.  The
+ * usual one-call-per-handle and stream rules.  HRAG_EINVAL (nothing enqueued, outputs untouched): a row-shard engine, an
+ * engine without passage embeddings, batch outside [1, max_batch], a bad mode, a NULL pointer, a short or misaligned
+ * workspace. */
+hrag_status hrag_reco_scores(hrag_engine *e, const int32_t *ex_ptr, const int32_t *ex_ptr_dev, const int32_t *ex_idx_dev,
+                             const int32_t *ex_sign_dev, int32_t batch, int32_t mode, float *out_dev, int64_t ld,
+                             void *workspace_dev, size_t workspace_bytes, hrag_stream stream);
+
+/* HRAG_RECO_AVERAGE_VECTOR: q_out_dev 16-bit [batch, kdim] (kdim = dim, or 3 * dim on a split engine) in the layout the
+ * similarity kernels take a query in; q_f32_out_dev fp32 [batch, dim] (may be NULL) the same vector before the last
+ * rounding -- what a split engine's calls take as their query; flags_out_dev int32 [batch].  Refusals as above. */
+hrag_status hrag_reco_query(hrag_engine *e, const int32_t *ex_ptr, const int32_t *ex_ptr_dev, const int32_t *ex_idx_dev,
+                            const int32_t *ex_sign_dev, int32_t batch, uint16_t *q_out_dev, float *q_f32_out_dev,
+                            int32_t *flags_out_dev, hrag_stream stream);
+
+/* Clears, in row b of words_dev uint32 [batch, ld_words] (one row per query, ld_words >= ceil(n / 32)), the bits of query
+ * b's non-empty examples: ids in [0, n) whose sign is not 0 (ex_sign_dev NULL: every id in [0, n)).  One thread per query,
+ * plain loads and stores: a row has one writer.  A repeated id is harmless, every other bit and word is left alone.  As in
+ * hrag_reco_rows there is no host ex_ptr here, so the device-side ex_ptr is taken as it is (a negative start reads from 0,
+ * a range is cut at HRAG_RECO_MAX_EXAMPLES): only the fused calls and hrag_reco_query clamp it to the host's total. */
+hrag_status hrag_reco_exclude(uint32_t *words_dev, int64_t ld_words, int64_t n, const int32_t *ex_ptr_dev,
+                              const int32_t *ex_idx_dev, const int32_t *ex_sign_dev, int32_t batch, hrag_stream stream);
 
 /* ---- lexical retrieval: sparse-vector (BM25, learned term weights) scores blended into the dense scores ----
  * Every score above starts from the cosine of dense embeddings, which smears the rare surface forms a multi-hop question
